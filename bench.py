@@ -2,6 +2,12 @@
 """Benchmark: 8192-point clouds per second through the PointNet++ SA + FP geometric path.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg5] [--batch B]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs)
+and prints the result line. --full adds, after the timed steps, every other leg: the oracle check
+of each buffer set's last step (`verified`), the un-pipelined latency, the whole-model `e2e`
+field, the measured copy peak and the CPU baseline (each with its own switch below).
 
 One step = every geometric op of the SSG SA x4 + FP x4 stack (stack.py) over one batch of
 B clouds per GPU (cfg2: B = 16 ScanNet-crop clouds of 8192 points, BASELINE.json configs[1]).
@@ -336,6 +342,35 @@ def verify_sets(config, runs, threads):
                        "copies; rtol=atol=1e-5 interpolated features / attention)"}
 
 
+DUMP_MAX_BYTES = 64 * 1024 * 1024
+DUMP_SEED = 20240229
+
+
+def dump_outputs(outs, out_dir, suffix="", max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: the tensors the timed path returned from its last step (Step.outputs():
+    what a caller of the step receives), as <out_dir>/out<i><suffix>.npy, float32 (float64 for
+    a non-float32 tensor). All files together stay under max_bytes: every array gets an
+    equal share, and a larger one is stored as a fixed sample of its flattened elements (sorted
+    indices drawn with DUMP_SEED, the same for equal shapes from run to run), so two builds
+    are compared element for element. Returns what was written, by file name."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = max_bytes // max(1, len(outs)) - 4096  # (the .npy header)
+    written = {}
+    for i, t in enumerate(outs):
+        a = t.detach().cpu().numpy()
+        a = a if a.dtype == np.float32 else a.astype(np.float64)
+        keep = share // a.dtype.itemsize
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": a.size > keep}
+        if a.size > keep:
+            rng = np.random.default_rng(DUMP_SEED + i)
+            a = a.reshape(-1)[np.sort(rng.integers(0, a.size, size=keep))]
+        name = f"out{i:02d}{suffix}.npy"
+        np.save(os.path.join(out_dir, name), np.ascontiguousarray(a))
+        written[name] = entry
+    return written
+
+
 def _e2e_child(args, e2e):
     """The whole-model measurement in a child process (`bench.py --model`, same config, queues
     and steps). HIP maps streams to hardware queues round-robin in creation order, so in the
@@ -440,6 +475,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--config", default="cfg2", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=None, help="clouds per GPU (default: config's)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed step's outputs to "
+                         "DIR/out<i>.npy (dump_outputs: float32 / float64, at most 64 MB in all, "
+                         "larger arrays as a fixed seeded sample); inputs are the same from run "
+                         "to run, so two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: the oracle check of "
+                         "each buffer set's last step (verified), the un-pipelined latency, the "
+                         "whole-model e2e field, the measured copy peak and the CPU baseline "
+                         "(--no-verify, --latency-reps, --e2e-steps, --no-cpu-baseline switch "
+                         "them singly). Without it a run only sets up, warms up, times the "
+                         "steps and prints the line; those fields are then null or absent")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-threads", type=int, default=None,
                     help="threads of the multi-threaded CPU baseline leg (default: the box's "
@@ -519,6 +566,9 @@ def main():
                          "ranks timing and the checksum gather run as in the real bench; no "
                          "kernels, value = null (tests/test_bench_launcher.py)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: only what the headline figure needs
+        args.no_verify = args.no_cpu_baseline = True
+        args.latency_reps = args.e2e_steps = 0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU: start the ranks as children BEFORE anything touches the GPU
         # (this process never initialises HIP), and exit with the launcher's status
@@ -663,6 +713,9 @@ def main():
         # a fault raises here, so a fast but wrong line is never printed
         post["fault_status"] = pipe.check_faults() if pipelined else \
             pkg._lib.check_device_faults(dev) or 0
+        if args.dump_outputs and model == args.model:  # (not the e2e leg's step)
+            post["dumped"] = dump_outputs(outs, args.dump_outputs,
+                                          f".rank{rank}" if world > 1 else "")
         if not model and args.diag_only is None and not args.no_verify:
             runs = (pipe.outputs_by_set() if pipelined else
                     [(inp, (graph.step if graph is not None else step).outputs(),
@@ -743,7 +796,7 @@ def main():
                     "frac": achieved / HBM_PEAK_GBPS}
         result = {
             "metric": METRIC, "value": value, "unit": "clouds/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup,
+            "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic: SplitMix64 ScanNet-crop clouds (8192 drawn with replacement from "
@@ -805,7 +858,9 @@ def main():
             result["e2e"] = e2e
         if args.diag_only:
             result["diagnostic"] = f"only the {args.diag_only} of each step ran: not a benchmark result"
-        if world == 1 and not args.model:
+        if args.dump_outputs:
+            result["dumped_outputs"] = {"dir": args.dump_outputs, "files": post.get("dumped")}
+        if world == 1 and not args.model and args.full:
             try:  # (outside the timed region, after it)
                 result["roofline"]["hbm"]["copy_peak_measured"] = copy_peak(dev)
             except Exception as e:  # a reported figure, never the product

@@ -21,7 +21,7 @@ fi
 
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
   echo "== bench"
-  timeout -k 10 ${BENCH_TIMEOUT:-600} python bench.py ${BENCH_ARGS:-} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+  timeout -k 10 ${BENCH_TIMEOUT:-600} python bench.py --full ${BENCH_ARGS:-} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
   rc=$?; cat $OUT/bench_$TAG.json; tail -5 $OUT/bench_$TAG.err; echo "bench rc=$rc"
   [ $rc -eq 0 ] || exit $rc
 fi

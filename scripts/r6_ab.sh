@@ -8,7 +8,7 @@ mkdir -p $OUT
 for r in $(seq 1 ${REPS:-2}); do
   for n in ${ABS:-A B}; do
     v="ARGS_$n"; e="ENV_$n"
-    env ${!e} timeout -k 10 300 python3 bench.py --steps ${STEPS:-500} --no-cpu-baseline --e2e-steps 0 ${!v} > $OUT/ab_${n}_$r.json 2> $OUT/ab_${n}_$r.err || { tail -20 $OUT/ab_${n}_$r.err; exit 1; }
+    env ${!e} timeout -k 10 300 python3 bench.py --steps ${STEPS:-500} --full --no-cpu-baseline --e2e-steps 0 ${!v} > $OUT/ab_${n}_$r.json 2> $OUT/ab_${n}_$r.err || { tail -20 $OUT/ab_${n}_$r.err; exit 1; }
   done
 done
 for f in $OUT/ab_*.json; do

@@ -11,7 +11,7 @@ for n in $(seq 1 ${REP:-3}); do
     for run in "drv:--gpus 1 --steps 20 --warmup 5" "c500:--steps 500" "cfg5:--config cfg5"; do
       tag=${run%%:*}; a=${run#*:}
       f=$OUT/${tag}_${v}_$n.json
-      timeout -k 10 300 python3 bench.py $a --no-cpu-baseline --e2e-steps 0 > $f 2> $f.err || { tail -20 $f.err; exit 1; }
+      timeout -k 10 300 python3 bench.py $a --full --no-cpu-baseline --e2e-steps 0 > $f 2> $f.err || { tail -20 $f.err; exit 1; }
       python3 -c "import json; d=json.loads(open('$f').read().strip().splitlines()[-1]); print('$tag $v $n', round(d['value']), round(d['roofline']['avg_launch_ms'],4), d.get('verified'), d.get('fault_status'))"
     done
   done

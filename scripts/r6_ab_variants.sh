@@ -12,7 +12,7 @@ for n in $(seq 1 ${REP:-2}); do
     timeout -k 10 200 python3 tools/bench_sampler.py > $OUT/sampler_${v}_$n.json 2> $OUT/sampler_${v}_$n.err || { tail -20 $OUT/sampler_${v}_$n.err; exit 1; }
     echo "sampler $v $n $(tail -1 $OUT/sampler_${v}_$n.json)"
     if [ -z "${NOSTEP:-}" ]; then
-      timeout -k 10 300 python3 bench.py --steps 500 --no-cpu-baseline --e2e-steps 0 > $OUT/cfg2_${v}_$n.json 2> $OUT/cfg2_${v}_$n.err || { tail -20 $OUT/cfg2_${v}_$n.err; exit 1; }
+      timeout -k 10 300 python3 bench.py --steps 500 --full --no-cpu-baseline --e2e-steps 0 > $OUT/cfg2_${v}_$n.json 2> $OUT/cfg2_${v}_$n.err || { tail -20 $OUT/cfg2_${v}_$n.err; exit 1; }
       python3 -c "import json; d=json.loads(open('$OUT/cfg2_${v}_$n.json').read().strip().splitlines()[-1]); print('cfg2-500 $v $n', round(d['value']), round(d['roofline']['avg_launch_ms'],4), d.get('verified'), d.get('fault_status'))"
     fi
   done

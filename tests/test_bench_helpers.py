@@ -58,6 +58,34 @@ def test_cpu_baseline_leg(bench):
         r["value_all_cores_extrapolated"] * r["scaling_efficiency_1_to_threads"])
 
 
+def test_dump_outputs(bench, tmp_path):
+    """bench.py --dump-outputs: float32 kept, other dtypes as float64, an array within its share
+    of the byte budget stored whole, a larger one as the same seeded sample on every call, and
+    the files together within the budget."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(3)
+    outs = [torch.rand(4, 50, 7, generator=g), torch.rand(3, 20000, generator=g),
+            torch.arange(40, dtype=torch.int32).reshape(5, 8)]
+    budget = 3 * (4096 + 8000)  # per array: 8000 bytes after the header allowance
+    a = bench.dump_outputs(outs, str(tmp_path / "a"), max_bytes=budget)
+    b = bench.dump_outputs(outs, str(tmp_path / "b"), max_bytes=budget)
+    assert a == b and sorted(a) == ["out00.npy", "out01.npy", "out02.npy"]
+    assert [a[k]["sampled"] for k in sorted(a)] == [False, True, False]
+    assert a["out01.npy"]["shape"] == [3, 20000]
+    got = [np.load(tmp_path / "a" / k) for k in sorted(a)]
+    assert got[0].dtype == np.float32 and np.array_equal(got[0], outs[0].numpy())
+    assert got[2].dtype == np.float64 and np.array_equal(got[2], outs[2].numpy())
+    assert got[1].dtype == np.float32 and got[1].shape == (2000,)
+    assert np.isin(got[1], outs[1].numpy()).all()
+    assert np.array_equal(got[1], np.load(tmp_path / "b" / "out01.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / k) for k in a) <= budget
+    changed = [o.clone() for o in outs]
+    changed[1] += 1.0  # every element differs, so any sample shows it
+    bench.dump_outputs(changed, str(tmp_path / "c"), max_bytes=budget)
+    assert not np.array_equal(got[1], np.load(tmp_path / "c" / "out01.npy"))
+
+
 @pytest.mark.parametrize("config", ["cfg2", "cfg3"])
 def test_verify_checker_catches_a_wrong_step(bench, config):
     """bench.py's `verified` field: the checker passes the oracle's own outputs and fails a
