@@ -467,6 +467,49 @@ int pn2_fp_mlp(const float* dist, const int32_t* nn_idx, const float* points1, i
 int pn2_shared_mlp(const float* x, long long rows, int cin, int nlayers,
                    const pn2_mlp_layer* layers, float* out, pn2_stream_t stream);
 
+/* ---------------------------------------------------------------- shared MLP, training -- */
+/* One tf_util.conv2d / conv1d layer with is_training=True (tf_util.py:165-185, batch norm on
+ * batch statistics :512-531): y = x W + b (pn2_shared_mlp over a pn2_mlp_pack of W and b with
+ * no batch norm and no activation), then the entry points below. All tensors row-major fp32.
+ * Every reduction is two-stage with a fixed order and no floating-point atomics, so results
+ * are bitwise reproducible. */
+
+/* Per-channel mean and BIASED variance of y (rows,C) over the rows. Stage 1: each workgroup
+ * reduces PN2_BN_BLOCK_ROWS rows of 32 channels to (mean, M2) partials (8-row batches merged
+ * with Chan's formula); stage 2 merges the partials in double precision. workspace:
+ * pn2_bn_workspace_size(rows, C) bytes of device memory (also enough for pn2_bn_act_bwd). */
+#define PN2_BN_BLOCK_ROWS 1024
+size_t pn2_bn_workspace_size(long long rows, int C);
+int pn2_bn_stats(const float* y, long long rows, int C, float* mean, float* var, void* workspace,
+                 size_t workspace_bytes, pn2_stream_t stream);
+/* out = act((y - mean) * (gamma / sqrt(var + eps)) + beta), act = ReLU when `relu`, else the
+ * identity. mean, var, gamma and beta may be NULL together: no batch norm, out = act(y). */
+int pn2_bn_act_fwd(const float* y, long long rows, int C, const float* mean, const float* var,
+                   const float* gamma, const float* beta, float eps, int relu, float* out,
+                   pn2_stream_t stream);
+/* Backward of pn2_bn_act_fwd. dz = grad_out * [pre-activation > 0] (the pre-activation is
+ * recomputed from y with the forward's fp32 expression, so the mask equals out > 0);
+ * grad_beta = sum dz, grad_gamma = sum dz * xhat, xhat = (y - mean) / sqrt(var + eps);
+ * grad_y = gamma / sqrt(var + eps) * (dz - grad_beta / rows - xhat * grad_gamma / rows).
+ * Without batch norm (mean, var, gamma, beta and grad_gamma NULL): grad_y = dz and grad_beta
+ * = sum dz (the bias gradient). workspace: pn2_bn_workspace_size(rows, C) bytes. */
+int pn2_bn_act_bwd(const float* grad_out, const float* y, long long rows, int C,
+                   const float* mean, const float* var, const float* gamma, const float* beta,
+                   float eps, int relu, float* grad_y, float* grad_gamma, float* grad_beta,
+                   void* workspace, size_t workspace_bytes, pn2_stream_t stream);
+/* grad_w (cin,cout) = x^T grad_y for x (rows,cin), grad_y (rows,cout), on the fp32 matrix
+ * cores. Rows are cut into slabs of PN2_WGRAD_SLAB_ROWS; a slab's 32x32 tile product is
+ * accumulated in fp32 from zero, slab results are added in double precision and written as at
+ * most PN2_WGRAD_MAX_PARTS partial tiles per output tile (fewer when that would exceed
+ * PN2_WGRAD_MAX_WS_BYTES of workspace), and stage 2 sums the partials in double precision.
+ * workspace: pn2_mlp_wgrad_workspace_size(rows, cin, cout) bytes. */
+#define PN2_WGRAD_SLAB_ROWS 1024
+#define PN2_WGRAD_MAX_PARTS 512
+#define PN2_WGRAD_MAX_WS_BYTES (64u << 20)
+size_t pn2_mlp_wgrad_workspace_size(long long rows, int cin, int cout);
+int pn2_mlp_wgrad(const float* x, const float* grad_y, long long rows, int cin, int cout,
+                  float* grad_w, void* workspace, size_t workspace_bytes, pn2_stream_t stream);
+
 /* ---------------------------------------------------------------- scene crops ---------- */
 
 /* Scene bounding box: bbox = [min x, min y, min z, max x, max y, max z] of points (N,3)

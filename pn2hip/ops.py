@@ -15,7 +15,12 @@ visible to torch.compile and TorchScript:
     three_interpolate(points, idx, weight)            tf_interpolate.py:19-28
     attn_reduce(Q, K, V)                              attention_layer.py:29-45 (reduction core)
 and the fused / gradient ops of the C ABI (farthest_point_sample_and_gather, group_concat,
-idw_weights, fp_fused, group_pool, *_grad).
+idw_weights, fp_fused, group_pool, *_grad), and the training-mode shared-MLP layer:
+
+    mlp_layer_train(x, weight, bias, gamma, beta, eps, relu)   tf_util.py:165-185, is_training
+                                                               -> (out, y, mean, var)
+    mlp_layer_train_grad(grad_out, x, weight, y, mean, var, gamma, beta, eps, relu, need_grad_x)
+                                       -> (grad_x, grad_w, grad_b, grad_gamma, grad_beta)
 """
 import importlib
 
@@ -25,7 +30,7 @@ NAMES = ("farthest_point_sample", "farthest_point_sample_and_gather", "gather_po
          "gather_point_grad", "prob_sample", "query_ball_point", "select_top_k", "knn_point",
          "group_point", "group_point_grad", "group_concat", "three_nn", "three_interpolate",
          "three_interpolate_grad", "idw_weights", "fp_fused", "attn_reduce", "attn_reduce_grad",
-         "group_pool")
+         "group_pool", "mlp_layer_train", "mlp_layer_train_grad")
 for _n in NAMES:
     globals()[_n] = getattr(_ops, _n)
 

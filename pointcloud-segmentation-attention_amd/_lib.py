@@ -138,6 +138,12 @@ SIGNATURES = {
                                      _I, _P, _P]),
     "pn2_fp_mlp": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "pn2_shared_mlp": (_I, [_P, _LL, _I, _I, _P, _P, _P]),
+    "pn2_bn_workspace_size": (_S, [_LL, _I]),
+    "pn2_bn_stats": (_I, [_P, _LL, _I, _P, _P, _P, _S, _P]),
+    "pn2_bn_act_fwd": (_I, [_P, _LL, _I, _P, _P, _P, _P, _F, _I, _P, _P]),
+    "pn2_bn_act_bwd": (_I, [_P, _P, _LL, _I, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _S, _P]),
+    "pn2_mlp_wgrad_workspace_size": (_S, [_LL, _I, _I]),
+    "pn2_mlp_wgrad": (_I, [_P, _P, _LL, _I, _I, _P, _P, _S, _P]),
     "pn2_scene_workspace_size": (_S, [_I]),
     "pn2_scene_bbox": (_I, [_P, _I, _P, _P, _S, _P]),
     "pn2_crop_workspace_size": (_S, [_I, _I, _I]),

@@ -10,7 +10,8 @@
 // Each op has a CUDA (= HIP on ROCm) kernel and a Meta kernel (shapes only, for fake tensors
 // and torch.compile). Autograd for gather_point / group_point / three_interpolate (w.r.t.
 // the points only, tf_sampling.py:44-48, tf_grouping.py:42-46, tf_interpolate.py:29-34) and
-// attn_reduce is registered from Python (torch.library.register_autograd, _torch_ops.py).
+// attn_reduce is registered from Python (torch.library.register_autograd, _torch_ops.py), and
+// so is the training-mode shared-MLP layer's (mlp_layer_train -> mlp_layer_train_grad).
 // CPU kernels exist only for the three ops the reference itself runs on the CPU (ThreeNN,
 // ThreeInterpolate, ThreeInterpolateGrad: registered for DEVICE_CPU only,
 // tf_interpolate.cpp:187,222,262), through the host twins pn2cpu_* (csrc/cpu_interp.cpp);
@@ -434,6 +435,145 @@ Tensor group_pool_hip(const Tensor& x_, const std::optional<Tensor>& gxyz_, int6
   return out;
 }
 
+// ---- training-mode shared-MLP layer (csrc/mlp_train.hip): tf_util.conv2d with is_training
+// (tf_util.py:165-185), conv + bias + batch-statistics batch norm + ReLU and its gradients
+bool has(const std::optional<Tensor>& t) { return t.has_value() && t->defined(); }
+
+// x (..., cin), weight (cin, cout), the per-channel vectors (cout) or all absent
+void chk_mlp_layer(const Tensor& x, const Tensor& weight, const std::optional<Tensor>& bias,
+                   const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta,
+                   const char* name) {
+  TORCH_CHECK_VALUE(weight.dim() == 2 && weight.size(0) > 0 && weight.size(1) > 0, name,
+                    " expects (cin, cout) weight");
+  TORCH_CHECK_VALUE(x.dim() >= 1 && x.size(-1) == weight.size(0), name,
+                    " expects (..., cin) x for (cin, cout) weight");
+  TORCH_CHECK_VALUE(has(gamma) == has(beta), name, " expects gamma and beta together");
+  const int64_t cout = weight.size(1);
+  for (const auto* v : {&bias, &gamma, &beta})
+    if (has(*v))
+      TORCH_CHECK_VALUE((*v)->dim() == 1 && (*v)->size(0) == cout, name,
+                        " expects (cout) bias, gamma and beta");
+}
+std::vector<int64_t> with_last(const Tensor& x, int64_t c) {
+  std::vector<int64_t> s(x.sizes().begin(), x.sizes().end());
+  s.back() = c;
+  return s;
+}
+Tensor workspace(const Tensor& like, size_t bytes) {
+  return at::empty({static_cast<int64_t>((bytes + 3) / 4 > 4 ? (bytes + 3) / 4 : 4)}, f32(like));
+}
+
+// out (rows, cout) = in (rows, cin) * w (cin, cout) + bias: pn2_mlp_pack + pn2_shared_mlp as one
+// layer with no batch norm and no activation
+void linear_rows(const Tensor& in, const Tensor& w, const Tensor& bias, int64_t rows, Tensor& out,
+                 const char* op) {
+  const int cin = I(w.size(0)), cout = I(w.size(1));
+  const size_t bytes = pn2_mlp_packed_size(cin, cout);
+  Tensor packed = workspace(in, bytes);
+  check_rc(pn2_mlp_pack(F(w), F(bias), nullptr, nullptr, cin, cout, P(packed), bytes,
+                        stream_of(in)), op);
+  const pn2_mlp_layer layer = {P(packed), cin, cout, 0};
+  check_rc(pn2_shared_mlp(F(in), rows, cin, 1, &layer, out.data_ptr<float>(), stream_of(in)), op);
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> mlp_layer_train_hip(
+    const Tensor& x_, const Tensor& weight_, const std::optional<Tensor>& bias_,
+    const std::optional<Tensor>& gamma_, const std::optional<Tensor>& beta_, double eps,
+    bool relu) {
+  const char* op = "mlp_layer_train";
+  chk_mlp_layer(x_, weight_, bias_, gamma_, beta_, op);
+  Tensor x = dev(x_, "x", at::kFloat), weight = dev(weight_, "weight", at::kFloat);
+  Tensor bias, gamma, beta;
+  if (has(bias_)) bias = dev(*bias_, "bias", at::kFloat);
+  const bool bn = has(gamma_);
+  if (bn) {
+    gamma = dev(*gamma_, "gamma", at::kFloat);
+    beta = dev(*beta_, "beta", at::kFloat);
+  }
+  c10::hip::HIPGuard g(x.device().index());
+  const int cin = I(weight.size(0)), cout = I(weight.size(1));
+  const int64_t rows = x.numel() / cin;
+  Tensor out = at::empty(with_last(x, cout), f32(x));
+  Tensor y = at::empty(with_last(x, cout), f32(x));
+  Tensor mean = at::empty({bn ? cout : 0}, f32(x)), var = at::empty({bn ? cout : 0}, f32(x));
+  if (rows == 0) {  // no rows, no statistics: defined values (tf_util.mlp_train skips its update)
+    mean.zero_();
+    var.zero_();
+    return {out, y, mean, var};
+  }
+  linear_rows(x, weight, bias, rows, y, op);
+  if (bn) {
+    const size_t ws = pn2_bn_workspace_size(rows, cout);
+    Tensor w = workspace(x, ws);
+    check_rc(pn2_bn_stats(F(y), rows, cout, mean.data_ptr<float>(), var.data_ptr<float>(), P(w),
+                          ws, stream_of(x)), op);
+  }
+  check_rc(pn2_bn_act_fwd(F(y), rows, cout, bn ? F(mean) : nullptr, bn ? F(var) : nullptr, F(gamma),
+                          F(beta), static_cast<float>(eps), relu ? 1 : 0, out.data_ptr<float>(),
+                          stream_of(x)), op);
+  return {out, y, mean, var};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_grad_hip(
+    const Tensor& grad_out_, const Tensor& x_, const Tensor& weight_, const Tensor& y_,
+    const std::optional<Tensor>& mean_, const std::optional<Tensor>& var_,
+    const std::optional<Tensor>& gamma_, const std::optional<Tensor>& beta_, double eps, bool relu,
+    bool need_grad_x) {
+  const char* op = "mlp_layer_train_grad";
+  chk_mlp_layer(x_, weight_, std::nullopt, gamma_, beta_, op);
+  const bool bn = has(gamma_);
+  const int cin = I(weight_.size(0)), cout = I(weight_.size(1));
+  TORCH_CHECK_VALUE(y_.sizes() == grad_out_.sizes() && y_.dim() == x_.dim() && y_.size(-1) == cout &&
+                        y_.numel() / cout == x_.numel() / cin,
+                    op, " expects (..., cout) grad_out and y for (..., cin) x");
+  if (bn)
+    TORCH_CHECK_VALUE(has(mean_) && has(var_) && mean_->dim() == 1 && mean_->size(0) == cout &&
+                          var_->dim() == 1 && var_->size(0) == cout,
+                      op, " expects (cout) mean and var with gamma and beta");
+  Tensor go = dev(grad_out_, "grad_out", at::kFloat), x = dev(x_, "x", at::kFloat);
+  Tensor weight = dev(weight_, "weight", at::kFloat), y = dev(y_, "y", at::kFloat);
+  Tensor mean, var, gamma, beta;
+  if (bn) {
+    mean = dev(*mean_, "mean", at::kFloat);
+    var = dev(*var_, "var", at::kFloat);
+    gamma = dev(*gamma_, "gamma", at::kFloat);
+    beta = dev(*beta_, "beta", at::kFloat);
+  }
+  c10::hip::HIPGuard g(x.device().index());
+  const int64_t rows = x.numel() / cin;
+  Tensor grad_x = need_grad_x ? at::empty(x.sizes(), f32(x)) : at::empty({0}, f32(x));
+  Tensor grad_w = at::empty({cin, cout}, f32(x));
+  // under batch norm the bias shifts the batch mean with it: its gradient is identically zero
+  Tensor grad_b = bn ? at::zeros({cout}, f32(x)) : at::empty({cout}, f32(x));
+  Tensor grad_gamma = at::empty({bn ? cout : 0}, f32(x));
+  Tensor grad_beta = at::empty({bn ? cout : 0}, f32(x));
+  if (rows == 0) {
+    grad_w.zero_();
+    grad_b.zero_();
+    grad_gamma.zero_();
+    grad_beta.zero_();
+    return {grad_x, grad_w, grad_b, grad_gamma, grad_beta};
+  }
+  Tensor grad_y = at::empty(y.sizes(), f32(x));
+  {
+    const size_t ws = pn2_bn_workspace_size(rows, cout);
+    Tensor w = workspace(x, ws);
+    check_rc(pn2_bn_act_bwd(F(go), F(y), rows, cout, F(mean), F(var), F(gamma), F(beta),
+                            static_cast<float>(eps), relu ? 1 : 0, grad_y.data_ptr<float>(),
+                            bn ? grad_gamma.data_ptr<float>() : nullptr,
+                            bn ? grad_beta.data_ptr<float>() : grad_b.data_ptr<float>(), P(w), ws,
+                            stream_of(x)), op);
+  }
+  {
+    const size_t ws = pn2_mlp_wgrad_workspace_size(rows, cin, cout);
+    Tensor w = workspace(x, ws);
+    check_rc(pn2_mlp_wgrad(F(x), F(grad_y), rows, cin, cout, grad_w.data_ptr<float>(), P(w), ws,
+                           stream_of(x)), op);
+  }
+  if (need_grad_x) linear_rows(grad_y, weight.t().contiguous(), Tensor(), rows, grad_x, op);
+  return {grad_x, grad_w, grad_b, grad_gamma, grad_beta};
+}
+
 // ------------------------------------------------------------------------- CPU kernels
 // (the reference's CPU-only ops; host twins in csrc/cpu_interp.cpp)
 Tensor host(const Tensor& t, const char* name, at::ScalarType dt) {
@@ -572,6 +712,24 @@ Tensor group_pool_meta(const Tensor& x, const std::optional<Tensor>& gxyz, int64
   return at::empty({x.size(0), x.size(1), mode == PN2_POOL_MAX_AND_AVG ? 2 * x.size(3) : x.size(3)},
                    mf(x));
 }
+std::tuple<Tensor, Tensor, Tensor, Tensor> mlp_layer_train_meta(
+    const Tensor& x, const Tensor& weight, const std::optional<Tensor>& bias,
+    const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta, double, bool) {
+  chk_mlp_layer(x, weight, bias, gamma, beta, "mlp_layer_train");
+  const int64_t cout = weight.size(1), nstat = has(gamma) ? cout : 0;
+  return {at::empty(with_last(x, cout), mf(x)), at::empty(with_last(x, cout), mf(x)),
+          at::empty({nstat}, mf(x)), at::empty({nstat}, mf(x))};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_grad_meta(
+    const Tensor&, const Tensor& x, const Tensor& weight, const Tensor&,
+    const std::optional<Tensor>&, const std::optional<Tensor>&, const std::optional<Tensor>& gamma,
+    const std::optional<Tensor>& beta, double, bool, bool need_grad_x) {
+  chk_mlp_layer(x, weight, std::nullopt, gamma, beta, "mlp_layer_train_grad");
+  const int64_t cout = weight.size(1), nstat = has(gamma) ? cout : 0;
+  return {need_grad_x ? at::empty(x.sizes(), mf(x)) : at::empty({0}, mf(x)),
+          at::empty(weight.sizes(), mf(x)), at::empty({cout}, mf(x)), at::empty({nstat}, mf(x)),
+          at::empty({nstat}, mf(x))};
+}
 
 }  // namespace
 
@@ -598,6 +756,11 @@ TORCH_LIBRARY(pn2, m) {
   m.def("attn_reduce(Tensor Q, Tensor K, Tensor V) -> Tensor");
   m.def("attn_reduce_grad(Tensor Q, Tensor K, Tensor V, Tensor grad_out) -> (Tensor, Tensor, Tensor)");
   m.def("group_pool(Tensor x, Tensor? grouped_xyz, int mode) -> Tensor");
+  m.def("mlp_layer_train(Tensor x, Tensor weight, Tensor? bias, Tensor? gamma, Tensor? beta, "
+        "float eps, bool relu) -> (Tensor out, Tensor y, Tensor mean, Tensor var)");
+  m.def("mlp_layer_train_grad(Tensor grad_out, Tensor x, Tensor weight, Tensor y, Tensor? mean, "
+        "Tensor? var, Tensor? gamma, Tensor? beta, float eps, bool relu, bool need_grad_x) -> "
+        "(Tensor grad_x, Tensor grad_w, Tensor grad_b, Tensor grad_gamma, Tensor grad_beta)");
 }
 
 // ROCm builds of PyTorch dispatch HIP tensors under the CUDA key.
@@ -621,6 +784,8 @@ TORCH_LIBRARY_IMPL(pn2, CUDA, m) {
   m.impl("attn_reduce", &attn_reduce_hip);
   m.impl("attn_reduce_grad", &attn_reduce_grad_hip);
   m.impl("group_pool", &group_pool_hip);
+  m.impl("mlp_layer_train", &mlp_layer_train_hip);
+  m.impl("mlp_layer_train_grad", &mlp_layer_train_grad_hip);
 }
 
 TORCH_LIBRARY_IMPL(pn2, CPU, m) {
@@ -649,4 +814,6 @@ TORCH_LIBRARY_IMPL(pn2, Meta, m) {
   m.impl("attn_reduce", &attn_reduce_meta);
   m.impl("attn_reduce_grad", &attn_reduce_grad_meta);
   m.impl("group_pool", &group_pool_meta);
+  m.impl("mlp_layer_train", &mlp_layer_train_meta);
+  m.impl("mlp_layer_train_grad", &mlp_layer_train_grad_meta);
 }

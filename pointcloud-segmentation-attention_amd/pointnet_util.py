@@ -472,6 +472,14 @@ def _pool_torch(x, pooling, grouped_xyz):
     raise InvalidArgumentError(f"unknown pooling {pooling!r}")
 
 
+def _mlp_autograd(store, x, layers, is_training, bn_decay):
+    """The differentiable shared MLP of the SA / FP modules: the HIP training layers
+    (tf_util.mlp_train) when training on a trainable store, else the torch composition."""
+    if is_training and store.is_trainable:
+        return tf_util.mlp_train(x, layers, bn_decay)
+    return tf_util.mlp_torch(x, layers, is_training, bn_decay)
+
+
 def pointnet_sa_module(xyz, points, npoint, radius, nsample, mlp, mlp2, group_all, is_training,
                        bn_decay, scope, bn=True, pooling='max', knn=False, use_xyz=True,
                        use_nchw=False, params=None):
@@ -481,7 +489,9 @@ def pointnet_sa_module(xyz, points, npoint, radius, nsample, mlp, mlp2, group_al
 
     Inference (is_training False, no autograd): FPS + ball query, then ONE kernel for group,
     MLP and pooling (pn2_group_mlp), and mlp2 as a per-point MLP. Training: the same ops
-    composed from differentiable torch ops (batch-statistics batch norm)."""
+    composed from differentiable torch ops (batch-statistics batch norm); on a trainable store
+    (tf_util.ParamStore.trainable()) the MLPs are the HIP training layers (tf_util.mlp_train),
+    which also give every variable its gradient."""
     store = params if params is not None else tf_util.default_store()
     xyz = device_tensor(xyz, "xyz", torch.float32)
     scopes = [f"{scope}/conv{i}" for i in range(len(mlp))]
@@ -499,12 +509,12 @@ def pointnet_sa_module(xyz, points, npoint, radius, nsample, mlp, mlp2, group_al
         3 if (use_xyz or _is_empty_points(points)) else 0)
     if is_training or _needs_grad(xyz, points):
         layers = tf_util.torch_layers(store, scopes, cin, mlp, bn=bn)
-        x = tf_util.mlp_torch(new_points, layers, is_training, bn_decay)
+        x = _mlp_autograd(store, new_points, layers, is_training, bn_decay)
         x = _pool_torch(x, pooling, grouped_xyz)
         if mlp2:
             c = int(x.shape[-1])
-            x = tf_util.mlp_torch(x, tf_util.torch_layers(store, post, c, mlp2, bn=bn),
-                                  is_training, bn_decay)
+            x = _mlp_autograd(store, x, tf_util.torch_layers(store, post, c, mlp2, bn=bn),
+                              is_training, bn_decay)
         return new_xyz, x, idx
     fused = tf_util.packed_mlp(store, scopes, cin, mlp, bn=bn)
     # group_all: one group of all N points centred on (0,0,0) (pointnet_util.py:72-87)
@@ -537,7 +547,8 @@ def pointnet_sa_module_msg(xyz, points, npoint, radius_list, nsample_list, mlp_l
         if training:
             gp, _ = group_concat(xyz, points, new_xyz, idx, use_xyz=use_xyz, xyz_last=True)
             layers = tf_util.torch_layers(store, scopes, cin, mlp_list[i], bn=bn)
-            outs.append(tf_util.mlp_torch(gp, layers, is_training, bn_decay).max(dim=2).values)
+            outs.append(_mlp_autograd(store, gp, layers, is_training,
+                                      bn_decay).max(dim=2).values)
         else:
             fused = tf_util.packed_mlp(store, scopes, cin, mlp_list[i], bn=bn)
             outs.append(group_mlp(xyz, points, new_xyz, idx, fused, "max", use_xyz=use_xyz,
@@ -560,7 +571,7 @@ def pointnet_fp_module(xyz1, xyz2, points1, points2, mlp, is_training, bn_decay,
     if is_training or _needs_grad(points1, points2):
         x = fp_interpolate(xyz1, xyz2, points1, points2, known_grid, unknown_grid)
         layers = tf_util.torch_layers(store, scopes, C1 + C2, mlp, bn=bn)
-        return tf_util.mlp_torch(x, layers, is_training, bn_decay)
+        return _mlp_autograd(store, x, layers, is_training, bn_decay)
     fused = tf_util.packed_mlp(store, scopes, C1 + C2, mlp, bn=bn)
     dist, idx = tf_interpolate.three_nn(xyz1, xyz2, known_grid, unknown_grid)
     return fp_mlp(dist, idx, points1, points2, fused)

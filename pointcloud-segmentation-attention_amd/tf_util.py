@@ -14,16 +14,27 @@ Parameters live in a ParamStore keyed by the reference's TF variable names
 ".../bn/moving_variance"), so a TF checkpoint's variables, exported to a dict of arrays, load
 unchanged. Missing variables are created with the reference's initialisers (xavier weights,
 zero biases, gamma 1, beta 0, moving mean 0, moving variance 1; tf_util.py:24-49).
+
+Training mode (is_training=True: batch norm on batch statistics, tf_util.py:512-531) runs on
+the HIP training layer torch.ops.pn2.mlp_layer_train (csrc/mlp_train.hip) through mlp_train,
+for the variables of a store made trainable with ParamStore.trainable(): device-resident
+leaves with gradients, moving averages updated in place on the device.
 """
 import math
 
 import numpy as np
 import torch
 
+from . import _torch_ops
 from ._lib import (PN2_MLP_MAX_LAYERS, PN2_MLP_RELU, InvalidArgumentError, MlpLayer, check,
                    device_tensor, lib, ptr, stream_of)
 
 BN_EPSILON = 1e-3  # tf.contrib.layers.batch_norm's default epsilon
+MOVING_SUFFIXES = ("moving_mean", "moving_variance")  # batch norm's non-trainable variables
+CONV_SUFFIXES = ("weights", "biases", "bn/gamma", "bn/beta", "bn/moving_mean",
+                 "bn/moving_variance")
+DENSE_SUFFIXES = ("kernel", "bias")
+BN_SUFFIXES = ("gamma", "beta", "moving_mean", "moving_variance")
 
 
 class ParamStore(dict):
@@ -33,13 +44,67 @@ class ParamStore(dict):
         super().__init__()
         self.seed = seed
         self.device = device
+        self.is_trainable = False
         self._packed = {}
+        self._stamps = {}
         for k, v in dict(*args, **kw).items():
             self[k] = v
 
     def __setitem__(self, name, value):
-        # checkpoint arrays (numpy or torch) are kept as float32 CPU tensors
-        super().__setitem__(name, torch.as_tensor(value, dtype=torch.float32).detach().cpu())
+        # checkpoint arrays (numpy or torch) are kept as float32 CPU tensors; a trainable store
+        # keeps them on its device, as leaves that require a gradient (moving statistics: not)
+        t = torch.as_tensor(value, dtype=torch.float32).detach()
+        if self.is_trainable:
+            t = t.to(self.device, copy=True).contiguous()
+            t.requires_grad_(not name.endswith(MOVING_SUFFIXES))
+        else:
+            t = t.cpu()
+        super().__setitem__(name, t)
+
+    def trainable(self, device="cuda"):
+        """Make the store trainable: every variable moves to `device`; conv / dense weights,
+        biases, gamma and beta become leaves with requires_grad=True (existing ones now, later
+        ones when they are created), the moving statistics plain device tensors that mlp_train
+        updates in place. Returns the store. With a trainable store, is_training=True runs the
+        HIP training layers (mlp_train); build the optimiser from parameters() after the model
+        has run once, so that every variable exists."""
+        if self.is_trainable and torch.device(self.device) == torch.device(device):
+            return self
+        self.device = device
+        self.is_trainable = True
+        for name in list(self):
+            self[name] = dict.__getitem__(self, name)
+        self.invalidate()
+        return self
+
+    def parameters(self):
+        """The trainable variables (torch.optim.Adam(store.parameters()))."""
+        for t in self.values():
+            if t.requires_grad:
+                yield t
+
+    def state_dict(self):
+        """TF variable name -> float32 numpy array on the CPU (loads back with ParamStore(d))."""
+        return {k: v.detach().cpu().numpy().copy() for k, v in self.items()}
+
+    def stamp(self, scopes, suffixes):
+        """In-place versions of the variables `scopes` x `suffixes` that exist (trainable store:
+        an optimiser step or a moving-average update changes it), or None."""
+        if not self.is_trainable:
+            return None
+        found = (dict.get(self, f"{s}/{k}") for s in scopes for k in suffixes)
+        return tuple((id(t), t._version) for t in found if t is not None)
+
+    def cached(self, key, scopes, suffixes, make):
+        """The packed object cached under `key`, rebuilt with make() when a variable it was
+        packed from has changed since."""
+        stamp = self.stamp(scopes, suffixes)
+        hit = self._packed.get(key)
+        if hit is None or self._stamps.get(key) != stamp:
+            hit = make()
+            self._packed[key] = hit
+            self._stamps[key] = self.stamp(scopes, suffixes)
+        return hit
 
     def _init(self, name, shape, kind):
         if kind == "xavier":  # tf.contrib.layers.xavier_initializer(): glorot uniform
@@ -87,6 +152,7 @@ class ParamStore(dict):
     def invalidate(self):
         """Drop packed copies (call after changing parameters in place)."""
         self._packed.clear()
+        self._stamps.clear()
 
 
 _default_store = None
@@ -105,6 +171,10 @@ class PackedLayer:
 
     def __init__(self, weights, biases=None, gamma=None, beta=None, moving_mean=None,
                  moving_variance=None, relu=True, eps=BN_EPSILON, device="cuda"):
+        # a trainable store's variables are packed by value (no autograd through the packing)
+        weights, biases, gamma, beta, moving_mean, moving_variance = (
+            v.detach() if isinstance(v, torch.Tensor) else v
+            for v in (weights, biases, gamma, beta, moving_mean, moving_variance))
         w = torch.as_tensor(weights, dtype=torch.float32)
         if w.dim() == 4:  # TF conv2d kernel [1,1,cin,cout]
             w = w.reshape(w.shape[-2], w.shape[-1])
@@ -171,58 +241,64 @@ def packed_mlp(store, scopes, cin, widths, bn=True, relu=True):
     """SharedMLP over the store's variables for conv scopes `scopes` (one per width), cached
     per scope tuple. `relu` applies to every layer (tf_util.conv2d's activation_fn)."""
     key = (tuple(scopes), cin, tuple(widths), bn, relu)
-    hit = store._packed.get(key)
-    if hit is not None:
-        return hit
-    layers, c = [], cin
-    for scope, w in zip(scopes, widths):
-        p = store.conv(scope, c, w, bn=bn)
-        layers.append(PackedLayer(p["weights"], p["biases"], p.get("gamma"), p.get("beta"),
-                                  p.get("moving_mean"), p.get("moving_variance"), relu=relu,
-                                  device=store.device))
-        c = w
-    mlp = SharedMLP(layers)
-    store._packed[key] = mlp
-    return mlp
+
+    def make():
+        layers, c = [], cin
+        for scope, w in zip(scopes, widths):
+            p = store.conv(scope, c, w, bn=bn)
+            layers.append(PackedLayer(p["weights"], p["biases"], p.get("gamma"), p.get("beta"),
+                                      p.get("moving_mean"), p.get("moving_variance"), relu=relu,
+                                      device=store.device))
+            c = w
+        return SharedMLP(layers)
+
+    return store.cached(key, scopes, CONV_SUFFIXES, make)
 
 
 def packed_dense(store, scope, cin, cout):
     """SharedMLP of one tf.layers.Dense (no activation) over the store's variables, cached."""
     key = ("dense", scope, cin, cout)
-    hit = store._packed.get(key)
-    if hit is None:
+
+    def make():
         p = store.dense(scope, cin, cout)
-        hit = SharedMLP([PackedLayer(p["weights"], p["biases"], relu=False, device=store.device)])
-        store._packed[key] = hit
-    return hit
+        return SharedMLP([PackedLayer(p["weights"], p["biases"], relu=False, device=store.device)])
+
+    return store.cached(key, [scope], DENSE_SUFFIXES, make)
 
 
 def bn_affine(store, scope, c, device):
     """Inference batch norm as (scale, shift) device tensors: x * scale + shift."""
     key = ("bn", scope, c)
-    hit = store._packed.get(key)
-    if hit is None:
-        p = store.bn(scope, c)
+
+    def make():
+        p = {k: v.detach() for k, v in store.bn(scope, c).items()}
         s64 = p["gamma"].double() / torch.sqrt(p["moving_variance"].double() + BN_EPSILON)
         shift = p["beta"].double() - p["moving_mean"].double() * s64
-        hit = (s64.float().to(device), shift.float().to(device))
-        store._packed[key] = hit
-    return hit
+        return (s64.float().to(device), shift.float().to(device))
+
+    return store.cached(key, [scope], BN_SUFFIXES, make)
 
 
 def conv2d(inputs, num_output_channels, kernel_size, scope, stride=[1, 1], padding='SAME',
            data_format='NHWC', use_xavier=True, stddev=1e-3, weight_decay=None,
            activation_fn=torch.relu, bn=False, bn_decay=None, is_training=None, params=None):
-    """tf_util.conv2d (tf_util.py:120-185) for the 1x1 kernels PointNet++ uses, NHWC,
-    inference mode. Extra keyword `params`: the ParamStore (default: default_store())."""
+    """tf_util.conv2d (tf_util.py:120-185) for the 1x1 kernels PointNet++ uses, NHWC.
+    Extra keyword `params`: the ParamStore (default: default_store()). is_training=True needs a
+    trainable store (ParamStore.trainable()) and runs mlp_train: batch-statistics batch norm,
+    gradients for the input and every variable."""
     if list(kernel_size) != [1, 1] or list(stride) != [1, 1] or data_format != 'NHWC':
         raise NotImplementedError("pn2hip's conv2d is the 1x1 NHWC shared MLP of PointNet++")
-    if is_training:
-        raise NotImplementedError("conv2d: the fused layer is inference-mode batch norm; "
-                                  "use pointnet_util.*(is_training=True) for training")
+    store = params if params is not None else default_store()
+    if is_training and not store.is_trainable:
+        raise NotImplementedError("conv2d: is_training=True needs a trainable store: call "
+                                  "ParamStore.trainable() on `params` (a plain store runs the "
+                                  "fused inference-mode layer only)")
     if activation_fn not in (None, torch.relu, torch.nn.functional.relu):
         raise NotImplementedError("conv2d: activation must be relu or None")
-    store = params if params is not None else default_store()
+    if is_training:
+        layers = torch_layers(store, [scope], int(inputs.shape[-1]), [num_output_channels],
+                              bn=bn, relu=activation_fn is not None)
+        return mlp_train(inputs, layers, bn_decay)
     mlp = packed_mlp(store, [scope], int(inputs.shape[-1]), [num_output_channels], bn=bn,
                      relu=activation_fn is not None)
     return mlp(inputs)
@@ -263,6 +339,28 @@ def mlp_torch(x, layers, is_training=False, bn_decay=None):
                 var = p["moving_variance"].to(x.device)
             y = (y - mean) * (gamma / torch.sqrt(var + BN_EPSILON)) + beta
         x = torch.relu(y) if L.relu else y
+    return x
+
+
+def mlp_train(x, layers, bn_decay=None):
+    """The layers of mlp_torch(x, layers, is_training=True) on the HIP training kernels
+    (torch.ops.pn2.mlp_layer_train: conv + bias + batch-statistics batch norm + ReLU, with
+    autograd for x and every variable), for the variables of a trainable ParamStore. The moving
+    averages are updated in place on the device by mlp_torch's rule: decay bn_decay (0.9 when
+    None) with the biased batch variance."""
+    decay = 0.9 if bn_decay is None else float(bn_decay)
+    x = device_tensor(x, "inputs", torch.float32)
+    for L in layers:
+        p = L.params
+        bn = p.get("gamma") is not None
+        rows = x.numel()
+        x, _, mean, var = _torch_ops.call(
+            "mlp_layer_train", x, p["weights"], p.get("biases"), p.get("gamma") if bn else None,
+            p.get("beta") if bn else None, BN_EPSILON, bool(L.relu))
+        if bn and rows > 0:  # no rows: no batch statistics, the moving averages stay
+            with torch.no_grad():
+                p["moving_mean"].mul_(decay).add_((1 - decay) * mean)
+                p["moving_variance"].mul_(decay).add_((1 - decay) * var)
     return x
 
 

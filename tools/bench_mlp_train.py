@@ -1,0 +1,192 @@
+#!/usr/bin/env python3
+"""Time one training-mode shared-MLP layer, forward plus backward, on the HIP kernels
+(torch.ops.pn2.mlp_layer_train, csrc/mlp_train.hip) against the torch composition it replaces
+(tf_util.mlp_torch with is_training=True plus autograd), at three layer shapes of cfg2:
+
+    SA1 conv1   524,288 rows   32 -> 32
+    FP4 conv0   131,072 rows  128 -> 128
+    SA4 conv1     8,192 rows  256 -> 512
+
+    python tools/bench_mlp_train.py [--repeats 7] [--iters 10] [--out summary.json]
+
+Each shape runs in a child process of its own under `timeout`; a shape that fails stops the
+run. Per shape: warm-up, then `repeats` timed windows of `iters` forward+backward passes per
+side, the two sides alternating, timed with events on the stream; the median window is
+reported. Both sides compute gradients for the input, weight, bias, gamma and beta. The torch
+side keeps its moving averages on the CPU (as tf_util.mlp_torch does: one device-to-host copy
+per layer) and gets its weights as device tensors.
+
+`max_rel_grad_diff` is the largest difference between the two sides' gradients over the
+largest gradient: last-bit differences of reordered fp32 sums, except that a pre-activation
+within rounding of zero can fall on either side of the ReLU (a discrete difference of up to
+one grad_out element), and that the bias gradient under batch norm is exactly 0 on the HIP
+side and rounding noise on the torch side (shown as 1.0).
+
+Then, per C entry point of the layer, the time of the call alone (events, median of `repeats`
+windows) and the bytes its algorithm has to move (computed from the shape) over that time,
+against the measured copy peak of 6.03 TB/s. The two GEMMs through pn2_shared_mlp
+include their pn2_mlp_pack.
+"""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+COPY_PEAK_TBS = 6.03
+SHAPES = {"SA1_conv1": (524288, 32, 32), "FP4_conv0": (131072, 128, 128),
+          "SA4_conv1": (8192, 256, 512)}
+EPS = 1e-3
+
+
+def windows(torch, fns, repeats, iters):
+    """Median time per call (us) of each fn: `repeats` windows of `iters` calls, alternating."""
+    for fn in fns:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = [[] for _ in fns]
+    for _ in range(repeats):
+        for k, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[k].append(e0.elapsed_time(e1) / iters * 1e3)
+    return [statistics.median(t) for t in times], [(min(t), max(t)) for t in times]
+
+
+def one(name, repeats, iters):
+    import torch
+    pkg = importlib.import_module("pointcloud-segmentation-attention_amd")
+    import pn2hip
+    L, tu, ops = importlib.import_module(pkg.__name__ + "._lib"), pkg.tf_util, pn2hip.ops
+    assert torch.cuda.is_available(), "bench_mlp_train needs the MI355X"
+    dev = torch.device("cuda:0")
+    rows, cin, cout = SHAPES[name]
+    g = torch.Generator().manual_seed(rows + cin)
+    lim = (6.0 / (cin + cout)) ** 0.5
+    leaf = lambda t: t.to(dev).requires_grad_(True)  # noqa: E731
+    x = leaf(torch.rand(rows, cin, generator=g) * 2 - 1)
+    w = leaf((torch.rand(cin, cout, generator=g) * 2 - 1) * lim)
+    b = leaf(torch.rand(cout, generator=g) * 0.2 - 0.1)
+    gamma = leaf(torch.rand(cout, generator=g) + 0.5)
+    beta = leaf(torch.rand(cout, generator=g) * 0.4 - 0.2)
+    go = (torch.rand(rows, cout, generator=g) * 2 - 1).to(dev)
+    leaves = (x, w, b, gamma, beta)
+    layer = tu.TorchLayer({"weights": w, "biases": b, "gamma": gamma, "beta": beta,
+                           "moving_mean": torch.zeros(cout), "moving_variance": torch.ones(cout)})
+
+    def clear():
+        for t in leaves:
+            t.grad = None
+
+    def hip():
+        clear()
+        ops.mlp_layer_train(x, w, b, gamma, beta, EPS, True)[0].backward(go)
+
+    def parent():
+        clear()
+        tu.mlp_torch(x, [layer], True, None).backward(go)
+
+    # same gradients on both sides (reordered fp32 sums differ in the last bits)
+    hip()
+    gh = [t.grad.clone() for t in leaves]
+    parent()
+    diffs = {}
+    for nm, a, t in zip(("x", "w", "b", "gamma", "beta"), gh, leaves):
+        scale = max(float(t.grad.abs().max()), 1e-6)
+        diffs[nm] = float((a - t.grad).abs().max()) / scale
+    (t_hip, t_par), spread = windows(torch, [hip, parent], repeats, iters)
+
+    # the C entry points alone
+    xd, wd, bd, gd, btd = (t.detach() for t in leaves)
+    lib, ptr, st = L.lib(), L.ptr, L.stream_of(xd)
+    f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
+    y, out, gy, gx, gw = f32(rows, cout), f32(rows, cout), f32(rows, cout), f32(rows, cin), f32(cin, cout)
+    mean, var, gg, gb = f32(cout), f32(cout), f32(cout), f32(cout)
+    ws_bn = int(lib.pn2_bn_workspace_size(rows, cout))
+    ws_wg = int(lib.pn2_mlp_wgrad_workspace_size(rows, cin, cout))
+    wsb, wsw = f32(max(ws_bn // 4, 4)), f32(max(ws_wg // 4, 4))
+    wt = wd.t().contiguous()
+
+    def gemm(inp, weight, bias, ci, co, dst):
+        nb = int(lib.pn2_mlp_packed_size(ci, co))
+        packed = f32((nb + 3) // 4)
+        L.check(lib.pn2_mlp_pack(ptr(weight), ptr(bias), None, None, ci, co, ptr(packed), nb, st),
+                "mlp_pack")
+        tab = (L.MlpLayer * 1)(L.MlpLayer(packed.data_ptr(), ci, co, 0))
+        L.check(lib.pn2_shared_mlp(ptr(inp), rows, ci, 1, tab, ptr(dst), st), "shared_mlp")
+
+    R, F = rows * 4, 4
+    calls = {
+        "pn2_shared_mlp y=xW+b": (lambda: gemm(xd, wd, bd, cin, cout, y), R * (cin + cout)),
+        "pn2_bn_stats": (lambda: L.check(lib.pn2_bn_stats(
+            ptr(y), rows, cout, ptr(mean), ptr(var), ptr(wsb), ws_bn, st), "bn_stats"), R * cout),
+        "pn2_bn_act_fwd": (lambda: L.check(lib.pn2_bn_act_fwd(
+            ptr(y), rows, cout, ptr(mean), ptr(var), ptr(gd), ptr(btd), EPS, 1, ptr(out), st),
+            "bn_act_fwd"), 2 * R * cout),
+        "pn2_bn_act_bwd": (lambda: L.check(lib.pn2_bn_act_bwd(
+            ptr(go), ptr(y), rows, cout, ptr(mean), ptr(var), ptr(gd), ptr(btd), EPS, 1, ptr(gy),
+            ptr(gg), ptr(gb), ptr(wsb), ws_bn, st), "bn_act_bwd"), 5 * R * cout),
+        "pn2_mlp_wgrad": (lambda: L.check(lib.pn2_mlp_wgrad(
+            ptr(xd), ptr(gy), rows, cin, cout, ptr(gw), ptr(wsw), ws_wg, st), "mlp_wgrad"),
+            R * (cin + cout) + ws_wg * 2 + F * cin * cout),
+        "pn2_shared_mlp grad_x=grad_y W^T": (lambda: gemm(gy, wt, None, cout, cin, gx),
+                                             R * (cin + cout)),
+    }
+    for fn, _ in calls.values():  # in order: each call's inputs exist
+        fn()
+    kern = {}
+    for nm, (fn, nbytes) in calls.items():
+        (us,), _ = windows(torch, [fn], repeats, iters)
+        kern[nm] = {"us": round(us, 1), "bytes": nbytes, "GBps": round(nbytes / us / 1e3, 1),
+                    "frac_copy_peak": round(nbytes / us / 1e6 / COPY_PEAK_TBS, 3)}
+    print(json.dumps({
+        "shape": name, "rows": rows, "cin": cin, "cout": cout, "repeats": repeats, "iters": iters,
+        "hip_fwd_bwd_us": round(t_hip, 1), "parent_fwd_bwd_us": round(t_par, 1),
+        "hip_min_max_us": [round(v, 1) for v in spread[0]],
+        "parent_min_max_us": [round(v, 1) for v in spread[1]],
+        "parent_over_hip": round(t_par / t_hip, 2), "no_slower": bool(t_hip <= t_par),
+        "max_rel_grad_diff": {k: float(f"{v:.3g}") for k, v in diffs.items()},
+        "entry_points": kern}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--timeout", type=int, default=150, help="seconds per shape")
+    ap.add_argument("--out", default=None, help="write the results as one JSON file")
+    ap.add_argument("--one", choices=sorted(SHAPES), help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.repeats < 5:
+        ap.error("--repeats must be at least 5")
+    if args.one:
+        return one(args.one, args.repeats, args.iters)
+    results = []
+    for name in SHAPES:
+        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__),
+               "--one", name, "--repeats", str(args.repeats), "--iters", str(args.iters)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        sys.stderr.write(r.stderr[-2000:])
+        if r.returncode != 0:
+            sys.exit(f"{name}: exit status {r.returncode}; stopping")
+        line = r.stdout.strip().splitlines()[-1]
+        print(line, flush=True)
+        results.append(json.loads(line))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"copy_peak_TBps": COPY_PEAK_TBS, "shapes": results}, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
