@@ -466,6 +466,11 @@ int pn2_fp_mlp(const float* dist, const int32_t* nn_idx, const float* points1, i
  * e.g. the fc1/fc2 head of pointnet2_sem_seg.py:57-60). */
 int pn2_shared_mlp(const float* x, long long rows, int cin, int nlayers,
                    const pn2_mlp_layer* layers, float* out, pn2_stream_t stream);
+/* R (row tiles per workgroup) and tpw (tiles per workgroup) that pn2_shared_mlp would launch
+ * with for these arguments on the current device; launches nothing. The same argument checks
+ * as pn2_shared_mlp (apart from the buffers it does not take); both are 0 for rows = 0. */
+int pn2_shared_mlp_plan(long long rows, int cin, int nlayers, const pn2_mlp_layer* layers,
+                        int* row_tiles, int* tiles_per_wg);
 
 /* ---------------------------------------------------------------- shared MLP, training -- */
 /* One tf_util.conv2d / conv1d layer with is_training=True (tf_util.py:165-185, batch norm on

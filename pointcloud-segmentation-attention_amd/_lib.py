@@ -138,6 +138,7 @@ SIGNATURES = {
                                      _I, _P, _P]),
     "pn2_fp_mlp": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "pn2_shared_mlp": (_I, [_P, _LL, _I, _I, _P, _P, _P]),
+    "pn2_shared_mlp_plan": (_I, [_LL, _I, _I, _P, _P, _P]),
     "pn2_bn_workspace_size": (_S, [_LL, _I]),
     "pn2_bn_stats": (_I, [_P, _LL, _I, _P, _P, _P, _S, _P]),
     "pn2_bn_act_fwd": (_I, [_P, _LL, _I, _P, _P, _P, _P, _F, _I, _P, _P]),

@@ -1139,6 +1139,24 @@ int device_cus() {
   return cache[dev];
 }
 
+// Several consecutive tiles per workgroup (weights staged once, the next tile's metadata
+// loads overlapping the current tile's layers), but only as many as keep >= 4 rounds of
+// workgroups: the dispatcher then still balances around CUs that other streams' kernels
+// hold (a grid of exactly the co-resident slots with static tile ranges waited for the SA1
+// sampler's CUs in the whole-model pipeline).
+int choose_tpw(long long nblocks, size_t lds) {
+#ifdef PN2_MLP_STAMP
+  (void)nblocks, (void)lds;
+  return 1;  // one tile per workgroup: the stamps are per tile
+#else
+  int tpw = 1;
+  constexpr int max_tpw = 8, rounds = 4;  // measured: scripts/ab_tpw.sh (DESIGN.md §3.7)
+  const long long slots = (long long)device_cus() * (lds * 2 <= kLdsLimit ? 2 : 1);
+  while (slots > 0 && tpw * 2 <= max_tpw && nblocks >= slots * rounds * tpw * 2) tpw *= 2;
+  return tpw;
+#endif
+}
+
 // Dynamic LDS beyond the 64 KiB default is opted into once per instantiation.
 template <int SRC, int R, bool WL>
 int launch_one(Params prm, long long nblocks, size_t lds, hipStream_t s) {
@@ -1147,21 +1165,10 @@ int launch_one(Params prm, long long nblocks, size_t lds, hipStream_t s) {
       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit);
   if (attr != hipSuccess) return (int)attr;
   prm.ntiles = (int)nblocks;
-  // Several consecutive tiles per workgroup (weights staged once, the next tile's metadata
-  // loads overlapping the current tile's layers), but only as many as keep >= 4 rounds of
-  // workgroups: the dispatcher then still balances around CUs that other streams' kernels
-  // hold (a grid of exactly the co-resident slots with static tile ranges waited for the SA1
-  // sampler's CUs in the whole-model pipeline).
-  prm.tpw = 1;
-  constexpr int max_tpw = 8, rounds = 4;  // measured: scripts/ab_tpw.sh (DESIGN.md §3.7)
-  const long long slots = (long long)device_cus() * (lds * 2 <= kLdsLimit ? 2 : 1);
-  while (slots > 0 && prm.tpw * 2 <= max_tpw && nblocks >= slots * rounds * prm.tpw * 2)
-    prm.tpw *= 2;
-  long long grid = (nblocks + prm.tpw - 1) / prm.tpw;
+  prm.tpw = choose_tpw(nblocks, lds);
+  const long long grid = (nblocks + prm.tpw - 1) / prm.tpw;
 #ifdef PN2_MLP_STAMP
   prm.stamp = g_stamp;
-  prm.tpw = 1;  // one tile per workgroup: the stamps are per tile
-  grid = nblocks;
 #endif
   hipLaunchKernelGGL((mlp_kernel<SRC, R, WL>), dim3((unsigned)grid), dim3(kBlock), lds, s, prm);
   PN2_RETURN_LAUNCH();
@@ -1433,18 +1440,48 @@ int pn2_fp_mlp(const float* dist, const int32_t* nn_idx, const float* points1, i
   return launch_rows_R<kSrcFP>(prm, R, nblocks, lds, (hipStream_t)stream);
 }
 
-int pn2_shared_mlp(const float* x, long long rows, int cin, int nlayers,
-                   const pn2_mlp_layer* layers, float* out, pn2_stream_t stream) {
+// The checks and the row-tile choice that pn2_shared_mlp and pn2_shared_mlp_plan share:
+// PN2_OK with *R = 0 for no rows (nothing to launch), else the R of the launch and its LDS.
+static int shared_mlp_prepare(pn2::Params& prm, long long rows, int cin, int nlayers,
+                              const pn2_mlp_layer* layers, const float* out, int* R,
+                              size_t* lds) {
   using namespace pn2;
+  *R = 0;
   if (rows < 0 || cin <= 0) return PN2_EINVAL;
   int rc = check_layers(nlayers, layers, cin);
   if (rc) return rc;
   if (rows == 0) return PN2_OK;
-  if (!x || !out || rows > 0x7fffffffLL) return PN2_EINVAL;
+  if (rows > 0x7fffffffLL) return PN2_EINVAL;
+  *R = choose_R_staged(prm, nlayers, layers, cin, (rows + 31) / 32, out, lds);
+  return *R ? PN2_OK : PN2_EINVAL;
+}
+
+int pn2_shared_mlp_plan(long long rows, int cin, int nlayers, const pn2_mlp_layer* layers,
+                        int* row_tiles, int* tiles_per_wg) {
+  using namespace pn2;
+  if (!row_tiles || !tiles_per_wg) return PN2_EINVAL;
+  *row_tiles = *tiles_per_wg = 0;
   Params prm = {};
   size_t lds = 0;
-  const int R = choose_R_staged(prm, nlayers, layers, cin, (rows + 31) / 32, out, &lds);
-  if (!R) return PN2_EINVAL;
+  int R = 0;
+  // the output pointer only selects vector stores (out_vec), never R or the LDS size
+  int rc = shared_mlp_prepare(prm, rows, cin, nlayers, layers, nullptr, &R, &lds);
+  if (rc || !R) return rc;
+  const long long nblocks = (rows + 32 * R - 1) / (32 * R);
+  *row_tiles = R;
+  *tiles_per_wg = choose_tpw(nblocks, lds);
+  return PN2_OK;
+}
+
+int pn2_shared_mlp(const float* x, long long rows, int cin, int nlayers,
+                   const pn2_mlp_layer* layers, float* out, pn2_stream_t stream) {
+  using namespace pn2;
+  Params prm = {};
+  size_t lds = 0;
+  int R = 0;
+  if (rows > 0 && (!x || !out)) return PN2_EINVAL;
+  int rc = shared_mlp_prepare(prm, rows, cin, nlayers, layers, out, &R, &lds);
+  if (rc || !R) return rc;
   prm.x = x;
   prm.cin = cin;
   prm.rows = rows;

@@ -213,6 +213,27 @@ def test_mlp_contract(pn2):
     assert lib.pn2_shared_mlp(fake, 10, 8, 2, good, fake, None) == E        # cin != input width
     assert lib.pn2_shared_mlp(fake, 10, 9, 1, misaligned, fake, None) == E
     assert lib.pn2_shared_mlp(None, 0, 9, 2, good, None, None) == 0         # no rows
+    # pn2_shared_mlp_plan: the same checks (it takes no buffers), and nothing to plan for no rows
+    R, tpw = ctypes.c_int(-1), ctypes.c_int(-1)
+    pR, pT = ctypes.addressof(R), ctypes.addressof(tpw)
+    assert lib.pn2_shared_mlp_plan(10, 9, 0, good, pR, pT) == E             # no layers
+    assert lib.pn2_shared_mlp_plan(10, 9, 7, good, pR, pT) == E             # > max layers
+    assert lib.pn2_shared_mlp_plan(10, 9, 2, bad_chain, pR, pT) == E        # cin != prev cout
+    assert lib.pn2_shared_mlp_plan(10, 8, 2, good, pR, pT) == E             # cin != input width
+    assert lib.pn2_shared_mlp_plan(10, 9, 1, misaligned, pR, pT) == E
+    assert lib.pn2_shared_mlp_plan(10, 9, 2, None, pR, pT) == E             # no layer table
+    assert lib.pn2_shared_mlp_plan(-1, 9, 2, good, pR, pT) == E             # rows < 0
+    assert lib.pn2_shared_mlp_plan(10, 0, 2, good, pR, pT) == E             # cin <= 0
+    assert lib.pn2_shared_mlp_plan(1 << 31, 9, 2, good, pR, pT) == E        # rows > INT_MAX
+    assert lib.pn2_shared_mlp(fake, 1 << 31, 9, 2, good, fake, None) == E
+    assert lib.pn2_shared_mlp(fake, -1, 9, 2, good, fake, None) == E
+    assert lib.pn2_shared_mlp(fake, 10, 0, 2, good, fake, None) == E
+    assert lib.pn2_shared_mlp_plan(10, 9, 2, good, None, pT) == E           # no result pointers
+    assert lib.pn2_shared_mlp_plan(10, 9, 2, good, pR, None) == E
+    assert (R.value, tpw.value) == (0, 0)                                   # zeroed on error
+    R.value = tpw.value = -1
+    assert lib.pn2_shared_mlp_plan(0, 9, 2, good, pR, pT) == 0              # no rows
+    assert (R.value, tpw.value) == (0, 0)
     # group source: width = C + 3 with use_xyz; pool mode range
     assert lib.pn2_group_mlp(fake, fake, fake, fake, 1, 10, 6, 4, 8, 1, 2, good, 4, fake,
                              None) == E
