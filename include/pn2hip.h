@@ -38,7 +38,11 @@
  *   pointnet_fp_module   pointnet_util.py:218-238 (interp + MLP)  → pn2_fp_mlp
  *   conv1d head          tf_util.py:52-117, pointnet2_sem_seg.py  → pn2_shared_mlp
  *                        :57-60 (fc1, fc2)
- *   get_subset           scannet_dataset/data_transformation.py  → pn2_scene_bbox,
+ *   conv2d, is_training  tf_util.py:165-185, :512-531 (batch     → pn2_bn_stats, pn2_bn_act_fwd,
+ *                        statistics) and its gradients             pn2_bn_act_bwd, pn2_mlp_wgrad
+ *   conv2d, is_training, pointnet_util.py:106-136 (the last MLP  → pn2_bn_act_pool_fwd,
+ *     + max pool         layer and reduce_max over nsample)        pn2_bn_act_pool_bwd
+ *   get_subset          scannet_dataset/data_transformation.py  → pn2_scene_bbox,
  *                        :70-154 (training crop sampler)           pn2_crop_sample
  *   whole-scene chunker  scannet_dataset/complete_scene_loader.py → pn2_subvolume_select,
  *                        :4-117 (subvolume selection, gathers)     pn2_gather_rows
@@ -502,6 +506,30 @@ int pn2_bn_act_bwd(const float* grad_out, const float* y, long long rows, int C,
                    const float* mean, const float* var, const float* gamma, const float* beta,
                    float eps, int relu, float* grad_y, float* grad_gamma, float* grad_beta,
                    void* workspace, size_t workspace_bytes, pn2_stream_t stream);
+/* pn2_bn_act_fwd fused with the max pool over the ns samples of a group, for the last MLP
+ * layer of a set-abstraction module: y is (groups,ns,C), out[g][c] = max_j act(bn(y[g][j][c]))
+ * (groups,C), bit for bit pn2_bn_act_fwd followed by a max over j, without the (groups,ns,C)
+ * activation being written. The max is over the activation, not over y (gamma may be
+ * negative). arg[g][c] (int32, (groups,C)) is the LOWEST j that attains it: 0 for a group whose
+ * activations are all equal (a dead ReLU channel), and never one of the rows a ball query pads
+ * with copies of its first neighbour. groups * ns <= 2^31 - 1. NaN inputs are unsupported. */
+int pn2_bn_act_pool_fwd(const float* y, long long groups, int ns, int C, const float* mean,
+                        const float* var, const float* gamma, const float* beta, float eps,
+                        int relu, float* out, int* arg, pn2_stream_t stream);
+/* Backward of pn2_bn_act_pool_fwd from grad_out (groups,C): dz[g][j][c] = grad_out[g][c] where
+ * j == arg[g][c] and (no ReLU or the recomputed pre-activation > 0), else 0 (an arg outside
+ * [0, ns) selects nothing); then pn2_bn_act_bwd's formulas with rows = groups * ns, written to
+ * every element of grad_y (groups,ns,C). The sums read one y element per (group, channel):
+ * stage 1 writes one partial per PN2_BN_POOL_BLOCK_GROUPS groups, stage 2 adds them in double
+ * precision in a fixed order. Without batch norm (mean, var, gamma, beta, grad_gamma NULL):
+ * grad_y = dz, grad_beta = sum dz. workspace: pn2_bn_pool_workspace_size(groups, C) bytes. */
+#define PN2_BN_POOL_BLOCK_GROUPS 128
+size_t pn2_bn_pool_workspace_size(long long groups, int C);
+int pn2_bn_act_pool_bwd(const float* grad_out, const int* arg, const float* y, long long groups,
+                        int ns, int C, const float* mean, const float* var, const float* gamma,
+                        const float* beta, float eps, int relu, float* grad_y, float* grad_gamma,
+                        float* grad_beta, void* workspace, size_t workspace_bytes,
+                        pn2_stream_t stream);
 /* grad_w (cin,cout) = x^T grad_y for x (rows,cin), grad_y (rows,cout), on the fp32 matrix
  * cores. Rows are cut into slabs of PN2_WGRAD_SLAB_ROWS; a slab's 32x32 tile product is
  * accumulated in fp32 from zero, slab results are added in double precision and written as at

@@ -21,6 +21,12 @@ idw_weights, fp_fused, group_pool, *_grad), and the training-mode shared-MLP lay
                                                                -> (out, y, mean, var)
     mlp_layer_train_grad(grad_out, x, weight, y, mean, var, gamma, beta, eps, relu, need_grad_x)
                                        -> (grad_x, grad_w, grad_b, grad_gamma, grad_beta)
+    mlp_layer_train_pool(x, weight, bias, gamma, beta, eps, relu)   the same layer on x
+                         (..., ns, cin) fused with the max over ns (pointnet_util.py:130-136)
+                                                               -> (out, y, mean, var, arg)
+    mlp_layer_train_pool_grad(grad_out, arg, x, weight, y, mean, var, gamma, beta, eps, relu,
+                              need_grad_x)
+                                       -> (grad_x, grad_w, grad_b, grad_gamma, grad_beta)
 """
 import importlib
 
@@ -30,7 +36,8 @@ NAMES = ("farthest_point_sample", "farthest_point_sample_and_gather", "gather_po
          "gather_point_grad", "prob_sample", "query_ball_point", "select_top_k", "knn_point",
          "group_point", "group_point_grad", "group_concat", "three_nn", "three_interpolate",
          "three_interpolate_grad", "idw_weights", "fp_fused", "attn_reduce", "attn_reduce_grad",
-         "group_pool", "mlp_layer_train", "mlp_layer_train_grad")
+         "group_pool", "mlp_layer_train", "mlp_layer_train_grad", "mlp_layer_train_pool",
+         "mlp_layer_train_pool_grad")
 for _n in NAMES:
     globals()[_n] = getattr(_ops, _n)
 

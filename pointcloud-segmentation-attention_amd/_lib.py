@@ -143,6 +143,10 @@ SIGNATURES = {
     "pn2_bn_stats": (_I, [_P, _LL, _I, _P, _P, _P, _S, _P]),
     "pn2_bn_act_fwd": (_I, [_P, _LL, _I, _P, _P, _P, _P, _F, _I, _P, _P]),
     "pn2_bn_act_bwd": (_I, [_P, _P, _LL, _I, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _S, _P]),
+    "pn2_bn_act_pool_fwd": (_I, [_P, _LL, _I, _I, _P, _P, _P, _P, _F, _I, _P, _P, _P]),
+    "pn2_bn_pool_workspace_size": (_S, [_LL, _I]),
+    "pn2_bn_act_pool_bwd": (_I, [_P, _P, _P, _LL, _I, _I, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P,
+                                 _S, _P]),
     "pn2_mlp_wgrad_workspace_size": (_S, [_LL, _I, _I]),
     "pn2_mlp_wgrad": (_I, [_P, _P, _LL, _I, _I, _P, _P, _S, _P]),
     "pn2_scene_workspace_size": (_S, [_I]),

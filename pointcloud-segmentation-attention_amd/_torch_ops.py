@@ -5,7 +5,8 @@ tensors / torch.compile. This module loads the library and registers autograd fo
 reference registers gradients for, w.r.t. the points only (tf_sampling.py:44-48 GatherPoint,
 tf_grouping.py:42-46 GroupPoint, tf_interpolate.py:29-34 ThreeInterpolate), plus the attention
 reduction (TF autodiff through attention_layer.py:35-42, all of Q, K, V) and the training-mode
-shared-MLP layer (mlp_layer_train: x, weight, bias, gamma, beta; csrc/mlp_train.hip).
+shared-MLP layer (mlp_layer_train, and mlp_layer_train_pool for the layer fused with the max
+pool over nsample: x, weight, bias, gamma, beta; csrc/mlp_train.hip).
 
 The mirror modules (tf_sampling, tf_grouping, tf_interpolate, attention_layer) call these ops
 for every reference-signature call; the pn2hip alias package re-exports them as pn2hip.ops.
@@ -87,7 +88,25 @@ def _register_autograd():
         return (gx if ctx.needs_input_grad[0] else None, gw, gb if ctx.has_bias else None,
                 gg if bn else None, gbeta if bn else None, None, None)
 
+    def mlp_pool_setup(ctx, inputs, output):
+        x, weight, bias, gamma, beta, eps, relu = inputs
+        out, y, mean, var, arg = output
+        ctx.mark_non_differentiable(y, mean, var, arg)
+        ctx.save_for_backward(x, weight, y, mean, var, arg, gamma, beta)
+        ctx.eps, ctx.relu, ctx.has_bias = eps, relu, bias is not None
+
+    def mlp_pool_bwd(ctx, grad_out, *_):
+        # grad_out is (..., cout): the (..., ns, cout) gradient of the activation never exists
+        x, weight, y, mean, var, arg, gamma, beta = ctx.saved_tensors
+        gx, gw, gb, gg, gbeta = torch.ops.pn2.mlp_layer_train_pool_grad(
+            grad_out.contiguous(), arg, x, weight, y, mean, var, gamma, beta, ctx.eps, ctx.relu,
+            ctx.needs_input_grad[0])
+        bn = gamma is not None
+        return (gx if ctx.needs_input_grad[0] else None, gw, gb if ctx.has_bias else None,
+                gg if bn else None, gbeta if bn else None, None, None)
+
     reg("pn2::mlp_layer_train", mlp_layer_bwd, setup_context=mlp_layer_setup)
+    reg("pn2::mlp_layer_train_pool", mlp_pool_bwd, setup_context=mlp_pool_setup)
     reg("pn2::gather_point", gather_bwd, setup_context=save_all)
     reg("pn2::group_point", group_bwd, setup_context=save_all)
     reg("pn2::three_interpolate", interp_bwd, setup_context=save_all)

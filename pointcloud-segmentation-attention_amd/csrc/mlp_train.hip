@@ -7,6 +7,10 @@
 //   backward   grad_y, grad_gamma, grad_beta = pn2_bn_act_bwd(grad_out, y, ...)
 //              grad_w = x^T grad_y    pn2_mlp_wgrad    (fp32 matrix cores)
 //              grad_x = grad_y W^T    pn2_shared_mlp over a pn2_mlp_pack of W^T
+//   last layer of a set-abstraction MLP, fused with the max pool over the ns samples of a group
+//   (y is (groups, ns, C)):
+//              out, arg = max_j act(bn(y))                        pn2_bn_act_pool_fwd
+//              grad_y, grad_gamma, grad_beta from (groups, C) grad_out  pn2_bn_act_pool_bwd
 //
 // Reductions are two-stage and ordered: stage 1 writes one partial per workgroup, stage 2
 // combines the partials in a fixed order in double precision. No floating-point atomics, so
@@ -37,6 +41,8 @@ constexpr int kBatch = 8;                    // rows per thread per step
 constexpr int kStep = kRowLanes * kBatch;    // 64 rows per workgroup step
 constexpr int kStatRows = PN2_BN_BLOCK_ROWS;  // rows per stage-1 partial (stats, bwd sums)
 constexpr int kActRows = 256;                 // rows per workgroup of the element-wise passes
+constexpr int kPoolGroups = PN2_BN_POOL_BLOCK_GROUPS;  // groups per stage-1 partial (pool bwd)
+constexpr int kPoolSplit = 64;                // above this ns a group is split across row lanes
 constexpr int kSlab = PN2_WGRAD_SLAB_ROWS;
 constexpr int kTile = 32 * 32;
 
@@ -303,6 +309,287 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply(
   }
 }
 
+// ---------------------------------------------------------------- activation + max pool --
+// The last layer of a set-abstraction MLP: out[g][c] = max_j act(bn(y[g][j][c])) over the ns
+// samples of group g, arg = the lowest j that attains it. The max is taken over the
+// activation, never over y: gamma may be negative, so bn can be decreasing in y. Candidates are
+// visited in ascending j and replace the best only on a strict >, so ties keep the lowest j:
+// an all-zero group gives arg 0, and the rows a ball query pads with copies of its first
+// neighbour (j = 0) never win.
+//
+// Two layouts, picked by ns on the host:
+//   groups (ns <= kPoolSplit): thread (cl, rl) owns whole groups rl, rl + 8, ... of the
+//     workgroup's block and walks their samples eight at a time; nothing crosses lanes.
+//   split  (ns >  kPoolSplit): a workgroup owns one group; row lane rl walks samples rl,
+//     rl + 8, ... and the eight lanes' (value, j) pairs are combined through LDS by
+//     (value descending, j ascending). Parallelism is groups x channel tiles x 256 threads, so
+//     group_all (groups = B, ns = N) still fills the row lanes.
+PN2_DEV float pool_act(float pre, int relu) { return relu ? fmaxf(pre, 0.f) : pre; }
+
+template <bool BN>
+__global__ __launch_bounds__(kBlock) void bn_act_pool_fwd_groups(
+    const float* __restrict__ y, long long groups, int ns, int C, int gpt,
+    const float* __restrict__ mean, const float* __restrict__ var,
+    const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int relu,
+    float* __restrict__ out, int* __restrict__ arg) {
+  const int cl = threadIdx.x & (kCols - 1), rl = threadIdx.x / kCols;
+  const int c = blockIdx.y * kCols + cl;
+  if (c >= C) return;
+  float m = 0.f, s = 1.f, b = 0.f;
+  if (BN) {
+    m = mean[c];
+    s = bn_scale(gamma[c], var[c], eps);
+    b = beta[c];
+  }
+  const long long g0 = (long long)blockIdx.x * (kRowLanes * gpt);
+  for (int t = 0; t < gpt; ++t) {
+    const long long g = g0 + rl + kRowLanes * t;
+    if (g >= groups) break;
+    const float* p = y + g * ns * C + c;
+    float best = 0.f;
+    int bj = 0;
+    for (int base = 0; base < ns; base += kBatch) {
+      float v[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) v[u] = base + u < ns ? p[(long long)(base + u) * C] : 0.f;
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int j = base + u;
+        const float a = pool_act(BN ? bn_pre(v[u], m, s, b) : v[u], relu);
+        if (j < ns && (j == 0 || a > best)) {
+          best = a;
+          bj = j;
+        }
+      }
+    }
+    out[g * C + c] = best;
+    arg[g * C + c] = bj;
+  }
+}
+
+template <bool BN>
+__global__ __launch_bounds__(kBlock) void bn_act_pool_fwd_split(
+    const float* __restrict__ y, int ns, int C, const float* __restrict__ mean,
+    const float* __restrict__ var, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float eps, int relu, float* __restrict__ out,
+    int* __restrict__ arg) {
+  __shared__ float shv[kRowLanes][kCols];
+  __shared__ int shj[kRowLanes][kCols];
+  const int cl = threadIdx.x & (kCols - 1), rl = threadIdx.x / kCols;
+  const int c = blockIdx.y * kCols + cl;
+  const long long g = blockIdx.x;
+  float best = 0.f;
+  int bj = -1;  // no sample seen yet
+  if (c < C) {
+    float m = 0.f, s = 1.f, b = 0.f;
+    if (BN) {
+      m = mean[c];
+      s = bn_scale(gamma[c], var[c], eps);
+      b = beta[c];
+    }
+    const float* p = y + g * ns * C + c;
+    for (int base = 0; base + rl < ns; base += kStep) {
+      float v[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int j = base + rl + kRowLanes * u;
+        v[u] = j < ns ? p[(long long)j * C] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int j = base + rl + kRowLanes * u;
+        const float a = pool_act(BN ? bn_pre(v[u], m, s, b) : v[u], relu);
+        if (j < ns && (bj < 0 || a > best)) {
+          best = a;
+          bj = j;
+        }
+      }
+    }
+  }
+  shv[rl][cl] = best;
+  shj[rl][cl] = bj;
+  __syncthreads();
+  if (rl == 0 && c < C) {  // row lane 0 holds j = 0, so bj >= 0 here
+    for (int k = 1; k < kRowLanes; ++k) {
+      const float v = shv[k][cl];
+      const int j = shj[k][cl];
+      if (j >= 0 && (v > best || (v == best && j < bj))) {
+        best = v;
+        bj = j;
+      }
+    }
+    out[g * C + c] = best;
+    arg[g * C + c] = bj;
+  }
+}
+
+// backward, stage 1 of the sums: dz is grad_out[g][c] at j = arg[g][c] (masked by the
+// recomputed pre-activation) and 0 elsewhere, so the sums read one gathered y element per
+// (group, channel). part[(blk * 2 + 0) * C + c] = sum dz, [(blk * 2 + 1) * C + c] = sum dz *
+// xhat over the kPoolGroups groups of block blk; stage 2 is bn_bwd_final. An arg outside
+// [0, ns) selects nothing.
+template <bool BN>
+__global__ __launch_bounds__(kBlock) void bn_pool_bwd_partial(
+    const float* __restrict__ go, const int* __restrict__ arg, const float* __restrict__ y,
+    long long groups, int ns, int C, const float* __restrict__ mean,
+    const float* __restrict__ var, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float eps, int relu, float* __restrict__ part) {
+  __shared__ float sh[2][kRowLanes][kCols];
+  const int cl = threadIdx.x & (kCols - 1), rl = threadIdx.x / kCols;
+  const int c = blockIdx.y * kCols + cl;
+  const long long g0 = (long long)blockIdx.x * kPoolGroups;
+  const int ng = block_rows(groups, g0, kPoolGroups);
+  float db = 0.f, dg = 0.f;
+  if (c < C) {
+    float m = 0.f, s = 1.f, b = 0.f, rstd = 1.f;
+    if (BN) {
+      m = mean[c];
+      s = bn_scale(gamma[c], var[c], eps);
+      b = beta[c];
+      rstd = __fdiv_rn(1.f, __fsqrt_rn(__fadd_rn(var[c], eps)));
+    }
+    const bool need_y = BN || relu;
+    for (int base = 0; base + rl < ng; base += kStep) {
+      float v[kBatch], gr[kBatch];
+      int a[kBatch];
+      bool ok[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int r = base + rl + kRowLanes * u;
+        const bool in = r < ng;
+        a[u] = in ? arg[(g0 + r) * C + c] : -1;
+        gr[u] = in ? go[(g0 + r) * C + c] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int r = base + rl + kRowLanes * u;
+        ok[u] = a[u] >= 0 && a[u] < ns;
+        v[u] = (ok[u] && need_y) ? y[((g0 + r) * ns + a[u]) * C + c] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const float pre = BN ? bn_pre(v[u], m, s, b) : v[u];
+        const float dz = (ok[u] && (!relu || pre > 0.f)) ? gr[u] : 0.f;
+        db += dz;
+        if (BN) dg += dz * ((v[u] - m) * rstd);
+      }
+    }
+  }
+  sh[0][rl][cl] = db;
+  sh[1][rl][cl] = dg;
+  __syncthreads();
+  if (rl == 0 && c < C) {
+    for (int k = 1; k < kRowLanes; ++k) {
+      db += sh[0][k][cl];
+      dg += sh[1][k][cl];
+    }
+    part[((size_t)blockIdx.x * 2 + 0) * C + c] = db;
+    part[((size_t)blockIdx.x * 2 + 1) * C + c] = dg;
+  }
+}
+
+// per-channel constants of the apply pass and its element: bn_bwd_apply's expression with dz
+// non-zero only at j = arg; without batch norm grad_y = dz
+struct PoolApply {
+  float m, s, b, rstd, mb, mg;
+};
+template <bool BN>
+PN2_DEV PoolApply pool_apply_consts(int c, long long rows, const float* mean, const float* var,
+                                    const float* gamma, const float* beta, float eps,
+                                    const float* grad_gamma, const float* grad_beta) {
+  PoolApply k = {0.f, 1.f, 0.f, 1.f, 0.f, 0.f};
+  if (BN) {
+    k.m = mean[c];
+    k.b = beta[c];
+    k.s = bn_scale(gamma[c], var[c], eps);
+    k.rstd = __fdiv_rn(1.f, __fsqrt_rn(__fadd_rn(var[c], eps)));
+    const float inv_rows = (float)(1.0 / (double)rows);
+    k.mb = grad_beta[c] * inv_rows;
+    k.mg = grad_gamma[c] * inv_rows;
+  }
+  return k;
+}
+template <bool BN>
+PN2_DEV float pool_apply(const PoolApply& k, float v, bool hit, float g, int relu) {
+  const float pre = BN ? bn_pre(v, k.m, k.s, k.b) : v;
+  const float dz = (hit && (!relu || pre > 0.f)) ? g : 0.f;
+  if (!BN) return dz;
+  const float xhat = (v - k.m) * k.rstd;
+  return k.s * ((dz - k.mb) - xhat * k.mg);
+}
+
+// backward, apply pass, the forward's two layouts. split: blockIdx.x = group * nchunk + chunk
+// of kActRows samples (no combine here, so a group may span workgroups).
+template <bool BN>
+__global__ __launch_bounds__(kBlock) void bn_pool_bwd_apply_groups(
+    const float* __restrict__ go, const int* __restrict__ arg, const float* __restrict__ y,
+    long long groups, int ns, int C, int gpt, const float* __restrict__ mean,
+    const float* __restrict__ var, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float eps, int relu, const float* __restrict__ grad_gamma,
+    const float* __restrict__ grad_beta, float* __restrict__ grad_y) {
+  const int cl = threadIdx.x & (kCols - 1), rl = threadIdx.x / kCols;
+  const int c = blockIdx.y * kCols + cl;
+  if (c >= C) return;
+  const PoolApply k = pool_apply_consts<BN>(c, groups * ns, mean, var, gamma, beta, eps,
+                                            grad_gamma, grad_beta);
+  const bool need_y = BN || relu;
+  const long long g0 = (long long)blockIdx.x * (kRowLanes * gpt);
+  for (int t = 0; t < gpt; ++t) {
+    const long long g = g0 + rl + kRowLanes * t;
+    if (g >= groups) break;
+    const float gr = go[g * C + c];
+    const int a = arg[g * C + c];
+    const float* p = y + g * ns * C + c;
+    float* pd = grad_y + g * ns * C + c;
+    for (int base = 0; base < ns; base += kBatch) {
+      float v[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u)
+        v[u] = (base + u < ns && need_y) ? p[(long long)(base + u) * C] : 0.f;
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int j = base + u;
+        if (j < ns) pd[(long long)j * C] = pool_apply<BN>(k, v[u], j == a, gr, relu);
+      }
+    }
+  }
+}
+
+template <bool BN>
+__global__ __launch_bounds__(kBlock) void bn_pool_bwd_apply_split(
+    const float* __restrict__ go, const int* __restrict__ arg, const float* __restrict__ y,
+    long long groups, int ns, int C, int nchunk, const float* __restrict__ mean,
+    const float* __restrict__ var, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float eps, int relu, const float* __restrict__ grad_gamma,
+    const float* __restrict__ grad_beta, float* __restrict__ grad_y) {
+  const int cl = threadIdx.x & (kCols - 1), rl = threadIdx.x / kCols;
+  const int c = blockIdx.y * kCols + cl;
+  if (c >= C) return;
+  const PoolApply k = pool_apply_consts<BN>(c, groups * ns, mean, var, gamma, beta, eps,
+                                            grad_gamma, grad_beta);
+  const bool need_y = BN || relu;
+  const long long g = blockIdx.x / nchunk;
+  const int j0 = (int)(blockIdx.x % nchunk) * kActRows;
+  const int nr = block_rows(ns, j0, kActRows);
+  const float gr = go[g * C + c];
+  const int a = arg[g * C + c] - j0;  // the winner's row within this chunk, if it is here
+  const float* p = y + (g * ns + j0) * C + c;
+  float* pd = grad_y + (g * ns + j0) * C + c;
+  for (int base = 0; base + rl < nr; base += kStep) {
+    float v[kBatch];
+#pragma unroll
+    for (int u = 0; u < kBatch; ++u) {
+      const int r = base + rl + kRowLanes * u;
+      v[u] = (r < nr && need_y) ? p[(long long)r * C] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < kBatch; ++u) {
+      const int r = base + rl + kRowLanes * u;
+      if (r < nr) pd[(long long)r * C] = pool_apply<BN>(k, v[u], r == a, gr, relu);
+    }
+  }
+}
+
 // ---------------------------------------------------------------- weight gradient -------
 // blockIdx.x = part p (slabs p, p + nparts, ...), blockIdx.y = (ti, tjg): input-channel tile
 // ti and output-channel tiles tjg * NJ .. + NJ - 1. Partial tiles are stored in accumulator
@@ -423,6 +710,19 @@ int wgrad_parts(long long rows, int cin, int cout) {
 
 int wgrad_nj(int cout32) { return cout32 >= 4 ? 4 : (cout32 >= 2 ? 2 : 1); }
 
+// groups per thread of the pooled kernels' groups layout: about kActRows rows per workgroup
+int pool_gpt(int ns) {
+  const int g = kActRows / kRowLanes / ns;
+  return g < 1 ? 1 : g;
+}
+
+// the argument checks the pooled forward and backward share; rows = groups * ns on success
+bool pool_shape_ok(long long groups, int ns, int C, long long* rows) {
+  if (groups <= 0 || ns <= 0 || C <= 0 || C > kMaxC || groups > kMaxRows) return false;
+  *rows = groups * ns;  // both below 2^31: no overflow
+  return *rows <= kMaxRows;
+}
+
 }  // namespace
 }  // namespace pn2
 
@@ -494,6 +794,97 @@ int pn2_bn_act_bwd(const float* grad_out, const float* y, long long rows, int C,
                        rows, C, mean, var, gamma, beta, eps, relu ? 1 : 0, grad_y, part);
     hipLaunchKernelGGL(bn_bwd_final, dim3(ct), dim3(kBlock), 0, s, part, C, nblk, grad_gamma,
                        grad_beta);
+  }
+  PN2_RETURN_LAUNCH();
+}
+
+int pn2_bn_act_pool_fwd(const float* y, long long groups, int ns, int C, const float* mean,
+                        const float* var, const float* gamma, const float* beta, float eps,
+                        int relu, float* out, int* arg, pn2_stream_t stream) {
+  using namespace pn2;
+  long long rows;
+  if (!pool_shape_ok(groups, ns, C, &rows) || !y || !out || !arg) return PN2_EINVAL;
+  const int given = (mean ? 1 : 0) + (var ? 1 : 0) + (gamma ? 1 : 0) + (beta ? 1 : 0);
+  if (given != 0 && given != 4) return PN2_EINVAL;
+  if (given && !(eps >= 0.f)) return PN2_EINVAL;
+  const unsigned ct = (unsigned)ceil_div(C, kCols);
+  hipStream_t s = (hipStream_t)stream;
+  const int r = relu ? 1 : 0;
+  if (ns <= kPoolSplit) {
+    const int gpt = pool_gpt(ns);
+    const dim3 grid((unsigned)ceil_div(groups, (long long)kRowLanes * gpt), ct);
+    if (given)
+      hipLaunchKernelGGL(bn_act_pool_fwd_groups<true>, grid, dim3(kBlock), 0, s, y, groups, ns, C,
+                         gpt, mean, var, gamma, beta, eps, r, out, arg);
+    else
+      hipLaunchKernelGGL(bn_act_pool_fwd_groups<false>, grid, dim3(kBlock), 0, s, y, groups, ns, C,
+                         gpt, mean, var, gamma, beta, eps, r, out, arg);
+  } else {
+    const dim3 grid((unsigned)groups, ct);
+    if (given)
+      hipLaunchKernelGGL(bn_act_pool_fwd_split<true>, grid, dim3(kBlock), 0, s, y, ns, C, mean,
+                         var, gamma, beta, eps, r, out, arg);
+    else
+      hipLaunchKernelGGL(bn_act_pool_fwd_split<false>, grid, dim3(kBlock), 0, s, y, ns, C, mean,
+                         var, gamma, beta, eps, r, out, arg);
+  }
+  PN2_RETURN_LAUNCH();
+}
+
+size_t pn2_bn_pool_workspace_size(long long groups, int C) {
+  if (groups <= 0 || C <= 0) return 0;
+  return (size_t)pn2::ceil_div(groups, pn2::kPoolGroups) * 2 * (size_t)C * sizeof(float);
+}
+
+int pn2_bn_act_pool_bwd(const float* grad_out, const int* arg, const float* y, long long groups,
+                        int ns, int C, const float* mean, const float* var, const float* gamma,
+                        const float* beta, float eps, int relu, float* grad_y, float* grad_gamma,
+                        float* grad_beta, void* workspace, size_t workspace_bytes,
+                        pn2_stream_t stream) {
+  using namespace pn2;
+  long long rows;
+  if (!pool_shape_ok(groups, ns, C, &rows)) return PN2_EINVAL;
+  if (!grad_out || !arg || !y || !grad_y || !grad_beta || !workspace) return PN2_EINVAL;
+  const int given = (mean ? 1 : 0) + (var ? 1 : 0) + (gamma ? 1 : 0) + (beta ? 1 : 0);
+  if (given != 0 && given != 4) return PN2_EINVAL;
+  if ((given != 0) != (grad_gamma != nullptr)) return PN2_EINVAL;
+  if (given && !(eps >= 0.f)) return PN2_EINVAL;
+  if (workspace_bytes < pn2_bn_pool_workspace_size(groups, C)) return PN2_EINVAL;
+  const int nblk = (int)ceil_div(groups, kPoolGroups);
+  const unsigned ct = (unsigned)ceil_div(C, kCols);
+  float* part = static_cast<float*>(workspace);
+  hipStream_t s = (hipStream_t)stream;
+  const int r = relu ? 1 : 0;
+  if (given)
+    hipLaunchKernelGGL(bn_pool_bwd_partial<true>, dim3(nblk, ct), dim3(kBlock), 0, s, grad_out,
+                       arg, y, groups, ns, C, mean, var, gamma, beta, eps, r, part);
+  else
+    hipLaunchKernelGGL(bn_pool_bwd_partial<false>, dim3(nblk, ct), dim3(kBlock), 0, s, grad_out,
+                       arg, y, groups, ns, C, mean, var, gamma, beta, eps, r, part);
+  hipLaunchKernelGGL(bn_bwd_final, dim3(ct), dim3(kBlock), 0, s, part, C, nblk, grad_gamma,
+                     grad_beta);
+  if (ns <= kPoolSplit) {
+    const int gpt = pool_gpt(ns);
+    const dim3 grid((unsigned)ceil_div(groups, (long long)kRowLanes * gpt), ct);
+    if (given)
+      hipLaunchKernelGGL(bn_pool_bwd_apply_groups<true>, grid, dim3(kBlock), 0, s, grad_out, arg,
+                         y, groups, ns, C, gpt, mean, var, gamma, beta, eps, r, grad_gamma,
+                         grad_beta, grad_y);
+    else
+      hipLaunchKernelGGL(bn_pool_bwd_apply_groups<false>, grid, dim3(kBlock), 0, s, grad_out, arg,
+                         y, groups, ns, C, gpt, mean, var, gamma, beta, eps, r, grad_gamma,
+                         grad_beta, grad_y);
+  } else {
+    const int nchunk = (int)ceil_div(ns, kActRows);
+    const dim3 grid((unsigned)(groups * nchunk), ct);
+    if (given)
+      hipLaunchKernelGGL(bn_pool_bwd_apply_split<true>, grid, dim3(kBlock), 0, s, grad_out, arg, y,
+                         groups, ns, C, nchunk, mean, var, gamma, beta, eps, r, grad_gamma,
+                         grad_beta, grad_y);
+    else
+      hipLaunchKernelGGL(bn_pool_bwd_apply_split<false>, grid, dim3(kBlock), 0, s, grad_out, arg,
+                         y, groups, ns, C, nchunk, mean, var, gamma, beta, eps, r, grad_gamma,
+                         grad_beta, grad_y);
   }
   PN2_RETURN_LAUNCH();
 }

@@ -11,7 +11,8 @@
 // and torch.compile). Autograd for gather_point / group_point / three_interpolate (w.r.t.
 // the points only, tf_sampling.py:44-48, tf_grouping.py:42-46, tf_interpolate.py:29-34) and
 // attn_reduce is registered from Python (torch.library.register_autograd, _torch_ops.py), and
-// so is the training-mode shared-MLP layer's (mlp_layer_train -> mlp_layer_train_grad).
+// so is the training-mode shared-MLP layer's (mlp_layer_train -> mlp_layer_train_grad, and
+// mlp_layer_train_pool -> mlp_layer_train_pool_grad for the layer fused with the max pool).
 // CPU kernels exist only for the three ops the reference itself runs on the CPU (ThreeNN,
 // ThreeInterpolate, ThreeInterpolateGrad: registered for DEVICE_CPU only,
 // tf_interpolate.cpp:187,222,262), through the host twins pn2cpu_* (csrc/cpu_interp.cpp);
@@ -574,6 +575,133 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_grad_hip(
   return {grad_x, grad_w, grad_b, grad_gamma, grad_beta};
 }
 
+// ---- the last layer of a set-abstraction MLP fused with the max pool over nsample
+// (pn2_bn_act_pool_fwd / _bwd): x (..., ns, cin) -> out, arg (..., cout); the (..., ns, cout)
+// activation is never allocated
+void chk_mlp_pool(const Tensor& x, const Tensor& weight, const std::optional<Tensor>& bias,
+                  const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta,
+                  const char* name) {
+  TORCH_CHECK_VALUE(x.dim() >= 2, name, " expects (..., ns, cin) x");
+  chk_mlp_layer(x, weight, bias, gamma, beta, name);
+  TORCH_CHECK_VALUE(x.size(-2) > 0, name, " expects at least one sample per group");
+}
+std::vector<int64_t> pooled_sizes(const Tensor& x, int64_t c) {
+  std::vector<int64_t> s(x.sizes().begin(), x.sizes().end() - 2);
+  s.push_back(c);
+  return s;
+}
+void chk_mlp_pool_grad(const Tensor& grad_out, const Tensor& arg, const Tensor& x,
+                       const Tensor& weight, const Tensor& y, const std::optional<Tensor>& mean,
+                       const std::optional<Tensor>& var, const std::optional<Tensor>& gamma,
+                       const std::optional<Tensor>& beta, const char* op) {
+  chk_mlp_pool(x, weight, std::nullopt, gamma, beta, op);
+  const int64_t cout = weight.size(1);
+  TORCH_CHECK_VALUE(y.sizes() == c10::IntArrayRef(with_last(x, cout)), op,
+                    " expects (..., ns, cout) y for (..., ns, cin) x");
+  TORCH_CHECK_VALUE(grad_out.sizes() == c10::IntArrayRef(pooled_sizes(x, cout)) &&
+                        arg.sizes() == grad_out.sizes(),
+                    op, " expects (..., cout) grad_out and arg for (..., ns, cin) x");
+  if (has(gamma))
+    TORCH_CHECK_VALUE(has(mean) && has(var) && mean->dim() == 1 && mean->size(0) == cout &&
+                          var->dim() == 1 && var->size(0) == cout,
+                      op, " expects (cout) mean and var with gamma and beta");
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_pool_hip(
+    const Tensor& x_, const Tensor& weight_, const std::optional<Tensor>& bias_,
+    const std::optional<Tensor>& gamma_, const std::optional<Tensor>& beta_, double eps,
+    bool relu) {
+  const char* op = "mlp_layer_train_pool";
+  chk_mlp_pool(x_, weight_, bias_, gamma_, beta_, op);
+  Tensor x = dev(x_, "x", at::kFloat), weight = dev(weight_, "weight", at::kFloat);
+  Tensor bias, gamma, beta;
+  if (has(bias_)) bias = dev(*bias_, "bias", at::kFloat);
+  const bool bn = has(gamma_);
+  if (bn) {
+    gamma = dev(*gamma_, "gamma", at::kFloat);
+    beta = dev(*beta_, "beta", at::kFloat);
+  }
+  c10::hip::HIPGuard g(x.device().index());
+  const int cin = I(weight.size(0)), cout = I(weight.size(1));
+  const int64_t rows = x.numel() / cin, ns = x.size(-2), groups = rows / ns;
+  Tensor out = at::empty(pooled_sizes(x, cout), f32(x));
+  Tensor arg = at::empty(pooled_sizes(x, cout), i32(x));
+  Tensor y = at::empty(with_last(x, cout), f32(x));
+  Tensor mean = at::empty({bn ? cout : 0}, f32(x)), var = at::empty({bn ? cout : 0}, f32(x));
+  if (rows == 0) {
+    mean.zero_();
+    var.zero_();
+    return {out, y, mean, var, arg};
+  }
+  // y, mean and var by the calls of mlp_layer_train: the same bits
+  linear_rows(x, weight, bias, rows, y, op);
+  if (bn) {
+    const size_t ws = pn2_bn_workspace_size(rows, cout);
+    Tensor w = workspace(x, ws);
+    check_rc(pn2_bn_stats(F(y), rows, cout, mean.data_ptr<float>(), var.data_ptr<float>(), P(w),
+                          ws, stream_of(x)), op);
+  }
+  check_rc(pn2_bn_act_pool_fwd(F(y), groups, I(ns), cout, bn ? F(mean) : nullptr,
+                               bn ? F(var) : nullptr, F(gamma), F(beta), static_cast<float>(eps),
+                               relu ? 1 : 0, out.data_ptr<float>(), arg.data_ptr<int32_t>(),
+                               stream_of(x)), op);
+  return {out, y, mean, var, arg};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_pool_grad_hip(
+    const Tensor& grad_out_, const Tensor& arg_, const Tensor& x_, const Tensor& weight_,
+    const Tensor& y_, const std::optional<Tensor>& mean_, const std::optional<Tensor>& var_,
+    const std::optional<Tensor>& gamma_, const std::optional<Tensor>& beta_, double eps, bool relu,
+    bool need_grad_x) {
+  const char* op = "mlp_layer_train_pool_grad";
+  chk_mlp_pool_grad(grad_out_, arg_, x_, weight_, y_, mean_, var_, gamma_, beta_, op);
+  const bool bn = has(gamma_);
+  const int cin = I(weight_.size(0)), cout = I(weight_.size(1));
+  Tensor go = dev(grad_out_, "grad_out", at::kFloat), arg = dev(arg_, "arg", at::kInt);
+  Tensor x = dev(x_, "x", at::kFloat), weight = dev(weight_, "weight", at::kFloat);
+  Tensor y = dev(y_, "y", at::kFloat);
+  Tensor mean, var, gamma, beta;
+  if (bn) {
+    mean = dev(*mean_, "mean", at::kFloat);
+    var = dev(*var_, "var", at::kFloat);
+    gamma = dev(*gamma_, "gamma", at::kFloat);
+    beta = dev(*beta_, "beta", at::kFloat);
+  }
+  c10::hip::HIPGuard g(x.device().index());
+  const int64_t rows = x.numel() / cin, ns = x.size(-2), groups = rows / ns;
+  Tensor grad_x = need_grad_x ? at::empty(x.sizes(), f32(x)) : at::empty({0}, f32(x));
+  Tensor grad_w = at::empty({cin, cout}, f32(x));
+  Tensor grad_b = bn ? at::zeros({cout}, f32(x)) : at::empty({cout}, f32(x));
+  Tensor grad_gamma = at::empty({bn ? cout : 0}, f32(x));
+  Tensor grad_beta = at::empty({bn ? cout : 0}, f32(x));
+  if (rows == 0) {
+    grad_w.zero_();
+    grad_b.zero_();
+    grad_gamma.zero_();
+    grad_beta.zero_();
+    return {grad_x, grad_w, grad_b, grad_gamma, grad_beta};
+  }
+  Tensor grad_y = at::empty(y.sizes(), f32(x));
+  {
+    const size_t ws = pn2_bn_pool_workspace_size(groups, cout);
+    Tensor w = workspace(x, ws);
+    check_rc(pn2_bn_act_pool_bwd(F(go), Ii(arg), F(y), groups, I(ns), cout, F(mean), F(var),
+                                 F(gamma), F(beta), static_cast<float>(eps), relu ? 1 : 0,
+                                 grad_y.data_ptr<float>(),
+                                 bn ? grad_gamma.data_ptr<float>() : nullptr,
+                                 bn ? grad_beta.data_ptr<float>() : grad_b.data_ptr<float>(),
+                                 P(w), ws, stream_of(x)), op);
+  }
+  {
+    const size_t ws = pn2_mlp_wgrad_workspace_size(rows, cin, cout);
+    Tensor w = workspace(x, ws);
+    check_rc(pn2_mlp_wgrad(F(x), F(grad_y), rows, cin, cout, grad_w.data_ptr<float>(), P(w), ws,
+                           stream_of(x)), op);
+  }
+  if (need_grad_x) linear_rows(grad_y, weight.t().contiguous(), Tensor(), rows, grad_x, op);
+  return {grad_x, grad_w, grad_b, grad_gamma, grad_beta};
+}
+
 // ------------------------------------------------------------------------- CPU kernels
 // (the reference's CPU-only ops; host twins in csrc/cpu_interp.cpp)
 Tensor host(const Tensor& t, const char* name, at::ScalarType dt) {
@@ -730,6 +858,27 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_grad_meta(
           at::empty(weight.sizes(), mf(x)), at::empty({cout}, mf(x)), at::empty({nstat}, mf(x)),
           at::empty({nstat}, mf(x))};
 }
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_pool_meta(
+    const Tensor& x, const Tensor& weight, const std::optional<Tensor>& bias,
+    const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta, double, bool) {
+  chk_mlp_pool(x, weight, bias, gamma, beta, "mlp_layer_train_pool");
+  const int64_t cout = weight.size(1), nstat = has(gamma) ? cout : 0;
+  return {at::empty(pooled_sizes(x, cout), mf(x)), at::empty(with_last(x, cout), mf(x)),
+          at::empty({nstat}, mf(x)), at::empty({nstat}, mf(x)),
+          at::empty(pooled_sizes(x, cout), mi(x))};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_pool_grad_meta(
+    const Tensor& grad_out, const Tensor& arg, const Tensor& x, const Tensor& weight,
+    const Tensor& y, const std::optional<Tensor>& mean, const std::optional<Tensor>& var,
+    const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta, double, bool,
+    bool need_grad_x) {
+  chk_mlp_pool_grad(grad_out, arg, x, weight, y, mean, var, gamma, beta,
+                    "mlp_layer_train_pool_grad");
+  const int64_t cout = weight.size(1), nstat = has(gamma) ? cout : 0;
+  return {need_grad_x ? at::empty(x.sizes(), mf(x)) : at::empty({0}, mf(x)),
+          at::empty(weight.sizes(), mf(x)), at::empty({cout}, mf(x)), at::empty({nstat}, mf(x)),
+          at::empty({nstat}, mf(x))};
+}
 
 }  // namespace
 
@@ -761,6 +910,12 @@ TORCH_LIBRARY(pn2, m) {
   m.def("mlp_layer_train_grad(Tensor grad_out, Tensor x, Tensor weight, Tensor y, Tensor? mean, "
         "Tensor? var, Tensor? gamma, Tensor? beta, float eps, bool relu, bool need_grad_x) -> "
         "(Tensor grad_x, Tensor grad_w, Tensor grad_b, Tensor grad_gamma, Tensor grad_beta)");
+  m.def("mlp_layer_train_pool(Tensor x, Tensor weight, Tensor? bias, Tensor? gamma, Tensor? beta, "
+        "float eps, bool relu) -> (Tensor out, Tensor y, Tensor mean, Tensor var, Tensor arg)");
+  m.def("mlp_layer_train_pool_grad(Tensor grad_out, Tensor arg, Tensor x, Tensor weight, Tensor y, "
+        "Tensor? mean, Tensor? var, Tensor? gamma, Tensor? beta, float eps, bool relu, "
+        "bool need_grad_x) -> "
+        "(Tensor grad_x, Tensor grad_w, Tensor grad_b, Tensor grad_gamma, Tensor grad_beta)");
 }
 
 // ROCm builds of PyTorch dispatch HIP tensors under the CUDA key.
@@ -786,6 +941,8 @@ TORCH_LIBRARY_IMPL(pn2, CUDA, m) {
   m.impl("group_pool", &group_pool_hip);
   m.impl("mlp_layer_train", &mlp_layer_train_hip);
   m.impl("mlp_layer_train_grad", &mlp_layer_train_grad_hip);
+  m.impl("mlp_layer_train_pool", &mlp_layer_train_pool_hip);
+  m.impl("mlp_layer_train_pool_grad", &mlp_layer_train_pool_grad_hip);
 }
 
 TORCH_LIBRARY_IMPL(pn2, CPU, m) {
@@ -816,4 +973,6 @@ TORCH_LIBRARY_IMPL(pn2, Meta, m) {
   m.impl("group_pool", &group_pool_meta);
   m.impl("mlp_layer_train", &mlp_layer_train_meta);
   m.impl("mlp_layer_train_grad", &mlp_layer_train_grad_meta);
+  m.impl("mlp_layer_train_pool", &mlp_layer_train_pool_meta);
+  m.impl("mlp_layer_train_pool_grad", &mlp_layer_train_pool_grad_meta);
 }

@@ -480,6 +480,16 @@ def _mlp_autograd(store, x, layers, is_training, bn_decay):
     return tf_util.mlp_torch(x, layers, is_training, bn_decay)
 
 
+def _mlp_pool_autograd(store, x, layers, is_training, bn_decay, pooling, grouped_xyz):
+    """_mlp_autograd followed by the pooling over nsample. Max pooling while training on a
+    trainable store runs fused with the last layer (tf_util.mlp_train, pool="max"): the same
+    bits, without the (B, npoint, nsample, C) activation or its gradient."""
+    if pooling == "max" and is_training and store.is_trainable and layers:
+        return tf_util.mlp_train(x, layers, bn_decay, pool="max")
+    return _pool_torch(_mlp_autograd(store, x, layers, is_training, bn_decay), pooling,
+                       grouped_xyz)
+
+
 def pointnet_sa_module(xyz, points, npoint, radius, nsample, mlp, mlp2, group_all, is_training,
                        bn_decay, scope, bn=True, pooling='max', knn=False, use_xyz=True,
                        use_nchw=False, params=None):
@@ -491,7 +501,8 @@ def pointnet_sa_module(xyz, points, npoint, radius, nsample, mlp, mlp2, group_al
     MLP and pooling (pn2_group_mlp), and mlp2 as a per-point MLP. Training: the same ops
     composed from differentiable torch ops (batch-statistics batch norm); on a trainable store
     (tf_util.ParamStore.trainable()) the MLPs are the HIP training layers (tf_util.mlp_train),
-    which also give every variable its gradient."""
+    which also give every variable its gradient, and max pooling runs fused with the last
+    layer."""
     store = params if params is not None else tf_util.default_store()
     xyz = device_tensor(xyz, "xyz", torch.float32)
     scopes = [f"{scope}/conv{i}" for i in range(len(mlp))]
@@ -509,8 +520,8 @@ def pointnet_sa_module(xyz, points, npoint, radius, nsample, mlp, mlp2, group_al
         3 if (use_xyz or _is_empty_points(points)) else 0)
     if is_training or _needs_grad(xyz, points):
         layers = tf_util.torch_layers(store, scopes, cin, mlp, bn=bn)
-        x = _mlp_autograd(store, new_points, layers, is_training, bn_decay)
-        x = _pool_torch(x, pooling, grouped_xyz)
+        x = _mlp_pool_autograd(store, new_points, layers, is_training, bn_decay, pooling,
+                               grouped_xyz)
         if mlp2:
             c = int(x.shape[-1])
             x = _mlp_autograd(store, x, tf_util.torch_layers(store, post, c, mlp2, bn=bn),
@@ -547,8 +558,8 @@ def pointnet_sa_module_msg(xyz, points, npoint, radius_list, nsample_list, mlp_l
         if training:
             gp, _ = group_concat(xyz, points, new_xyz, idx, use_xyz=use_xyz, xyz_last=True)
             layers = tf_util.torch_layers(store, scopes, cin, mlp_list[i], bn=bn)
-            outs.append(_mlp_autograd(store, gp, layers, is_training,
-                                      bn_decay).max(dim=2).values)
+            outs.append(_mlp_pool_autograd(store, gp, layers, is_training, bn_decay, "max",
+                                           None))
         else:
             fused = tf_util.packed_mlp(store, scopes, cin, mlp_list[i], bn=bn)
             outs.append(group_mlp(xyz, points, new_xyz, idx, fused, "max", use_xyz=use_xyz,

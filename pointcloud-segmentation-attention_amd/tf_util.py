@@ -342,21 +342,31 @@ def mlp_torch(x, layers, is_training=False, bn_decay=None):
     return x
 
 
-def mlp_train(x, layers, bn_decay=None):
+def mlp_train(x, layers, bn_decay=None, pool=None):
     """The layers of mlp_torch(x, layers, is_training=True) on the HIP training kernels
     (torch.ops.pn2.mlp_layer_train: conv + bias + batch-statistics batch norm + ReLU, with
     autograd for x and every variable), for the variables of a trainable ParamStore. The moving
     averages are updated in place on the device by mlp_torch's rule: decay bn_decay (0.9 when
-    None) with the biased batch variance."""
+    None) with the biased batch variance.
+
+    pool="max": x is (..., ns, cin) and the last layer runs fused with the max over the ns
+    axis (torch.ops.pn2.mlp_layer_train_pool): the result, (..., cout), has the bits of
+    mlp_train(x, layers).max(dim=-2).values, and neither the last activation nor its gradient is
+    materialised."""
+    if pool not in (None, "max"):
+        raise InvalidArgumentError(f"mlp_train fuses max pooling only, got pool={pool!r}")
+    if pool and not layers:
+        raise InvalidArgumentError("mlp_train: pool needs at least one layer")
     decay = 0.9 if bn_decay is None else float(bn_decay)
     x = device_tensor(x, "inputs", torch.float32)
-    for L in layers:
+    for i, L in enumerate(layers):
         p = L.params
         bn = p.get("gamma") is not None
         rows = x.numel()
+        op = "mlp_layer_train_pool" if pool and i == len(layers) - 1 else "mlp_layer_train"
         x, _, mean, var = _torch_ops.call(
-            "mlp_layer_train", x, p["weights"], p.get("biases"), p.get("gamma") if bn else None,
-            p.get("beta") if bn else None, BN_EPSILON, bool(L.relu))
+            op, x, p["weights"], p.get("biases"), p.get("gamma") if bn else None,
+            p.get("beta") if bn else None, BN_EPSILON, bool(L.relu))[:4]
         if bn and rows > 0:  # no rows: no batch statistics, the moving averages stay
             with torch.no_grad():
                 p["moving_mean"].mul_(decay).add_((1 - decay) * mean)
