@@ -42,6 +42,10 @@
  *                        statistics) and its gradients             pn2_bn_act_bwd, pn2_mlp_wgrad
  *   conv2d, is_training, pointnet_util.py:106-136 (the last MLP  → pn2_bn_act_pool_fwd,
  *     + max pool         layer and reduce_max over nsample)        pn2_bn_act_pool_bwd
+ *   AttentionLayer,      attention_layer.py:10-45, :256-259, :303 → pn2_attn_kv_reduce,
+ *     is_training        (K and V projected together, and the     pn2_attn_kv_reduce_grad,
+ *                        gradients)                                pn2_attn_dx_scatter,
+ *                                                                  pn2_col_sum
  *   get_subset          scannet_dataset/data_transformation.py  → pn2_scene_bbox,
  *                        :70-154 (training crop sampler)           pn2_crop_sample
  *   whole-scene chunker  scannet_dataset/complete_scene_loader.py → pn2_subvolume_select,
@@ -542,6 +546,40 @@ int pn2_bn_act_pool_bwd(const float* grad_out, const int* arg, const float* y, l
 size_t pn2_mlp_wgrad_workspace_size(long long rows, int cin, int cout);
 int pn2_mlp_wgrad(const float* x, const float* grad_y, long long rows, int cin, int cout,
                   float* grad_w, void* workspace, size_t workspace_bytes, pn2_stream_t stream);
+
+/* ---------------------------------------------------------------- attention, training --- */
+/* The AttentionLayer of the attention SA modules (attention_layer.py:10-45, :256-259) with
+ * is_training=True: K and V are projected together, KV = X [Wk | Wv] + [bk | bv] (one
+ * pn2_shared_mlp over a pn2_mlp_pack of the (C, 2C) matrix), so KV (G,ns,2C) holds in row j of
+ * group g the K row followed by the V row, and X is read once. */
+
+/* pn2_attn_reduce on that layout: Q (G,C), KV (G,ns,2C) -> out (G,C). Pseudo-key i of head h is
+ * the 4 floats at flat index f = 4*ns*h + 4*i of the group's row-major (ns,C) K matrix (the
+ * tf.reshape reinterpretation), i.e. KV[g][f / C][f % C .. +3]; its value vector is
+ * KV[g][f / C][C + f % C .. +3]. The result has the bits of pn2_attn_reduce on de-interleaved
+ * copies. 16-byte aligned buffers, C % 4 == 0, ns > 0, ns * C < 2^30; G = 0 is a no-op. */
+int pn2_attn_kv_reduce(const float* Q, const float* KV, long long G, int ns, int C, float* out,
+                       pn2_stream_t stream);
+/* Its backward (the formulas of pn2_attn_reduce_grad): grad_Q (G,C) and grad_KV (G,ns,2C), in
+ * KV's layout, from grad_out (G,C). Every element written, no accumulation; K and V are read
+ * once, and every reduction has a fixed order (two runs give equal bits; they are not the
+ * bits of pn2_attn_reduce_grad, whose reduction order differs). */
+int pn2_attn_kv_reduce_grad(const float* Q, const float* KV, const float* grad_out, long long G,
+                            int ns, int C, float* grad_Q, float* grad_KV, pn2_stream_t stream);
+/* In place on grad_x (G,ns,C): grad_x[g][0][c] += grad_xq[g][c] (the query is the group's
+ * first row, attention_layer.py:259); then, where grad_pmax is given and 0 <= arg[g][c] < ns,
+ * grad_x[g][arg[g][c]][c] += grad_pmax[g][c] (the max pool of the _and_pooling module, :303).
+ * One thread per (g, c) does both adds in that order: no atomics, deterministic. An arg
+ * outside [0, ns) selects nothing and is never dereferenced. grad_pmax and arg (int32, (G,C))
+ * are NULL together. */
+int pn2_attn_dx_scatter(float* grad_x, const float* grad_xq, const float* grad_pmax,
+                        const int* arg, long long G, int ns, int C, pn2_stream_t stream);
+/* out[c] = sum over the rows of x (rows,C): the bias gradients. Two-stage like pn2_bn_act_bwd's
+ * sums: fp32 partials over PN2_BN_BLOCK_ROWS rows, then double precision in a fixed order.
+ * workspace: pn2_col_sum_workspace_size(rows, C) bytes. */
+size_t pn2_col_sum_workspace_size(long long rows, int C);
+int pn2_col_sum(const float* x, long long rows, int C, float* out, void* workspace,
+                size_t workspace_bytes, pn2_stream_t stream);
 
 /* ---------------------------------------------------------------- scene crops ---------- */
 

@@ -1,7 +1,8 @@
 """torch.ops.pn2.* under the reference's op names and argument order.
 
 Each name is the registered PyTorch operator itself (csrc/torch_ops.cpp: HIP + Meta kernels,
-autograd for gather_point / group_point / three_interpolate / attn_reduce), so calls are
+autograd for gather_point / group_point / three_interpolate / attn_reduce and the training
+layers mlp_layer_train, mlp_layer_train_pool, attn_kv_train, bn_train), so calls are
 visible to torch.compile and TorchScript:
 
     farthest_point_sample(npoint, inp)                tf_sampling.py:49-57
@@ -27,6 +28,20 @@ idw_weights, fp_fused, group_pool, *_grad), and the training-mode shared-MLP lay
     mlp_layer_train_pool_grad(grad_out, arg, x, weight, y, mean, var, gamma, beta, eps, relu,
                               need_grad_x)
                                        -> (grad_x, grad_w, grad_b, grad_gamma, grad_beta)
+
+and the training-mode AttentionLayer of the attention SA modules (csrc/attn_train.hip):
+
+    attn_kv_train(x, wq, bq, wk, bk, wv, bv, add_max)   attention_layer.py:10-45, :256-259: x
+                         (..., ns, C); q = x[..., 0, :] wq + bq; kv = x [wk | wv] + [bk | bv]
+                         (..., ns, 2C), one GEMM; att = the reduction (..., C); add_max: pmax, arg
+                         = the max over ns of x and the lowest sample that attains it (:303), else
+                         0-element tensors               -> (att, pmax, arg, q, kv)
+    attn_kv_train_grad(grad_att, grad_pmax, arg, x, wq, wk, wv, q, kv, need_grad_x)
+               -> (grad_x, grad_wq, grad_bq, grad_wk, grad_bk, grad_wv, grad_bv)
+    bn_train(x, gamma, beta, eps, relu)                 batch-statistics batch norm of x (..., C)
+                         (tf_util.py:512-531; :261)      -> (out, mean, var)
+    bn_train_grad(grad_out, x, mean, var, gamma, beta, eps, relu)
+                                                         -> (grad_x, grad_gamma, grad_beta)
 """
 import importlib
 
@@ -37,7 +52,8 @@ NAMES = ("farthest_point_sample", "farthest_point_sample_and_gather", "gather_po
          "group_point", "group_point_grad", "group_concat", "three_nn", "three_interpolate",
          "three_interpolate_grad", "idw_weights", "fp_fused", "attn_reduce", "attn_reduce_grad",
          "group_pool", "mlp_layer_train", "mlp_layer_train_grad", "mlp_layer_train_pool",
-         "mlp_layer_train_pool_grad")
+         "mlp_layer_train_pool_grad", "attn_kv_train", "attn_kv_train_grad", "bn_train",
+         "bn_train_grad")
 for _n in NAMES:
     globals()[_n] = getattr(_ops, _n)
 

@@ -149,6 +149,11 @@ SIGNATURES = {
                                  _S, _P]),
     "pn2_mlp_wgrad_workspace_size": (_S, [_LL, _I, _I]),
     "pn2_mlp_wgrad": (_I, [_P, _P, _LL, _I, _I, _P, _P, _S, _P]),
+    "pn2_attn_kv_reduce": (_I, [_P, _P, _LL, _I, _I, _P, _P]),
+    "pn2_attn_kv_reduce_grad": (_I, [_P, _P, _P, _LL, _I, _I, _P, _P, _P]),
+    "pn2_attn_dx_scatter": (_I, [_P, _P, _P, _P, _LL, _I, _I, _P]),
+    "pn2_col_sum_workspace_size": (_S, [_LL, _I]),
+    "pn2_col_sum": (_I, [_P, _LL, _I, _P, _P, _S, _P]),
     "pn2_scene_workspace_size": (_S, [_I]),
     "pn2_scene_bbox": (_I, [_P, _I, _P, _P, _S, _P]),
     "pn2_crop_workspace_size": (_S, [_I, _I, _I]),

@@ -6,7 +6,9 @@ reference registers gradients for, w.r.t. the points only (tf_sampling.py:44-48 
 tf_grouping.py:42-46 GroupPoint, tf_interpolate.py:29-34 ThreeInterpolate), plus the attention
 reduction (TF autodiff through attention_layer.py:35-42, all of Q, K, V) and the training-mode
 shared-MLP layer (mlp_layer_train, and mlp_layer_train_pool for the layer fused with the max
-pool over nsample: x, weight, bias, gamma, beta; csrc/mlp_train.hip).
+pool over nsample: x, weight, bias, gamma, beta; csrc/mlp_train.hip), the training-mode attention
+layer (attn_kv_train: x and the three Dense layers' variables; csrc/attn_train.hip) and the
+stand-alone batch-statistics batch norm (bn_train: x, gamma, beta).
 
 The mirror modules (tf_sampling, tf_grouping, tf_interpolate, attention_layer) call these ops
 for every reference-signature call; the pn2hip alias package re-exports them as pn2hip.ops.
@@ -105,6 +107,37 @@ def _register_autograd():
         return (gx if ctx.needs_input_grad[0] else None, gw, gb if ctx.has_bias else None,
                 gg if bn else None, gbeta if bn else None, None, None)
 
+    def attn_kv_setup(ctx, inputs, output):
+        x, wq, bq, wk, bk, wv, bv, add_max = inputs
+        att, pmax, arg, q, kv = output
+        ctx.mark_non_differentiable(arg, q, kv)
+        ctx.save_for_backward(x, wq, wk, wv, q, kv, arg)
+        ctx.add_max = add_max
+
+    def attn_kv_bwd(ctx, grad_att, grad_pmax, *_):
+        # grad_x is written once by the (2C -> C) GEMM and patched at 2 G C elements: the query
+        # row's and the max pool's gradients never exist as (..., ns, C) tensors
+        x, wq, wk, wv, q, kv, arg = ctx.saved_tensors
+        grads = torch.ops.pn2.attn_kv_train_grad(
+            grad_att.contiguous(), grad_pmax.contiguous() if ctx.add_max else None, arg, x, wq,
+            wk, wv, q, kv, ctx.needs_input_grad[0])
+        return (grads[0] if ctx.needs_input_grad[0] else None,) + tuple(grads[1:]) + (None,)
+
+    def bn_setup(ctx, inputs, output):
+        x, gamma, beta, eps, relu = inputs
+        out, mean, var = output
+        ctx.mark_non_differentiable(mean, var)
+        ctx.save_for_backward(x, mean, var, gamma, beta)
+        ctx.eps, ctx.relu = eps, relu
+
+    def bn_bwd(ctx, grad_out, *_):
+        x, mean, var, gamma, beta = ctx.saved_tensors
+        gx, gg, gbeta = torch.ops.pn2.bn_train_grad(grad_out.contiguous(), x, mean, var, gamma,
+                                                    beta, ctx.eps, ctx.relu)
+        return gx, gg, gbeta, None, None
+
+    reg("pn2::attn_kv_train", attn_kv_bwd, setup_context=attn_kv_setup)
+    reg("pn2::bn_train", bn_bwd, setup_context=bn_setup)
     reg("pn2::mlp_layer_train", mlp_layer_bwd, setup_context=mlp_layer_setup)
     reg("pn2::mlp_layer_train_pool", mlp_pool_bwd, setup_context=mlp_pool_setup)
     reg("pn2::gather_point", gather_bwd, setup_context=save_all)

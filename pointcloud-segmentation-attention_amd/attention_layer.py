@@ -117,7 +117,12 @@ def pointnet_sa_module_attention(xyz, points, npoint, radius, nsample, mlp, mlp2
     Returns (new_xyz, new_points (B, npoint, mlp[-1] or mlp2[-1]), idx). Variables:
     '<scope>/conv<i>/...' (the MLP), '<scope>/ScannetAttentionLayer/dense{,_1,_2}/{kernel,bias}'
     (query, key, value), '<scope>/<scope>/{gamma,beta,moving_mean,moving_variance}' (the batch
-    norm after the attention, :261), '<scope>/conv_post_<i>/...' (mlp2)."""
+    norm after the attention, :261), '<scope>/conv_post_<i>/...' (mlp2).
+
+    is_training=True on a trainable store (ParamStore.trainable()) runs the HIP training layers:
+    tf_util.mlp_train for the MLP and mlp2, attention_train for the AttentionLayer, its batch
+    norm and the pool, with gradients for every variable. On a plain store is_training=True (or
+    inputs that require a gradient) runs the differentiable torch composition."""
     store = params if params is not None else tf_util.default_store()
     pu = pointnet_util
     xyz = device_tensor(xyz, "xyz", torch.float32)
@@ -137,7 +142,13 @@ def pointnet_sa_module_attention(xyz, points, npoint, radius, nsample, mlp, mlp2
     else:
         _, new_xyz = tf_sampling.farthest_point_sample_and_gather(npoint, xyz)
         idx, _ = tf_grouping.query_ball_point(radius, nsample, xyz, new_xyz)
-    if training:
+    # is_training on a trainable store: the HIP training layers, gradients for every variable
+    hip_train = bool(is_training) and store.is_trainable
+    if hip_train:
+        X = tf_util.mlp_train(grouped, tf_util.torch_layers(store, scopes, cin, mlp, bn=bn),
+                              bn_decay)
+        out = attention_train(X, store, scope, C, bn_decay, and_pooling)
+    elif training:
         X = tf_util.mlp_torch(grouped, tf_util.torch_layers(store, scopes, cin, mlp, bn=bn),
                               is_training, bn_decay)
         dense = lambda sc, x: x @ store.dense(sc, C, C)["weights"].to(x.device) + \
@@ -155,12 +166,29 @@ def pointnet_sa_module_attention(xyz, points, npoint, radius, nsample, mlp, mlp2
                                   use_xyz=use_xyz)
     if mlp2:
         post = [f"{scope}/conv_post_{i}" for i in range(len(mlp2))]
-        if training:
+        if hip_train:
+            out = tf_util.mlp_train(out, tf_util.torch_layers(store, post, C, mlp2, bn=bn),
+                                    bn_decay)
+        elif training:
             out = tf_util.mlp_torch(out, tf_util.torch_layers(store, post, C, mlp2, bn=bn),
                                     is_training, bn_decay)
         else:
             out = tf_util.packed_mlp(store, post, C, mlp2, bn=bn)(out)
     return new_xyz, out, idx
+
+
+def attention_train(X, store, scope, C, bn_decay=None, and_pooling=False):
+    """Training tail of the attention SA layers on the per-point MLP output X (B,M,ns,C), for a
+    trainable store: torch.ops.pn2.attn_kv_train (the Dense query of each group's first
+    neighbour, :259; key and value projected together in one GEMM; the reduction; with
+    and_pooling the max over ns, :303), then the batch-statistics batch norm '<scope>/<scope>'
+    (:261, tf_util.bn_train) and + the max. Autograd reaches X and all eight variables."""
+    q, k, v = (store.dense(s, C, C) for s in _attention_scopes(scope))
+    att, pmax = call("attn_kv_train", device_tensor(X, "X", torch.float32), q["weights"],
+                     q["biases"], k["weights"], k["biases"], v["weights"], v["biases"],
+                     bool(and_pooling))[:2]
+    out = tf_util.bn_train(att, store.bn(f"{scope}/{scope}", C), bn_decay)
+    return out + pmax if and_pooling else out
 
 
 def group_mlp_attention(xyz, points, new_xyz, idx, mlp, store, scope, and_pooling=False,

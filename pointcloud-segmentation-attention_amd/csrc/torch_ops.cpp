@@ -12,7 +12,9 @@
 // the points only, tf_sampling.py:44-48, tf_grouping.py:42-46, tf_interpolate.py:29-34) and
 // attn_reduce is registered from Python (torch.library.register_autograd, _torch_ops.py), and
 // so is the training-mode shared-MLP layer's (mlp_layer_train -> mlp_layer_train_grad, and
-// mlp_layer_train_pool -> mlp_layer_train_pool_grad for the layer fused with the max pool).
+// mlp_layer_train_pool -> mlp_layer_train_pool_grad for the layer fused with the max pool), the
+// training-mode attention layer's (attn_kv_train -> attn_kv_train_grad) and the stand-alone
+// batch-statistics batch norm's (bn_train -> bn_train_grad).
 // CPU kernels exist only for the three ops the reference itself runs on the CPU (ThreeNN,
 // ThreeInterpolate, ThreeInterpolateGrad: registered for DEVICE_CPU only,
 // tf_interpolate.cpp:187,222,262), through the host twins pn2cpu_* (csrc/cpu_interp.cpp);
@@ -702,6 +704,199 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_pool_grad_hip
   return {grad_x, grad_w, grad_b, grad_gamma, grad_beta};
 }
 
+// ---- training-mode AttentionLayer of the attention SA modules (csrc/attn_train.hip;
+// attention_layer.py:10-45 as instantiated at :256-259): the Dense query of each group's first
+// row, K and V projected together into one (..., ns, 2C) tensor, the reduction on that layout
+// and, with add_max, the max over ns of x with its arg (the _and_pooling module, :303)
+void chk_attn_kv(const Tensor& x, const Tensor& wq, const Tensor& wk, const Tensor& wv,
+                 const char* op) {
+  TORCH_CHECK_VALUE(x.dim() >= 2 && x.size(-2) > 0 && x.size(-1) > 0 && x.size(-1) % 4 == 0, op,
+                    " expects (..., ns, C) x with ns > 0 and C % 4 == 0 (key_dim 4)");
+  const int64_t C = x.size(-1);
+  for (const Tensor* w : {&wq, &wk, &wv})
+    TORCH_CHECK_VALUE(w->dim() == 2 && w->size(0) == C && w->size(1) == C, op,
+                      " expects (C, C) wq, wk and wv for (..., ns, C) x");
+}
+void chk_attn_kv_bias(const Tensor& x, const Tensor& bq, const Tensor& bk, const Tensor& bv,
+                      const char* op) {
+  for (const Tensor* b : {&bq, &bk, &bv})
+    TORCH_CHECK_VALUE(b->dim() == 1 && b->size(0) == x.size(-1), op,
+                      " expects (C) bq, bk and bv for (..., ns, C) x");
+}
+void chk_attn_kv_grad(const Tensor& grad_att, const std::optional<Tensor>& grad_pmax,
+                      const Tensor& arg, const Tensor& x, const Tensor& wq, const Tensor& wk,
+                      const Tensor& wv, const Tensor& q, const Tensor& kv, const char* op) {
+  chk_attn_kv(x, wq, wk, wv, op);
+  const int64_t C = x.size(-1);
+  const std::vector<int64_t> pooled = pooled_sizes(x, C);
+  TORCH_CHECK_VALUE(grad_att.sizes() == c10::IntArrayRef(pooled) && q.sizes() == grad_att.sizes(),
+                    op, " expects (..., C) grad_att and q for (..., ns, C) x");
+  TORCH_CHECK_VALUE(kv.sizes() == c10::IntArrayRef(with_last(x, 2 * C)), op,
+                    " expects (..., ns, 2C) kv for (..., ns, C) x");
+  if (has(grad_pmax))
+    TORCH_CHECK_VALUE(grad_pmax->sizes() == c10::IntArrayRef(pooled) &&
+                          arg.sizes() == grad_pmax->sizes(),
+                      op, " expects (..., C) grad_pmax and arg for (..., ns, C) x");
+}
+
+void col_sum(const Tensor& x, int64_t rows, int C, Tensor& out, const char* op) {
+  const size_t ws = pn2_col_sum_workspace_size(rows, C);
+  Tensor w = workspace(x, ws);
+  check_rc(pn2_col_sum(F(x), rows, C, out.data_ptr<float>(), P(w), ws, stream_of(x)), op);
+}
+void wgrad(const Tensor& x, const Tensor& grad_y, int64_t rows, int cin, int cout, Tensor& grad_w,
+           const char* op) {
+  const size_t ws = pn2_mlp_wgrad_workspace_size(rows, cin, cout);
+  Tensor w = workspace(x, ws);
+  check_rc(pn2_mlp_wgrad(F(x), F(grad_y), rows, cin, cout, grad_w.data_ptr<float>(), P(w), ws,
+                         stream_of(x)), op);
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> attn_kv_train_hip(
+    const Tensor& x_, const Tensor& wq_, const Tensor& bq_, const Tensor& wk_, const Tensor& bk_,
+    const Tensor& wv_, const Tensor& bv_, bool add_max) {
+  const char* op = "attn_kv_train";
+  chk_attn_kv(x_, wq_, wk_, wv_, op);
+  chk_attn_kv_bias(x_, bq_, bk_, bv_, op);
+  Tensor x = dev(x_, "x", at::kFloat);
+  Tensor wq = dev(wq_, "wq", at::kFloat), bq = dev(bq_, "bq", at::kFloat);
+  Tensor wk = dev(wk_, "wk", at::kFloat), bk = dev(bk_, "bk", at::kFloat);
+  Tensor wv = dev(wv_, "wv", at::kFloat), bv = dev(bv_, "bv", at::kFloat);
+  c10::hip::HIPGuard g(x.device().index());
+  const int C = I(x.size(-1)), ns = I(x.size(-2));
+  const int64_t rows = x.numel() / C, G = rows / ns;
+  const std::vector<int64_t> pooled = pooled_sizes(x, C);
+  Tensor att = at::empty(pooled, f32(x)), q = at::empty(pooled, f32(x));
+  Tensor kv = at::empty(with_last(x, 2 * C), f32(x));
+  Tensor pmax = add_max ? at::empty(pooled, f32(x)) : at::empty({0}, f32(x));
+  Tensor arg = add_max ? at::empty(pooled, i32(x)) : at::empty({0}, i32(x));
+  if (G == 0) return {att, pmax, arg, q, kv};
+  // the query is the group's first row (attention_layer.py:259): G rows
+  linear_rows(x.select(-2, 0).contiguous(), wq, bq, G, q, op);
+  // [K | V] = x [wk | wv] + [bk | bv]: one GEMM, x read once
+  linear_rows(x, at::cat({wk, wv}, 1), at::cat({bk, bv}, 0), rows, kv, op);
+  check_rc(pn2_attn_kv_reduce(F(q), F(kv), G, ns, C, att.data_ptr<float>(), stream_of(x)), op);
+  if (add_max)  // no batch norm, no ReLU: the plain max over ns, arg = the lowest j
+    check_rc(pn2_bn_act_pool_fwd(F(x), G, ns, C, nullptr, nullptr, nullptr, nullptr, 0.f, 0,
+                                 pmax.data_ptr<float>(), arg.data_ptr<int32_t>(), stream_of(x)),
+             op);
+  return {att, pmax, arg, q, kv};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> attn_kv_train_grad_hip(
+    const Tensor& grad_att_, const std::optional<Tensor>& grad_pmax_, const Tensor& arg_,
+    const Tensor& x_, const Tensor& wq_, const Tensor& wk_, const Tensor& wv_, const Tensor& q_,
+    const Tensor& kv_, bool need_grad_x) {
+  const char* op = "attn_kv_train_grad";
+  chk_attn_kv_grad(grad_att_, grad_pmax_, arg_, x_, wq_, wk_, wv_, q_, kv_, op);
+  Tensor go = dev(grad_att_, "grad_att", at::kFloat), x = dev(x_, "x", at::kFloat);
+  Tensor wq = dev(wq_, "wq", at::kFloat), wk = dev(wk_, "wk", at::kFloat);
+  Tensor wv = dev(wv_, "wv", at::kFloat), q = dev(q_, "q", at::kFloat);
+  Tensor kv = dev(kv_, "kv", at::kFloat);
+  Tensor gp, arg;
+  if (has(grad_pmax_)) {
+    gp = dev(*grad_pmax_, "grad_pmax", at::kFloat);
+    arg = dev(arg_, "arg", at::kInt);
+  }
+  c10::hip::HIPGuard g(x.device().index());
+  const int C = I(x.size(-1)), ns = I(x.size(-2));
+  const int64_t rows = x.numel() / C, G = rows / ns;
+  Tensor grad_x = need_grad_x ? at::empty(x.sizes(), f32(x)) : at::empty({0}, f32(x));
+  Tensor grad_wq = at::empty({C, C}, f32(x)), grad_bq = at::empty({C}, f32(x));
+  if (G == 0) {
+    grad_wq.zero_();
+    grad_bq.zero_();
+    return {grad_x, grad_wq, grad_bq, at::zeros({C, C}, f32(x)), at::zeros({C}, f32(x)),
+            at::zeros({C, C}, f32(x)), at::zeros({C}, f32(x))};
+  }
+  Tensor grad_q = at::empty(q.sizes(), f32(x)), grad_kv = at::empty(kv.sizes(), f32(x));
+  check_rc(pn2_attn_kv_reduce_grad(F(q), F(kv), F(go), G, ns, C, grad_q.data_ptr<float>(),
+                                   grad_kv.data_ptr<float>(), stream_of(x)), op);
+  // [grad_wk | grad_wv] = x^T grad_kv: one weight-gradient GEMM; grad_wq over the G query rows
+  Tensor grad_wkv = at::empty({C, 2 * C}, f32(x)), grad_bkv = at::empty({2 * C}, f32(x));
+  wgrad(x, grad_kv, rows, C, 2 * C, grad_wkv, op);
+  wgrad(x.select(-2, 0).contiguous(), grad_q, G, C, C, grad_wq, op);
+  col_sum(grad_kv, rows, 2 * C, grad_bkv, op);
+  col_sum(grad_q, G, C, grad_bq, op);
+  if (need_grad_x) {
+    // grad_x = grad_kv [wk | wv]^T, written once, then patched at 2 G C elements
+    linear_rows(grad_kv, at::cat({wk, wv}, 1).t().contiguous(), Tensor(), rows, grad_x, op);
+    Tensor grad_xq = at::empty(q.sizes(), f32(x));
+    linear_rows(grad_q, wq.t().contiguous(), Tensor(), G, grad_xq, op);
+    check_rc(pn2_attn_dx_scatter(grad_x.data_ptr<float>(), F(grad_xq), F(gp),
+                                 gp.defined() ? Ii(arg) : nullptr, G, ns, C, stream_of(x)), op);
+  }
+  return {grad_x, grad_wq, grad_bq,
+          grad_wkv.slice(1, 0, C).contiguous(), grad_bkv.slice(0, 0, C).clone(),
+          grad_wkv.slice(1, C, 2 * C).contiguous(), grad_bkv.slice(0, C, 2 * C).clone()};
+}
+
+// ---- batch-statistics batch norm on its own (the batch norm after the attention,
+// attention_layer.py:261): pn2_bn_stats + pn2_bn_act_fwd, pn2_bn_act_bwd on x (..., C)
+void chk_bn(const Tensor& x, const Tensor& gamma, const Tensor& beta, const char* op) {
+  TORCH_CHECK_VALUE(x.dim() >= 1 && x.size(-1) > 0, op, " expects (..., C) x");
+  TORCH_CHECK_VALUE(gamma.dim() == 1 && gamma.size(0) == x.size(-1) && beta.dim() == 1 &&
+                        beta.size(0) == x.size(-1),
+                    op, " expects (C) gamma and beta for (..., C) x");
+}
+
+std::tuple<Tensor, Tensor, Tensor> bn_train_hip(const Tensor& x_, const Tensor& gamma_,
+                                                const Tensor& beta_, double eps, bool relu) {
+  const char* op = "bn_train";
+  chk_bn(x_, gamma_, beta_, op);
+  Tensor x = dev(x_, "x", at::kFloat), gamma = dev(gamma_, "gamma", at::kFloat);
+  Tensor beta = dev(beta_, "beta", at::kFloat);
+  c10::hip::HIPGuard g(x.device().index());
+  const int C = I(x.size(-1));
+  const int64_t rows = x.numel() / C;
+  Tensor out = at::empty(x.sizes(), f32(x));
+  Tensor mean = at::empty({C}, f32(x)), var = at::empty({C}, f32(x));
+  if (rows == 0) {
+    mean.zero_();
+    var.zero_();
+    return {out, mean, var};
+  }
+  const size_t ws = pn2_bn_workspace_size(rows, C);
+  Tensor w = workspace(x, ws);
+  check_rc(pn2_bn_stats(F(x), rows, C, mean.data_ptr<float>(), var.data_ptr<float>(), P(w), ws,
+                        stream_of(x)), op);
+  check_rc(pn2_bn_act_fwd(F(x), rows, C, F(mean), F(var), F(gamma), F(beta),
+                          static_cast<float>(eps), relu ? 1 : 0, out.data_ptr<float>(),
+                          stream_of(x)), op);
+  return {out, mean, var};
+}
+
+std::tuple<Tensor, Tensor, Tensor> bn_train_grad_hip(const Tensor& grad_out_, const Tensor& x_,
+                                                     const Tensor& mean_, const Tensor& var_,
+                                                     const Tensor& gamma_, const Tensor& beta_,
+                                                     double eps, bool relu) {
+  const char* op = "bn_train_grad";
+  chk_bn(x_, gamma_, beta_, op);
+  TORCH_CHECK_VALUE(grad_out_.sizes() == x_.sizes(), op, " expects grad_out shaped like x");
+  TORCH_CHECK_VALUE(mean_.sizes() == gamma_.sizes() && var_.sizes() == gamma_.sizes(), op,
+                    " expects (C) mean and var");
+  Tensor go = dev(grad_out_, "grad_out", at::kFloat), x = dev(x_, "x", at::kFloat);
+  Tensor mean = dev(mean_, "mean", at::kFloat), var = dev(var_, "var", at::kFloat);
+  Tensor gamma = dev(gamma_, "gamma", at::kFloat), beta = dev(beta_, "beta", at::kFloat);
+  c10::hip::HIPGuard g(x.device().index());
+  const int C = I(x.size(-1));
+  const int64_t rows = x.numel() / C;
+  Tensor grad_x = at::empty(x.sizes(), f32(x));
+  Tensor grad_gamma = at::empty({C}, f32(x)), grad_beta = at::empty({C}, f32(x));
+  if (rows == 0) {
+    grad_gamma.zero_();
+    grad_beta.zero_();
+    return {grad_x, grad_gamma, grad_beta};
+  }
+  const size_t ws = pn2_bn_workspace_size(rows, C);
+  Tensor w = workspace(x, ws);
+  check_rc(pn2_bn_act_bwd(F(go), F(x), rows, C, F(mean), F(var), F(gamma), F(beta),
+                          static_cast<float>(eps), relu ? 1 : 0, grad_x.data_ptr<float>(),
+                          grad_gamma.data_ptr<float>(), grad_beta.data_ptr<float>(), P(w), ws,
+                          stream_of(x)), op);
+  return {grad_x, grad_gamma, grad_beta};
+}
+
 // ------------------------------------------------------------------------- CPU kernels
 // (the reference's CPU-only ops; host twins in csrc/cpu_interp.cpp)
 Tensor host(const Tensor& t, const char* name, at::ScalarType dt) {
@@ -880,6 +1075,46 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_pool_grad_met
           at::empty({nstat}, mf(x))};
 }
 
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> attn_kv_train_meta(
+    const Tensor& x, const Tensor& wq, const Tensor& bq, const Tensor& wk, const Tensor& bk,
+    const Tensor& wv, const Tensor& bv, bool add_max) {
+  chk_attn_kv(x, wq, wk, wv, "attn_kv_train");
+  chk_attn_kv_bias(x, bq, bk, bv, "attn_kv_train");
+  const int64_t C = x.size(-1);
+  const std::vector<int64_t> pooled = pooled_sizes(x, C);
+  return {at::empty(pooled, mf(x)),
+          add_max ? at::empty(pooled, mf(x)) : at::empty({0}, mf(x)),
+          add_max ? at::empty(pooled, mi(x)) : at::empty({0}, mi(x)),
+          at::empty(pooled, mf(x)), at::empty(with_last(x, 2 * C), mf(x))};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> attn_kv_train_grad_meta(
+    const Tensor& grad_att, const std::optional<Tensor>& grad_pmax, const Tensor& arg,
+    const Tensor& x, const Tensor& wq, const Tensor& wk, const Tensor& wv, const Tensor& q,
+    const Tensor& kv, bool need_grad_x) {
+  chk_attn_kv_grad(grad_att, grad_pmax, arg, x, wq, wk, wv, q, kv, "attn_kv_train_grad");
+  const int64_t C = x.size(-1);
+  return {need_grad_x ? at::empty(x.sizes(), mf(x)) : at::empty({0}, mf(x)),
+          at::empty({C, C}, mf(x)), at::empty({C}, mf(x)), at::empty({C, C}, mf(x)),
+          at::empty({C}, mf(x)), at::empty({C, C}, mf(x)), at::empty({C}, mf(x))};
+}
+std::tuple<Tensor, Tensor, Tensor> bn_train_meta(const Tensor& x, const Tensor& gamma,
+                                                 const Tensor& beta, double, bool) {
+  chk_bn(x, gamma, beta, "bn_train");
+  const int64_t C = x.size(-1);
+  return {at::empty(x.sizes(), mf(x)), at::empty({C}, mf(x)), at::empty({C}, mf(x))};
+}
+std::tuple<Tensor, Tensor, Tensor> bn_train_grad_meta(const Tensor& grad_out, const Tensor& x,
+                                                      const Tensor& mean, const Tensor& var,
+                                                      const Tensor& gamma, const Tensor& beta,
+                                                      double, bool) {
+  chk_bn(x, gamma, beta, "bn_train_grad");
+  TORCH_CHECK_VALUE(grad_out.sizes() == x.sizes(), "bn_train_grad expects grad_out shaped like x");
+  TORCH_CHECK_VALUE(mean.sizes() == gamma.sizes() && var.sizes() == gamma.sizes(),
+                    "bn_train_grad expects (C) mean and var");
+  const int64_t C = x.size(-1);
+  return {at::empty(x.sizes(), mf(x)), at::empty({C}, mf(x)), at::empty({C}, mf(x))};
+}
+
 }  // namespace
 
 // Schemas: the reference op names and argument order (tf_sampling.py, tf_grouping.py,
@@ -916,6 +1151,16 @@ TORCH_LIBRARY(pn2, m) {
         "Tensor? mean, Tensor? var, Tensor? gamma, Tensor? beta, float eps, bool relu, "
         "bool need_grad_x) -> "
         "(Tensor grad_x, Tensor grad_w, Tensor grad_b, Tensor grad_gamma, Tensor grad_beta)");
+  m.def("attn_kv_train(Tensor x, Tensor wq, Tensor bq, Tensor wk, Tensor bk, Tensor wv, Tensor bv, "
+        "bool add_max) -> (Tensor att, Tensor pmax, Tensor arg, Tensor q, Tensor kv)");
+  m.def("attn_kv_train_grad(Tensor grad_att, Tensor? grad_pmax, Tensor arg, Tensor x, Tensor wq, "
+        "Tensor wk, Tensor wv, Tensor q, Tensor kv, bool need_grad_x) -> "
+        "(Tensor grad_x, Tensor grad_wq, Tensor grad_bq, Tensor grad_wk, Tensor grad_bk, "
+        "Tensor grad_wv, Tensor grad_bv)");
+  m.def("bn_train(Tensor x, Tensor gamma, Tensor beta, float eps, bool relu) -> "
+        "(Tensor out, Tensor mean, Tensor var)");
+  m.def("bn_train_grad(Tensor grad_out, Tensor x, Tensor mean, Tensor var, Tensor gamma, "
+        "Tensor beta, float eps, bool relu) -> (Tensor grad_x, Tensor grad_gamma, Tensor grad_beta)");
 }
 
 // ROCm builds of PyTorch dispatch HIP tensors under the CUDA key.
@@ -943,6 +1188,10 @@ TORCH_LIBRARY_IMPL(pn2, CUDA, m) {
   m.impl("mlp_layer_train_grad", &mlp_layer_train_grad_hip);
   m.impl("mlp_layer_train_pool", &mlp_layer_train_pool_hip);
   m.impl("mlp_layer_train_pool_grad", &mlp_layer_train_pool_grad_hip);
+  m.impl("attn_kv_train", &attn_kv_train_hip);
+  m.impl("attn_kv_train_grad", &attn_kv_train_grad_hip);
+  m.impl("bn_train", &bn_train_hip);
+  m.impl("bn_train_grad", &bn_train_grad_hip);
 }
 
 TORCH_LIBRARY_IMPL(pn2, CPU, m) {
@@ -975,4 +1224,8 @@ TORCH_LIBRARY_IMPL(pn2, Meta, m) {
   m.impl("mlp_layer_train_grad", &mlp_layer_train_grad_meta);
   m.impl("mlp_layer_train_pool", &mlp_layer_train_pool_meta);
   m.impl("mlp_layer_train_pool_grad", &mlp_layer_train_pool_grad_meta);
+  m.impl("attn_kv_train", &attn_kv_train_meta);
+  m.impl("attn_kv_train_grad", &attn_kv_train_grad_meta);
+  m.impl("bn_train", &bn_train_meta);
+  m.impl("bn_train_grad", &bn_train_grad_meta);
 }

@@ -16,8 +16,8 @@ unchanged. Missing variables are created with the reference's initialisers (xavi
 zero biases, gamma 1, beta 0, moving mean 0, moving variance 1; tf_util.py:24-49).
 
 Training mode (is_training=True: batch norm on batch statistics, tf_util.py:512-531) runs on
-the HIP training layer torch.ops.pn2.mlp_layer_train (csrc/mlp_train.hip) through mlp_train,
-for the variables of a store made trainable with ParamStore.trainable(): device-resident
+the HIP training layer torch.ops.pn2.mlp_layer_train (csrc/mlp_train.hip) through mlp_train
+(and bn_train for a batch norm on its own), for the variables of a store made trainable with ParamStore.trainable(): device-resident
 leaves with gradients, moving averages updated in place on the device.
 """
 import math
@@ -372,6 +372,24 @@ def mlp_train(x, layers, bn_decay=None, pool=None):
                 p["moving_mean"].mul_(decay).add_((1 - decay) * mean)
                 p["moving_variance"].mul_(decay).add_((1 - decay) * var)
     return x
+
+
+def bn_train(x, params, bn_decay=None, relu=False):
+    """Batch-statistics batch norm of x (..., C) on its own (tf_util.py:512-531 with
+    is_training=True; the batch norm after the attention, attention_layer.py:261) on the HIP
+    training kernels (torch.ops.pn2.bn_train, autograd for x, gamma and beta), for the variables
+    `params` = store.bn(scope, C) of a trainable ParamStore. The moving averages are updated in
+    place on the device by mlp_train's rule: decay bn_decay (0.9 when None), biased batch
+    variance, no update when x has no rows."""
+    decay = 0.9 if bn_decay is None else float(bn_decay)
+    x = device_tensor(x, "inputs", torch.float32)
+    out, mean, var = _torch_ops.call("bn_train", x, params["gamma"], params["beta"], BN_EPSILON,
+                                     bool(relu))
+    if x.numel() > 0:
+        with torch.no_grad():
+            params["moving_mean"].mul_(decay).add_((1 - decay) * mean)
+            params["moving_variance"].mul_(decay).add_((1 - decay) * var)
+    return out
 
 
 class TorchLayer:
