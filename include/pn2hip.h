@@ -46,6 +46,10 @@
  *     is_training        (K and V projected together, and the     pn2_attn_kv_reduce_grad,
  *                        gradients)                                pn2_attn_dx_scatter,
  *                                                                  pn2_col_sum
+ *   dropout, is_training tf_util.py:594-612, pointnet2_sem_seg.py:56 → pn2_dropout,
+ *                                                                  pn2cpu_dropout (host)
+ *   get_loss             pointnet2_sem_seg.py:62-69 (tf.losses.    → pn2_softmax_xent_fwd,
+ *                        sparse_softmax_cross_entropy + weights)   pn2_softmax_xent_bwd
  *   get_subset          scannet_dataset/data_transformation.py  → pn2_scene_bbox,
  *                        :70-154 (training crop sampler)           pn2_crop_sample
  *   whole-scene chunker  scannet_dataset/complete_scene_loader.py → pn2_subvolume_select,
@@ -580,6 +584,50 @@ int pn2_attn_dx_scatter(float* grad_x, const float* grad_xq, const float* grad_p
 size_t pn2_col_sum_workspace_size(long long rows, int C);
 int pn2_col_sum(const float* x, long long rows, int C, float* out, void* workspace,
                 size_t workspace_bytes, pn2_stream_t stream);
+
+/* ---------------------------------------------------------------- segmentation head, training */
+/* The last three operations of a pointnet2_sem_seg training step (pointnet2_sem_seg.py:56,
+ * :62-69): the dropout between fc1 and fc2 and get_loss. csrc/head_train.hip. */
+
+/* tf_util.dropout with is_training (tf_util.py:594-612; TF 1.x: div(x, keep_prob) * mask):
+ *   out[e] = keep(e) ? x[e] / keep_prob : 0      (one correctly rounded fp32 division)
+ * over n floats. keep(e) is Philox4x32-10 (csrc/philox.h): key = (seed & 0xffffffff,
+ * seed >> 32), counter = (q & 0xffffffff, q >> 32, 0, 0) with q = e / 4; element e takes output
+ * word e % 4 and is kept iff word < floor(keep_prob * 2^32) (computed on the host in double).
+ * The mask is a pure function of (seed, e): nothing is saved, the backward is the same call on
+ * the gradient with the same seed, and the result does not depend on the launch shape. It is
+ * not TensorFlow's generator. keep_prob must lie in (0, 1] (1 copies); n = 0
+ * returns 0 without a launch; out == x is allowed. Pointers that are not 16-byte aligned take a
+ * scalar path. */
+int pn2_dropout(const float* x, long long n, float keep_prob, uint64_t seed, float* out,
+                pn2_stream_t stream);
+/* The same function on HOST pointers in plain C++, synchronous: the GPU result equals it bit
+ * for bit. */
+int pn2cpu_dropout(const float* x, long long n, float keep_prob, uint64_t seed, float* out);
+
+/* tf.losses.sparse_softmax_cross_entropy(labels, logits, weights) with its default reduction
+ * SUM_BY_NONZERO_WEIGHTS. logits (rows,C) fp32, labels (rows) int32, weights (rows) fp32 or
+ * NULL for all ones. One read of the logits. Per row: lse = m + log sum exp(z - m), m = max z,
+ * (saved for the backward), pred = the argmax with the lowest index on ties (may be NULL), ce =
+ * lse - z[label]. Two scalars in device memory: num_present = the rows with w != 0, loss = sum
+ * w * ce / num_present, or 0 when num_present = 0. The sum is two-stage: one fp32 partial per
+ * PN2_XENT_BLOCK_ROWS rows, added in double in a fixed order; no atomics, two runs give equal
+ * bits. A label outside [0, C) is never dereferenced: that row's ce is NaN (TF's GPU kernel).
+ * NaN logits are unsupported. 0 < rows < 2^31, 0 < C <= 65535. workspace:
+ * pn2_softmax_xent_workspace_size(rows) bytes. */
+#define PN2_XENT_BLOCK_ROWS 128
+size_t pn2_softmax_xent_workspace_size(long long rows);
+int pn2_softmax_xent_fwd(const float* logits, const int32_t* labels, const float* weights,
+                         long long rows, int C, float* lse, int32_t* pred, float* loss,
+                         int32_t* num_present, void* workspace, size_t workspace_bytes,
+                         pn2_stream_t stream);
+/* Its backward, one read of the logits and one write: grad_logits[i][c] = g * w_i /
+ * num_present * (exp(z_ic - lse_i) - [c == label_i]), g = *grad_loss. g and num_present are
+ * read from device memory (nothing synchronises); num_present = 0 writes every element as 0.
+ * The weights get no gradient (the reference feeds them from a placeholder). */
+int pn2_softmax_xent_bwd(const float* grad_loss, const float* logits, const int32_t* labels,
+                         const float* weights, const float* lse, const int32_t* num_present,
+                         long long rows, int C, float* grad_logits, pn2_stream_t stream);
 
 /* ---------------------------------------------------------------- scene crops ---------- */
 

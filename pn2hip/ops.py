@@ -42,6 +42,16 @@ and the training-mode AttentionLayer of the attention SA modules (csrc/attn_trai
                          (tf_util.py:512-531; :261)      -> (out, mean, var)
     bn_train_grad(grad_out, x, mean, var, gamma, beta, eps, relu)
                                                          -> (grad_x, grad_gamma, grad_beta)
+
+and the training-mode segmentation head (csrc/head_train.hip):
+
+    dropout(x, keep_prob, seed)                         tf_util.py:594-612 with is_training: the
+                         mask is Philox4x32-10 of (seed, element), nothing is saved; autograd
+                         applies the same op to the gradient
+    softmax_xent(logits, labels, weights)               tf.losses.sparse_softmax_cross_entropy
+                         with SUM_BY_NONZERO_WEIGHTS (pointnet2_sem_seg.py:62-69); pred = argmax
+                                                         -> (loss, lse, pred, num_present)
+    softmax_xent_grad(grad_loss, logits, labels, weights, lse, num_present) -> grad_logits
 """
 import importlib
 
@@ -53,7 +63,7 @@ NAMES = ("farthest_point_sample", "farthest_point_sample_and_gather", "gather_po
          "three_interpolate_grad", "idw_weights", "fp_fused", "attn_reduce", "attn_reduce_grad",
          "group_pool", "mlp_layer_train", "mlp_layer_train_grad", "mlp_layer_train_pool",
          "mlp_layer_train_pool_grad", "attn_kv_train", "attn_kv_train_grad", "bn_train",
-         "bn_train_grad")
+         "bn_train_grad", "dropout", "softmax_xent", "softmax_xent_grad")
 for _n in NAMES:
     globals()[_n] = getattr(_ops, _n)
 

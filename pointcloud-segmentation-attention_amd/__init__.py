@@ -7,7 +7,9 @@ Drop-in modules (reference names, argument order, shapes, dtypes, error messages
   tf_interpolate  three_nn, three_interpolate (+grad)
   pointnet_util   sample_and_group(_all/_msg), group_pool, fp_interpolate,
                   pointnet_sa_module(_msg), pointnet_fp_module (fused group/interp + MLP + pool)
-  tf_util         conv2d / conv1d (1x1, inference), ParamStore, SharedMLP
+  tf_util         conv2d / conv1d (1x1), dropout, sparse_softmax_cross_entropy, ParamStore,
+                  SharedMLP
+  pointnet2_sem_seg      get_model, get_loss (the SSG segmentation model and its weighted loss)
   data_transformation    get_subset (the ScanNet crop sampler) on the GPU
   complete_scene_loader  the whole-scene chunker (selection + gathers on the GPU)
   attention_layer attention_reduce, AttentionLayer
@@ -16,9 +18,9 @@ Everything runs the gfx950 kernels of libpn2hip.so (C ABI: include/pn2hip.h).
 The directory name has hyphens, so import it with importlib:
     pn2 = importlib.import_module("pointcloud-segmentation-attention_amd")
 """
-from . import attention_layer, complete_scene_loader, data_transformation, grid, plan, pointnet_util, \
-    shard, stack, synth, tf_grouping, tf_interpolate, tf_sampling, tf_util
+from . import attention_layer, complete_scene_loader, data_transformation, grid, plan, pointnet2_sem_seg, \
+    pointnet_util, shard, stack, synth, tf_grouping, tf_interpolate, tf_sampling, tf_util
 from ._lib import LIB_PATH, InvalidArgumentError, Pn2RuntimeError, lib
 
 __all__ = ["tf_sampling", "tf_grouping", "tf_interpolate", "pointnet_util", "attention_layer", "grid", "tf_util", "data_transformation", "complete_scene_loader",
-           "synth", "stack", "shard", "plan", "lib", "LIB_PATH", "InvalidArgumentError", "Pn2RuntimeError"]
+           "synth", "stack", "shard", "plan", "pointnet2_sem_seg", "lib", "LIB_PATH", "InvalidArgumentError", "Pn2RuntimeError"]

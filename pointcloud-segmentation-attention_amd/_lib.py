@@ -39,6 +39,8 @@ class Pn2RuntimeError(RuntimeError):
 
 _P, _I, _F, _S = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 _LL = ctypes.c_longlong
+_U64 = ctypes.c_uint64
+PN2_XENT_BLOCK_ROWS = 128  # include/pn2hip.h
 
 
 class MlpLayer(ctypes.Structure):
@@ -154,6 +156,11 @@ SIGNATURES = {
     "pn2_attn_dx_scatter": (_I, [_P, _P, _P, _P, _LL, _I, _I, _P]),
     "pn2_col_sum_workspace_size": (_S, [_LL, _I]),
     "pn2_col_sum": (_I, [_P, _LL, _I, _P, _P, _S, _P]),
+    "pn2_dropout": (_I, [_P, _LL, _F, _U64, _P, _P]),
+    "pn2cpu_dropout": (_I, [_P, _LL, _F, _U64, _P]),
+    "pn2_softmax_xent_workspace_size": (_S, [_LL]),
+    "pn2_softmax_xent_fwd": (_I, [_P, _P, _P, _LL, _I, _P, _P, _P, _P, _P, _S, _P]),
+    "pn2_softmax_xent_bwd": (_I, [_P, _P, _P, _P, _P, _P, _LL, _I, _P, _P]),
     "pn2_scene_workspace_size": (_S, [_I]),
     "pn2_scene_bbox": (_I, [_P, _I, _P, _P, _S, _P]),
     "pn2_crop_workspace_size": (_S, [_I, _I, _I]),

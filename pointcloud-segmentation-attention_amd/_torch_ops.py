@@ -8,7 +8,9 @@ reduction (TF autodiff through attention_layer.py:35-42, all of Q, K, V) and the
 shared-MLP layer (mlp_layer_train, and mlp_layer_train_pool for the layer fused with the max
 pool over nsample: x, weight, bias, gamma, beta; csrc/mlp_train.hip), the training-mode attention
 layer (attn_kv_train: x and the three Dense layers' variables; csrc/attn_train.hip) and the
-stand-alone batch-statistics batch norm (bn_train: x, gamma, beta).
+stand-alone batch-statistics batch norm (bn_train: x, gamma, beta). The training head's ops
+(csrc/head_train.hip: dropout, the same op on the gradient with the same seed; softmax_xent,
+the logits only) carry their autograd in libpn2torch.so itself (csrc/torch_ops.cpp).
 
 The mirror modules (tf_sampling, tf_grouping, tf_interpolate, attention_layer) call these ops
 for every reference-signature call; the pn2hip alias package re-exports them as pn2hip.ops.

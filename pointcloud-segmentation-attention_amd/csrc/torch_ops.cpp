@@ -14,7 +14,9 @@
 // so is the training-mode shared-MLP layer's (mlp_layer_train -> mlp_layer_train_grad, and
 // mlp_layer_train_pool -> mlp_layer_train_pool_grad for the layer fused with the max pool), the
 // training-mode attention layer's (attn_kv_train -> attn_kv_train_grad) and the stand-alone
-// batch-statistics batch norm's (bn_train -> bn_train_grad).
+// batch-statistics batch norm's (bn_train -> bn_train_grad). The training head's autograd
+// (dropout -> dropout with the same seed, softmax_xent -> softmax_xent_grad;
+// csrc/head_train.hip) is registered here, in C++: see "autograd (C++)" below.
 // CPU kernels exist only for the three ops the reference itself runs on the CPU (ThreeNN,
 // ThreeInterpolate, ThreeInterpolateGrad: registered for DEVICE_CPU only,
 // tf_interpolate.cpp:187,222,262), through the host twins pn2cpu_* (csrc/cpu_interp.cpp);
@@ -22,6 +24,7 @@
 #include <ATen/ATen.h>
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
+#include <torch/csrc/autograd/custom_function.h>
 #include <torch/library.h>
 
 #include <string>
@@ -897,6 +900,101 @@ std::tuple<Tensor, Tensor, Tensor> bn_train_grad_hip(const Tensor& grad_out_, co
   return {grad_x, grad_gamma, grad_beta};
 }
 
+// ---- training-mode segmentation head (csrc/head_train.hip): tf_util.dropout with is_training
+// (tf_util.py:594-612) and get_loss's weighted sparse softmax cross-entropy
+// (pointnet2_sem_seg.py:62-69, tf.losses' SUM_BY_NONZERO_WEIGHTS)
+void chk_dropout(const Tensor& x, double keep_prob) {
+  TORCH_CHECK_VALUE(keep_prob > 0.0 && keep_prob <= 1.0 && static_cast<float>(keep_prob) > 0.f,
+                    "dropout expects keep_prob in (0, 1], got ", keep_prob);
+  TORCH_CHECK_VALUE(x.scalar_type() == at::kFloat, "dropout expects a float32 x, got ",
+                    x.scalar_type());
+}
+// logits (..., C), labels (...) int32, weights (...) float32 or absent
+void chk_xent(const Tensor& logits, const Tensor& labels, const std::optional<Tensor>& weights,
+              const char* op) {
+  TORCH_CHECK_VALUE(logits.dim() >= 1 && logits.size(-1) > 0 && logits.size(-1) <= 65535, op,
+                    " expects (..., C) logits with 0 < C <= 65535");
+  TORCH_CHECK_VALUE(logits.scalar_type() == at::kFloat, op, " expects float32 logits, got ",
+                    logits.scalar_type());
+  TORCH_CHECK_VALUE(labels.scalar_type() == at::kInt, op, " expects int32 labels, got ",
+                    labels.scalar_type());
+  const c10::IntArrayRef lead = logits.sizes().slice(0, logits.dim() - 1);
+  TORCH_CHECK_VALUE(labels.sizes() == lead, op, " expects labels shaped like logits without its ",
+                    "last axis: logits ", logits.sizes(), ", labels ", labels.sizes());
+  if (has(weights)) {
+    TORCH_CHECK_VALUE(weights->scalar_type() == at::kFloat, op, " expects float32 weights, got ",
+                      weights->scalar_type());
+    TORCH_CHECK_VALUE(weights->sizes() == lead, op, " expects weights shaped like labels: labels ",
+                      labels.sizes(), ", weights ", weights->sizes());
+  }
+}
+void chk_xent_grad(const Tensor& grad_loss, const Tensor& logits, const Tensor& labels,
+                   const std::optional<Tensor>& weights, const Tensor& lse,
+                   const Tensor& num_present, const char* op) {
+  chk_xent(logits, labels, weights, op);
+  TORCH_CHECK_VALUE(grad_loss.numel() == 1 && grad_loss.scalar_type() == at::kFloat, op,
+                    " expects a float32 scalar grad_loss");
+  TORCH_CHECK_VALUE(lse.sizes() == labels.sizes() && lse.scalar_type() == at::kFloat, op,
+                    " expects float32 lse shaped like labels");
+  TORCH_CHECK_VALUE(num_present.numel() == 1 && num_present.scalar_type() == at::kInt, op,
+                    " expects an int32 scalar num_present");
+}
+
+Tensor dropout_hip(const Tensor& x_, double keep_prob, int64_t seed) {
+  chk_dropout(x_, keep_prob);
+  Tensor x = dev(x_, "x", at::kFloat);
+  c10::hip::HIPGuard g(x.device().index());
+  Tensor out = at::empty(x.sizes(), f32(x));
+  if (x.numel() == 0) return out;
+  check_rc(pn2_dropout(F(x), x.numel(), static_cast<float>(keep_prob),
+                       static_cast<uint64_t>(seed), out.data_ptr<float>(), stream_of(x)),
+           "dropout");
+  return out;
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> softmax_xent_hip(const Tensor& logits_,
+                                                            const Tensor& labels_,
+                                                            const std::optional<Tensor>& weights_) {
+  const char* op = "softmax_xent";
+  chk_xent(logits_, labels_, weights_, op);
+  Tensor logits = dev(logits_, "logits", at::kFloat), labels = dev(labels_, "labels", at::kInt);
+  Tensor weights;
+  if (has(weights_)) weights = dev(*weights_, "weights", at::kFloat);
+  c10::hip::HIPGuard g(logits.device().index());
+  const int C = I(logits.size(-1));
+  const int64_t rows = labels.numel();
+  Tensor lse = at::empty(labels.sizes(), f32(logits));
+  Tensor pred = at::empty(labels.sizes(), i32(logits));
+  if (rows == 0)  // no rows: TF's safe division gives 0
+    return {at::zeros({}, f32(logits)), lse, pred, at::zeros({}, i32(logits))};
+  Tensor loss = at::empty({}, f32(logits)), num_present = at::empty({}, i32(logits));
+  const size_t ws = pn2_softmax_xent_workspace_size(rows);
+  Tensor w = workspace(logits, ws);
+  check_rc(pn2_softmax_xent_fwd(F(logits), Ii(labels), F(weights), rows, C, lse.data_ptr<float>(),
+                                pred.data_ptr<int32_t>(), loss.data_ptr<float>(),
+                                num_present.data_ptr<int32_t>(), P(w), ws, stream_of(logits)), op);
+  return {loss, lse, pred, num_present};
+}
+
+Tensor softmax_xent_grad_hip(const Tensor& grad_loss_, const Tensor& logits_, const Tensor& labels_,
+                             const std::optional<Tensor>& weights_, const Tensor& lse_,
+                             const Tensor& num_present_) {
+  const char* op = "softmax_xent_grad";
+  chk_xent_grad(grad_loss_, logits_, labels_, weights_, lse_, num_present_, op);
+  Tensor gl = dev(grad_loss_, "grad_loss", at::kFloat);
+  Tensor logits = dev(logits_, "logits", at::kFloat), labels = dev(labels_, "labels", at::kInt);
+  Tensor lse = dev(lse_, "lse", at::kFloat), np = dev(num_present_, "num_present", at::kInt);
+  Tensor weights;
+  if (has(weights_)) weights = dev(*weights_, "weights", at::kFloat);
+  c10::hip::HIPGuard g(logits.device().index());
+  Tensor grad = at::empty(logits.sizes(), f32(logits));
+  const int64_t rows = labels.numel();
+  if (rows == 0) return grad;
+  check_rc(pn2_softmax_xent_bwd(F(gl), F(logits), Ii(labels), F(weights), F(lse), Ii(np), rows,
+                                I(logits.size(-1)), grad.data_ptr<float>(), stream_of(logits)), op);
+  return grad;
+}
+
 // ------------------------------------------------------------------------- CPU kernels
 // (the reference's CPU-only ops; host twins in csrc/cpu_interp.cpp)
 Tensor host(const Tensor& t, const char* name, at::ScalarType dt) {
@@ -1115,6 +1213,91 @@ std::tuple<Tensor, Tensor, Tensor> bn_train_grad_meta(const Tensor& grad_out, co
   return {at::empty(x.sizes(), mf(x)), at::empty({C}, mf(x)), at::empty({C}, mf(x))};
 }
 
+Tensor dropout_meta(const Tensor& x, double keep_prob, int64_t) {
+  chk_dropout(x, keep_prob);
+  return at::empty(x.sizes(), mf(x));
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> softmax_xent_meta(const Tensor& logits,
+                                                             const Tensor& labels,
+                                                             const std::optional<Tensor>& weights) {
+  chk_xent(logits, labels, weights, "softmax_xent");
+  return {at::empty({}, mf(logits)), at::empty(labels.sizes(), mf(logits)),
+          at::empty(labels.sizes(), mi(logits)), at::empty({}, mi(logits))};
+}
+Tensor softmax_xent_grad_meta(const Tensor& grad_loss, const Tensor& logits, const Tensor& labels,
+                              const std::optional<Tensor>& weights, const Tensor& lse,
+                              const Tensor& num_present) {
+  chk_xent_grad(grad_loss, logits, labels, weights, lse, num_present, "softmax_xent_grad");
+  return at::empty(logits.sizes(), mf(logits));
+}
+
+// ------------------------------------------------------------------------- autograd (C++)
+// The two ops of the training head carry their autograd here instead of in _torch_ops.py: the
+// head is bound by launches and host time, and a Python-registered backward
+// costs more host time per call than both kernels take on the device. Forward and backward go
+// back through the dispatcher, so the HIP and Meta kernels above serve both.
+using torch::autograd::AutogradContext;
+using torch::autograd::variable_list;
+
+struct DropoutFn : public torch::autograd::Function<DropoutFn> {
+  static Tensor forward(AutogradContext* ctx, const Tensor& x, double keep_prob, int64_t seed) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    ctx->saved_data["keep_prob"] = keep_prob;  // the mask is a function of (seed, element)
+    ctx->saved_data["seed"] = seed;
+    static auto op = c10::Dispatcher::singleton()
+                         .findSchemaOrThrow("pn2::dropout", "")
+                         .typed<Tensor(const Tensor&, double, int64_t)>();
+    return op.call(x, keep_prob, seed);
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    if (!grads[0].defined()) return {Tensor(), Tensor(), Tensor()};
+    static auto op = c10::Dispatcher::singleton()
+                         .findSchemaOrThrow("pn2::dropout", "")
+                         .typed<Tensor(const Tensor&, double, int64_t)>();
+    return {op.call(grads[0].contiguous(), ctx->saved_data["keep_prob"].toDouble(),
+                    ctx->saved_data["seed"].toInt()),
+            Tensor(), Tensor()};
+  }
+};
+Tensor dropout_autograd(const Tensor& x, double keep_prob, int64_t seed) {
+  return DropoutFn::apply(x, keep_prob, seed);
+}
+
+struct SoftmaxXentFn : public torch::autograd::Function<SoftmaxXentFn> {
+  static variable_list forward(AutogradContext* ctx, const Tensor& logits, const Tensor& labels,
+                               const std::optional<Tensor>& weights) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    static auto op =
+        c10::Dispatcher::singleton()
+            .findSchemaOrThrow("pn2::softmax_xent", "")
+            .typed<std::tuple<Tensor, Tensor, Tensor, Tensor>(
+                const Tensor&, const Tensor&, const std::optional<Tensor>&)>();
+    auto [loss, lse, pred, num_present] = op.call(logits, labels, weights);
+    ctx->mark_non_differentiable({lse, pred, num_present});
+    ctx->save_for_backward({logits, labels, has(weights) ? *weights : Tensor(), lse, num_present});
+    return {loss, lse, pred, num_present};
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    // the weights get no gradient: the reference feeds them from a placeholder
+    if (!grads[0].defined()) return {Tensor(), Tensor(), Tensor()};
+    const variable_list saved = ctx->get_saved_variables();
+    static auto op = c10::Dispatcher::singleton()
+                         .findSchemaOrThrow("pn2::softmax_xent_grad", "")
+                         .typed<Tensor(const Tensor&, const Tensor&, const Tensor&,
+                                       const std::optional<Tensor>&, const Tensor&,
+                                       const Tensor&)>();
+    const std::optional<Tensor> weights =
+        saved[2].defined() ? std::optional<Tensor>(saved[2]) : std::nullopt;
+    return {op.call(grads[0].contiguous(), saved[0], saved[1], weights, saved[3], saved[4]),
+            Tensor(), Tensor()};
+  }
+};
+std::tuple<Tensor, Tensor, Tensor, Tensor> softmax_xent_autograd(
+    const Tensor& logits, const Tensor& labels, const std::optional<Tensor>& weights) {
+  variable_list o = SoftmaxXentFn::apply(logits, labels, weights);
+  return {o[0], o[1], o[2], o[3]};
+}
+
 }  // namespace
 
 // Schemas: the reference op names and argument order (tf_sampling.py, tf_grouping.py,
@@ -1161,6 +1344,11 @@ TORCH_LIBRARY(pn2, m) {
         "(Tensor out, Tensor mean, Tensor var)");
   m.def("bn_train_grad(Tensor grad_out, Tensor x, Tensor mean, Tensor var, Tensor gamma, "
         "Tensor beta, float eps, bool relu) -> (Tensor grad_x, Tensor grad_gamma, Tensor grad_beta)");
+  m.def("dropout(Tensor x, float keep_prob, int seed) -> Tensor");
+  m.def("softmax_xent(Tensor logits, Tensor labels, Tensor? weights) -> "
+        "(Tensor loss, Tensor lse, Tensor pred, Tensor num_present)");
+  m.def("softmax_xent_grad(Tensor grad_loss, Tensor logits, Tensor labels, Tensor? weights, "
+        "Tensor lse, Tensor num_present) -> Tensor");
 }
 
 // ROCm builds of PyTorch dispatch HIP tensors under the CUDA key.
@@ -1192,6 +1380,14 @@ TORCH_LIBRARY_IMPL(pn2, CUDA, m) {
   m.impl("attn_kv_train_grad", &attn_kv_train_grad_hip);
   m.impl("bn_train", &bn_train_hip);
   m.impl("bn_train_grad", &bn_train_grad_hip);
+  m.impl("dropout", &dropout_hip);
+  m.impl("softmax_xent", &softmax_xent_hip);
+  m.impl("softmax_xent_grad", &softmax_xent_grad_hip);
+}
+
+TORCH_LIBRARY_IMPL(pn2, Autograd, m) {
+  m.impl("dropout", &dropout_autograd);
+  m.impl("softmax_xent", &softmax_xent_autograd);
 }
 
 TORCH_LIBRARY_IMPL(pn2, CPU, m) {
@@ -1228,4 +1424,7 @@ TORCH_LIBRARY_IMPL(pn2, Meta, m) {
   m.impl("attn_kv_train_grad", &attn_kv_train_grad_meta);
   m.impl("bn_train", &bn_train_meta);
   m.impl("bn_train_grad", &bn_train_grad_meta);
+  m.impl("dropout", &dropout_meta);
+  m.impl("softmax_xent", &softmax_xent_meta);
+  m.impl("softmax_xent_grad", &softmax_xent_grad_meta);
 }

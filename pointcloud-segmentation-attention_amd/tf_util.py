@@ -18,7 +18,9 @@ zero biases, gamma 1, beta 0, moving mean 0, moving variance 1; tf_util.py:24-49
 Training mode (is_training=True: batch norm on batch statistics, tf_util.py:512-531) runs on
 the HIP training layer torch.ops.pn2.mlp_layer_train (csrc/mlp_train.hip) through mlp_train
 (and bn_train for a batch norm on its own), for the variables of a store made trainable with ParamStore.trainable(): device-resident
-leaves with gradients, moving averages updated in place on the device.
+leaves with gradients, moving averages updated in place on the device. The segmentation head's
+last operations train on csrc/head_train.hip: dropout (tf_util.py:594-612) and
+sparse_softmax_cross_entropy (the tf.losses call of pointnet2_sem_seg.get_loss).
 """
 import math
 
@@ -390,6 +392,46 @@ def bn_train(x, params, bn_decay=None, relu=False):
             params["moving_mean"].mul_(decay).add_((1 - decay) * mean)
             params["moving_variance"].mul_(decay).add_((1 - decay) * var)
     return out
+
+
+def dropout(inputs, is_training, scope, keep_prob=0.5, noise_shape=None, seed=None):
+    """tf_util.dropout (tf_util.py:594-612) on the HIP kernel (torch.ops.pn2.dropout,
+    csrc/head_train.hip): with is_training, inputs / keep_prob where the mask keeps an element, 0
+    elsewhere; without it, `inputs` itself. The mask is Philox4x32-10 of (seed, element index),
+    so no mask tensor is kept and autograd applies the same op to the gradient. Extra keyword
+    `seed`: a Python int; None draws one from torch's default CPU generator (so
+    torch.manual_seed makes a run reproducible, and nothing touches the device). It creates no
+    variables, so it takes no store; `scope` is the reference's name scope only."""
+    if noise_shape is not None:
+        raise NotImplementedError("dropout: noise_shape is not supported (the reference never "
+                                  "passes one)")
+    if not is_training:
+        return inputs
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, ()))
+    return _torch_ops.call("dropout", device_tensor(inputs, "inputs", torch.float32),
+                           float(keep_prob), int(seed))
+
+
+def sparse_softmax_cross_entropy(labels, logits, weights=1.0):
+    """tf.losses.sparse_softmax_cross_entropy(labels, logits, weights) with its default reduction
+    SUM_BY_NONZERO_WEIGHTS (the loss of pointnet2_sem_seg.get_loss): sum of weights * (logsumexp
+    (logits) - logits[label]) over the number of non-zero weights, 0 when there is none. logits
+    (..., C) float32, labels (...) integer, weights a Python scalar or a float32 tensor of the
+    labels' shape. One HIP kernel pass each way (torch.ops.pn2.softmax_xent); the gradient flows
+    to the logits only."""
+    logits = device_tensor(logits, "logits", torch.float32)
+    if isinstance(labels, torch.Tensor) and labels.dtype in (torch.int64, torch.int16,
+                                                             torch.uint8, torch.int8):
+        labels = labels.to(torch.int32)
+    labels = device_tensor(labels, "labels", torch.int32)
+    if isinstance(weights, torch.Tensor) and weights.dim() > 0:
+        return _torch_ops.call("softmax_xent", logits, labels,
+                               device_tensor(weights, "weights", torch.float32))[0]
+    w = float(weights)
+    loss = _torch_ops.call("softmax_xent", logits, labels, None)[0]
+    # a scalar w weights every row alike: w * the mean, and no row is present at w = 0
+    return torch.zeros_like(loss) if w == 0.0 else loss * w
 
 
 class TorchLayer:

@@ -1,0 +1,214 @@
+#!/usr/bin/env python3
+"""Time the training-mode segmentation head, forward plus backward, on the HIP kernels of
+csrc/head_train.hip (torch.ops.pn2.dropout, torch.ops.pn2.softmax_xent) against the torch ops
+they replace, at the cfg2 head shape with B = 16 (131,072 rows):
+
+    loss      the weighted loss alone on 131,072 x 21 logits
+    tail      dropout(131,072 x 128) -> fc2 (128 -> 21, mlp_layer_train) -> loss
+    dropout   dropout alone on 131,072 x 128 (reported without a bar: torch's dropout is one
+              kernel already; what the HIP op removes is the mask tensor)
+
+    python tools/bench_head_train.py [--repeats 7] [--iters 10] [--out summary.json]
+
+The torch side is torch.nn.functional.dropout and the weighted loss composed as
+(F.cross_entropy(reduction="none") * w).sum() / count_nonzero(w), with autograd for both; fc2
+is mlp_layer_train on both sides of `tail`. Each shape runs in a child process of its own under
+`timeout`; a shape that fails stops the run. Per shape: warm-up, then `repeats` timed windows of
+`iters` forward+backward passes per side, the two sides alternating, timed with events on the
+stream; the median window, the range and the peak of torch.cuda.max_memory_allocated over one
+pass above the memory held before it are reported. The bar on `loss` and `tail`: the HIP side's
+median window is no higher than the torch side's, measured in the same run.
+
+Then, for `loss` and `dropout`, the C entry points alone (events, median of `repeats` windows)
+with the bytes their algorithm has to move over that time.
+"""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+ROWS, FEAT, NCLASS = 16 * 8192, 128, 21
+SHAPES = ("loss", "tail", "dropout")
+BARRED = ("loss", "tail")
+KEEP = 0.5
+
+
+def windows(torch, fns, repeats, iters):
+    """Per fn the time per call (us) of `repeats` windows of `iters` calls, alternating."""
+    for fn in fns:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = [[] for _ in fns]
+    for _ in range(repeats):
+        for k, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[k].append(e0.elapsed_time(e1) / iters * 1e3)
+    return times
+
+
+def peak_delta(torch, fn):
+    """Bytes one call allocates at its peak above what is held before it."""
+    fn()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    before = torch.cuda.memory_allocated()
+    fn()
+    torch.cuda.synchronize()
+    return int(torch.cuda.max_memory_allocated() - before)
+
+
+def one(name, repeats, iters):
+    import torch
+    import torch.nn.functional as F
+    importlib.import_module("pointcloud-segmentation-attention_amd")
+    import pn2hip
+    ops = pn2hip.ops
+    assert torch.cuda.is_available(), "bench_head_train needs the MI355X"
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(7)
+    leaf = lambda t: t.to(dev).requires_grad_(True)  # noqa: E731
+    labels = torch.randint(0, NCLASS, (ROWS,), generator=g, dtype=torch.int32).to(dev)
+    labels64 = labels.long()
+    smpw = torch.rand(ROWS, generator=g) * 4.5 + 0.5
+    smpw[torch.rand(ROWS, generator=g) < 0.3] = 0.0  # unannotated points
+    smpw = smpw.to(dev)
+    logits = leaf(torch.rand(ROWS, NCLASS, generator=g) * 8 - 4)
+    feats = leaf(torch.rand(ROWS, FEAT, generator=g) * 2)
+    lim = (6.0 / (FEAT + NCLASS)) ** 0.5
+    w2 = leaf((torch.rand(FEAT, NCLASS, generator=g) * 2 - 1) * lim)
+    b2 = leaf(torch.zeros(NCLASS))
+    go = (torch.rand(ROWS, FEAT, generator=g) * 2 - 1).to(dev)
+    leaves = (logits, feats, w2, b2)
+    seed = [0]
+
+    def clear():
+        for t in leaves:
+            t.grad = None
+
+    def loss_hip(z):
+        return ops.softmax_xent(z, labels, smpw)[0]
+
+    def loss_torch(z):
+        ce = F.cross_entropy(z, labels64, reduction="none")
+        return (ce * smpw).sum() / torch.count_nonzero(smpw)
+
+    def drop_hip(x):
+        seed[0] += 1
+        return ops.dropout(x, KEEP, seed[0])
+
+    def drop_torch(x):
+        return F.dropout(x, 1.0 - KEEP, True)
+
+    def fc2(x):
+        return ops.mlp_layer_train(x, w2, b2, None, None, 1e-3, False)[0]
+
+    def side(drop, loss):
+        if name == "loss":
+            def fn():
+                clear()
+                loss(logits).backward()
+        elif name == "tail":
+            def fn():
+                clear()
+                loss(fc2(drop(feats))).backward()
+        else:
+            def fn():
+                clear()
+                drop(feats).backward(go)
+        return fn
+
+    hip, ref = side(drop_hip, loss_hip), side(drop_torch, loss_torch)
+    check = {}
+    if name == "loss":  # the two sides compute the same objective
+        a, b = float(loss_hip(logits).detach()), float(loss_torch(logits).detach())
+        check = {"loss_hip": a, "loss_torch": b}
+    t_hip, t_ref = windows(torch, [hip, ref], repeats, iters)
+    m_hip, m_ref = statistics.median(t_hip), statistics.median(t_ref)
+    res = {"shape": name, "rows": ROWS, "classes": NCLASS, "features": FEAT, "repeats": repeats,
+           "iters": iters, "hip_fwd_bwd_us": round(m_hip, 1), "torch_fwd_bwd_us": round(m_ref, 1),
+           "hip_min_max_us": [round(min(t_hip), 1), round(max(t_hip), 1)],
+           "torch_min_max_us": [round(min(t_ref), 1), round(max(t_ref), 1)],
+           "torch_over_hip": round(m_ref / m_hip, 2),
+           "hip_peak_alloc_bytes": peak_delta(torch, hip),
+           "torch_peak_alloc_bytes": peak_delta(torch, ref)}
+    if name in BARRED:
+        res["no_slower"] = bool(m_hip <= m_ref)
+    res.update(check)
+
+    # the C entry points alone: the time of the call and the bytes its algorithm has to move
+    L = importlib.import_module("pointcloud-segmentation-attention_amd._lib")
+    lib, ptr, st = L.lib(), L.ptr, L.stream_of(feats)
+    calls = {}
+    if name == "dropout":
+        x, out = feats.detach(), torch.empty_like(feats)
+        calls["pn2_dropout"] = (lambda: L.check(lib.pn2_dropout(
+            ptr(x), x.numel(), KEEP, 1234, ptr(out), st), "dropout"), 2 * 4 * x.numel())
+    elif name == "loss":
+        z, gz = logits.detach(), torch.empty_like(logits)
+        lse = torch.empty(ROWS, device=dev)
+        pred = torch.empty(ROWS, dtype=torch.int32, device=dev)
+        loss, npres = torch.empty((), device=dev), torch.empty((), dtype=torch.int32, device=dev)
+        one_ = torch.ones((), device=dev)
+        nws = int(lib.pn2_softmax_xent_workspace_size(ROWS))
+        ws = torch.empty(nws // 4, device=dev)
+        zb = 4 * z.numel()
+        calls["pn2_softmax_xent_fwd"] = (lambda: L.check(lib.pn2_softmax_xent_fwd(
+            ptr(z), ptr(labels), ptr(smpw), ROWS, NCLASS, ptr(lse), ptr(pred), ptr(loss),
+            ptr(npres), ptr(ws), nws, st), "softmax_xent_fwd"), zb + 4 * 4 * ROWS)
+        calls["pn2_softmax_xent_bwd"] = (lambda: L.check(lib.pn2_softmax_xent_bwd(
+            ptr(one_), ptr(z), ptr(labels), ptr(smpw), ptr(lse), ptr(npres), ROWS, NCLASS,
+            ptr(gz), st), "softmax_xent_bwd"), 2 * zb + 3 * 4 * ROWS)
+    kern = {}
+    for nm, (fn, nbytes) in calls.items():  # in order: the backward reads the forward's outputs
+        fn()
+        (t,) = windows(torch, [fn], repeats, iters)
+        us = statistics.median(t)
+        kern[nm] = {"us": round(us, 1), "bytes": nbytes, "GBps": round(nbytes / us / 1e3, 1)}
+    if kern:
+        res["entry_points"] = kern
+    print(json.dumps(res))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--timeout", type=int, default=120, help="seconds per shape")
+    ap.add_argument("--out", default=None, help="write the results as one JSON file")
+    ap.add_argument("--one", choices=SHAPES, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.repeats < 5:
+        ap.error("--repeats must be at least 5")
+    if args.one:
+        return one(args.one, args.repeats, args.iters)
+    results = []
+    for name in SHAPES:
+        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__),
+               "--one", name, "--repeats", str(args.repeats), "--iters", str(args.iters)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        sys.stderr.write(r.stderr[-2000:])
+        if r.returncode != 0:
+            sys.exit(f"{name}: exit status {r.returncode}; stopping")
+        line = r.stdout.strip().splitlines()[-1]
+        print(line, flush=True)
+        results.append(json.loads(line))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"shapes": results}, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
