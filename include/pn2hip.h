@@ -389,6 +389,45 @@ int pn2_fp_grid_fused_known(const void* known_grid, const float* xyz1, const flo
                             const float* points2, int C2, int B, int n, int m, float* out,
                             float* dist, int32_t* idx, pn2_stream_t stream);
 
+/* ---------------------------------------------------------------- ordered gradients ------ */
+
+/* The gradients of group_point and three_interpolate as gathers in a fixed order
+ * (csrc/geom_train.hip): no float atomics, no zero-fill pass, two runs give equal bits. The
+ * training path of the SA and FP modules uses them; pn2_group_point_grad and
+ * pn2_three_interpolate_grad above keep the reference's atomics.
+ *
+ * Inverse index. keys (B,S) int32 with values in [0,K): slot s of cloud b points at row
+ * keys[b][s]. The index holds, per cloud, offsets[K+1] and the slots grouped by key, each key's
+ * slots in ascending slot order: a pure function of `keys`. A key outside [0,K) is never used as
+ * an index; its slot is left out (the reference would write out of bounds). Any segment length
+ * from 0 to S is handled, all slots on one key included. `inv` is a 16-byte aligned device
+ * buffer of at least pn2_inverse_index_size(B,S,K) bytes (a multiple of 16, monotonic in each
+ * argument, 0 for B <= 0). Bounds: K <= PN2_INV_MAX_KEYS (the counts of a cloud live in one
+ * workgroup's LDS), S <= PN2_INV_MAX_SLOTS, B <= 65535 (clouds are grid rows); beyond them, for a
+ * NULL, misaligned or too small buffer: PN2_EINVAL before any launch. B = 0 or S = 0: a no-op. */
+#define PN2_INV_MAX_KEYS 16384
+#define PN2_INV_MAX_SLOTS (1 << 20)
+size_t pn2_inverse_index_size(int B, int S, int K);
+int pn2_inverse_index_build(const int32_t* keys, int B, int S, int K, void* inv, size_t inv_bytes,
+                            pn2_stream_t stream);
+/* grad_points (B,N,C): grad_points[b][n][c] = ((+0.0f + g[s0]) + g[s1]) + ... over the slots
+ * s0 < s1 < ... of key n in `inv` = the index of idx (B, M*nsample) with K = N, where
+ * g[s] = grad_out[(b*M*nsample + s)*ld + col0 + c]: the source rows are `ld` floats apart and
+ * columns [col0, col0+C) are read in place (col0 + C <= ld, else PN2_EINVAL), so the points'
+ * columns of group_concat's gradient need no slice copy (ld = C + 3; col0 = 3 in the SSG
+ * order, 0 with PN2_XYZ_LAST). Every element is written: a point no group took gets +0.0f.
+ * One __fadd_rn per slot. M*nsample = 0: all +0.0f, `inv` is not read. */
+int pn2_group_point_grad_ordered(const float* grad_out, int ld, int col0, const void* inv, int B,
+                                 int N, int C, int M, int nsample, float* grad_points,
+                                 pn2_stream_t stream);
+/* grad_points (B,m,C), the same ordered sum over `inv` = the index of idx (B, 3n) with K = m
+ * (slot s = 3*i + t), of __fmul_rn(grad_out[(b*n + i)*ld + col0 + c], weight[b][s]): product
+ * rounded, then added, no FMA: tf_interpolate.cpp:143-145 in its loop order. With ld = C and
+ * col0 = 0 the result equals pn2cpu_three_interpolate_grad bit for bit for any idx in range. */
+int pn2_three_interpolate_grad_ordered(const float* grad_out, int ld, int col0, const void* inv,
+                                       const float* weight, int B, int n, int C, int m,
+                                       float* grad_points, pn2_stream_t stream);
+
 /* ---------------------------------------------------------------- attention / pooling --- */
 
 /* AttentionLayer reduction core (attention_layer.py:35-42) with key_dim = output_dim = 4,

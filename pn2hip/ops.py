@@ -52,6 +52,19 @@ and the training-mode segmentation head (csrc/head_train.hip):
                          with SUM_BY_NONZERO_WEIGHTS (pointnet2_sem_seg.py:62-69); pred = argmax
                                                          -> (loss, lse, pred, num_present)
     softmax_xent_grad(grad_loss, logits, labels, weights, lse, num_present) -> grad_logits
+
+and the training-mode geometry of the SA and FP modules (csrc/geom_train.hip): the fused forward
+kernels, with gradients that are gathers in a fixed order (no float atomics: two runs give equal
+bits); autograd is registered for `points`, `points1` and `points2`, never for coordinates:
+
+    group_concat_train(xyz, points, new_xyz, idx, use_xyz, xyz_last)   group_concat's new_points
+    group_concat_train_grad(grad_new_points, idx, N, C, col0)          -> grad_points (B, N, C)
+                         from columns [col0, col0 + C) of the gradient, read in place
+    fp_apply_train(dist, idx, points1, points2)         IDW weights of three_nn's dist, the
+                         interpolation of points2 and the concat [interp, points1]
+    fp_apply_train_grad(grad_out, dist, idx, m, C2, C1) -> (grad_points2 (B, m, C2),
+                         grad_points1 (B, n, C1)); bit-equal to the reference's CPU
+                         ThreeInterpolateGrad loop
 """
 import importlib
 
@@ -63,7 +76,8 @@ NAMES = ("farthest_point_sample", "farthest_point_sample_and_gather", "gather_po
          "three_interpolate_grad", "idw_weights", "fp_fused", "attn_reduce", "attn_reduce_grad",
          "group_pool", "mlp_layer_train", "mlp_layer_train_grad", "mlp_layer_train_pool",
          "mlp_layer_train_pool_grad", "attn_kv_train", "attn_kv_train_grad", "bn_train",
-         "bn_train_grad", "dropout", "softmax_xent", "softmax_xent_grad")
+         "bn_train_grad", "dropout", "softmax_xent", "softmax_xent_grad", "group_concat_train",
+         "group_concat_train_grad", "fp_apply_train", "fp_apply_train_grad")
 for _n in NAMES:
     globals()[_n] = getattr(_ops, _n)
 

@@ -127,6 +127,10 @@ SIGNATURES = {
     "pn2cpu_three_nn": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "pn2cpu_three_interpolate": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "pn2cpu_three_interpolate_grad": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "pn2_inverse_index_size": (_S, [_I, _I, _I]),
+    "pn2_inverse_index_build": (_I, [_P, _I, _I, _I, _P, _S, _P]),
+    "pn2_group_point_grad_ordered": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "pn2_three_interpolate_grad_ordered": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "pn2_fp_fused_layers": (_I, [_P, _I, _I, _P]),
     "pn2_fp_fused": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
     "pn2_attn_reduce": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),

@@ -10,7 +10,9 @@ pool over nsample: x, weight, bias, gamma, beta; csrc/mlp_train.hip), the traini
 layer (attn_kv_train: x and the three Dense layers' variables; csrc/attn_train.hip) and the
 stand-alone batch-statistics batch norm (bn_train: x, gamma, beta). The training head's ops
 (csrc/head_train.hip: dropout, the same op on the gradient with the same seed; softmax_xent,
-the logits only) carry their autograd in libpn2torch.so itself (csrc/torch_ops.cpp).
+the logits only) and the training-mode geometry ops (csrc/geom_train.hip: group_concat_train,
+the points only; fp_apply_train, points1 and points2) carry their autograd in libpn2torch.so
+itself (csrc/torch_ops.cpp).
 
 The mirror modules (tf_sampling, tf_grouping, tf_interpolate, attention_layer) call these ops
 for every reference-signature call; the pn2hip alias package re-exports them as pn2hip.ops.

@@ -300,9 +300,10 @@ Tensor group_point_grad_hip(const Tensor& points, const Tensor& idx_, const Tens
   return gp;
 }
 
-std::tuple<Tensor, Tensor> group_concat_hip(const Tensor& xyz_, const std::optional<Tensor>& points_,
-                                            const Tensor& new_xyz_, const Tensor& idx_, bool use_xyz,
-                                            bool xyz_last) {
+// (want_gx false: grouped_xyz is not written and comes back undefined)
+std::tuple<Tensor, Tensor> group_concat_impl(const Tensor& xyz_, const std::optional<Tensor>& points_,
+                                             const Tensor& new_xyz_, const Tensor& idx_, bool use_xyz,
+                                             bool xyz_last, bool want_gx) {
   chk_group_concat(xyz_, points_, new_xyz_, idx_);
   Tensor xyz = dev(xyz_, "xyz", at::kFloat), new_xyz = dev(new_xyz_, "new_xyz", at::kFloat);
   Tensor idx = dev(idx_, "idx", at::kInt);
@@ -312,13 +313,20 @@ std::tuple<Tensor, Tensor> group_concat_hip(const Tensor& xyz_, const std::optio
   const int B = I(xyz.size(0)), N = I(xyz.size(1)), M = I(idx.size(1)), ns = I(idx.size(2));
   const int C = points.defined() ? I(points.size(2)) : 0;
   const int cout = !points.defined() ? 3 : (use_xyz ? C + 3 : C);
-  Tensor gx = at::empty({B, M, ns, 3}, f32(xyz));
+  Tensor gx;
+  if (want_gx) gx = at::empty({B, M, ns, 3}, f32(xyz));
   Tensor np = at::empty({B, M, ns, cout}, f32(xyz));
   const int flags = (use_xyz ? PN2_USE_XYZ : 0) | (xyz_last ? PN2_XYZ_LAST : 0);
   check_rc(pn2_group_concat(F(xyz), F(points), F(new_xyz), Ii(idx), B, N, C, M, ns, flags,
-                            gx.data_ptr<float>(), np.data_ptr<float>(), stream_of(xyz)),
+                            want_gx ? gx.data_ptr<float>() : nullptr, np.data_ptr<float>(),
+                            stream_of(xyz)),
            "group_concat");
   return {gx, np};
+}
+std::tuple<Tensor, Tensor> group_concat_hip(const Tensor& xyz, const std::optional<Tensor>& points,
+                                            const Tensor& new_xyz, const Tensor& idx, bool use_xyz,
+                                            bool xyz_last) {
+  return group_concat_impl(xyz, points, new_xyz, idx, use_xyz, xyz_last, true);
 }
 
 std::tuple<Tensor, Tensor> three_nn_hip(const Tensor& xyz1_, const Tensor& xyz2_) {
@@ -995,6 +1003,109 @@ Tensor softmax_xent_grad_hip(const Tensor& grad_loss_, const Tensor& logits_, co
   return grad;
 }
 
+// ---- training-mode geometry (csrc/geom_train.hip): the fused forward kernels of the SA and FP
+// modules with their gradients as ordered gathers (no float atomics, no zero fill, no slices)
+void chk_group_concat_grad(const Tensor& grad, const Tensor& idx, int64_t N, int64_t C,
+                           int64_t col0) {
+  TORCH_CHECK_VALUE(grad.dim() == 4 && idx.dim() == 3 && grad.size(0) == idx.size(0) &&
+                        grad.size(1) == idx.size(1) && grad.size(2) == idx.size(2),
+                    "group_concat_train_grad expects grad_new_points (B,M,ns,Cout), idx (B,M,ns)");
+  TORCH_CHECK_VALUE(N >= 0 && C >= 0 && col0 >= 0 && col0 + C <= grad.size(3),
+                    "group_concat_train_grad expects columns [col0, col0 + C) inside Cout");
+}
+void chk_fp_apply_train(const Tensor& dist, const Tensor& idx, const std::optional<Tensor>& points1,
+                        const Tensor& points2) {
+  TORCH_CHECK_VALUE(dist.dim() == 3 && dist.size(2) == 3 && idx.dim() == 3 &&
+                        idx.sizes() == dist.sizes(),
+                    "fp_apply_train expects (b,n,3) dist and idx");
+  TORCH_CHECK_VALUE(points2.dim() == 3 && points2.size(0) == dist.size(0),
+                    "fp_apply_train expects (b,m,c2) points2");
+  if (points1.has_value() && points1->numel() > 0)
+    TORCH_CHECK_VALUE(points1->dim() == 3 && points1->size(0) == dist.size(0) &&
+                          points1->size(1) == dist.size(1),
+                      "fp_apply_train expects (b,n,c1) points1");
+}
+void chk_fp_apply_train_grad(const Tensor& grad_out, const Tensor& dist, const Tensor& idx,
+                             int64_t m, int64_t C2, int64_t C1) {
+  TORCH_CHECK_VALUE(dist.dim() == 3 && dist.size(2) == 3 && idx.dim() == 3 &&
+                        idx.sizes() == dist.sizes(),
+                    "fp_apply_train_grad expects (b,n,3) dist and idx");
+  TORCH_CHECK_VALUE(m >= 0 && C2 >= 0 && C1 >= 0 && grad_out.dim() == 3 &&
+                        grad_out.size(0) == dist.size(0) && grad_out.size(1) == dist.size(1) &&
+                        grad_out.size(2) == C2 + C1,
+                    "fp_apply_train_grad expects (b,n,C2+C1) grad_out");
+}
+
+// the inverse index of keys (B, S) over K rows per cloud (pn2_inverse_index_build)
+Tensor inverse_index(const Tensor& keys, int B, int S, int K, const char* op) {
+  const size_t bytes = pn2_inverse_index_size(B, S, K);
+  Tensor inv = workspace(keys, bytes);
+  check_rc(pn2_inverse_index_build(Ii(keys), B, S, K, P(inv), bytes, stream_of(keys)), op);
+  return inv;
+}
+
+Tensor group_concat_train_hip(const Tensor& xyz, const std::optional<Tensor>& points,
+                              const Tensor& new_xyz, const Tensor& idx, bool use_xyz,
+                              bool xyz_last) {
+  return std::get<1>(group_concat_impl(xyz, points, new_xyz, idx, use_xyz, xyz_last, false));
+}
+
+Tensor group_concat_train_grad_hip(const Tensor& grad_, const Tensor& idx_, int64_t N, int64_t C,
+                                   int64_t col0) {
+  const char* op = "group_concat_train_grad";
+  chk_group_concat_grad(grad_, idx_, N, C, col0);
+  Tensor grad = dev(grad_, "grad_new_points", at::kFloat), idx = dev(idx_, "idx", at::kInt);
+  c10::hip::HIPGuard g(grad.device().index());
+  const int B = I(idx.size(0)), M = I(idx.size(1)), ns = I(idx.size(2));
+  TORCH_CHECK_VALUE(idx.size(1) * idx.size(2) <= PN2_INV_MAX_SLOTS && N <= PN2_INV_MAX_KEYS, op,
+                    ": more slots or points per cloud than the inverse index takes");
+  Tensor gp = at::empty({B, N, C}, f32(grad));
+  if (gp.numel() == 0) return gp;
+  Tensor inv = inverse_index(idx, B, M * ns, I(N), op);
+  check_rc(pn2_group_point_grad_ordered(F(grad), I(grad.size(3)), I(col0), P(inv), B, I(N), I(C),
+                                        M, ns, gp.data_ptr<float>(), stream_of(grad)), op);
+  return gp;
+}
+
+Tensor fp_apply_train_hip(const Tensor& dist_, const Tensor& idx_,
+                          const std::optional<Tensor>& points1_, const Tensor& points2_) {
+  chk_fp_apply_train(dist_, idx_, points1_, points2_);
+  Tensor dist = dev(dist_, "dist", at::kFloat), idx = dev(idx_, "idx", at::kInt);
+  Tensor points2 = dev(points2_, "points2", at::kFloat);
+  Tensor points1;
+  if (points1_.has_value() && points1_->numel() > 0) points1 = dev(*points1_, "points1", at::kFloat);
+  c10::hip::HIPGuard g(dist.device().index());
+  const int B = I(dist.size(0)), n = I(dist.size(1)), m = I(points2.size(1));
+  const int C2 = I(points2.size(2)), C1 = points1.defined() ? I(points1.size(2)) : 0;
+  Tensor out = at::empty({B, n, C2 + C1}, f32(dist));
+  check_rc(pn2_fp_apply(F(dist), Ii(idx), nullptr, F(points1), C1, F(points2), C2, B, n, m,
+                        out.data_ptr<float>(), stream_of(dist)), "fp_apply_train");
+  return out;
+}
+
+std::tuple<Tensor, Tensor> fp_apply_train_grad_hip(const Tensor& grad_out_, const Tensor& dist_,
+                                                   const Tensor& idx_, int64_t m, int64_t C2,
+                                                   int64_t C1) {
+  const char* op = "fp_apply_train_grad";
+  chk_fp_apply_train_grad(grad_out_, dist_, idx_, m, C2, C1);
+  Tensor grad = dev(grad_out_, "grad_out", at::kFloat), dist = dev(dist_, "dist", at::kFloat);
+  Tensor idx = dev(idx_, "idx", at::kInt);
+  c10::hip::HIPGuard g(grad.device().index());
+  const int B = I(dist.size(0)), n = I(dist.size(1));
+  TORCH_CHECK_VALUE(3 * dist.size(1) <= PN2_INV_MAX_SLOTS && m <= PN2_INV_MAX_KEYS, op,
+                    ": more unknown or known points per cloud than the inverse index takes");
+  Tensor g1 = grad.narrow(2, C2, C1).contiguous();  // the points1 columns: one strided copy
+  Tensor g2 = at::empty({B, m, C2}, f32(grad));
+  if (g2.numel() == 0) return {g2, g1};
+  Tensor weight = at::empty_like(dist);  // the bits of pn2_idw_weights: the forward's weights
+  if (n > 0) check_rc(pn2_idw_weights(F(dist), B, n, weight.data_ptr<float>(), stream_of(grad)), op);
+  Tensor inv = inverse_index(idx, B, 3 * n, I(m), op);
+  check_rc(pn2_three_interpolate_grad_ordered(F(grad), I(C2 + C1), 0, P(inv), F(weight), B, n,
+                                              I(C2), I(m), g2.data_ptr<float>(), stream_of(grad)),
+           op);
+  return {g2, g1};
+}
+
 // ------------------------------------------------------------------------- CPU kernels
 // (the reference's CPU-only ops; host twins in csrc/cpu_interp.cpp)
 Tensor host(const Tensor& t, const char* name, at::ScalarType dt) {
@@ -1230,6 +1341,29 @@ Tensor softmax_xent_grad_meta(const Tensor& grad_loss, const Tensor& logits, con
   chk_xent_grad(grad_loss, logits, labels, weights, lse, num_present, "softmax_xent_grad");
   return at::empty(logits.sizes(), mf(logits));
 }
+Tensor group_concat_train_meta(const Tensor& xyz, const std::optional<Tensor>& points,
+                               const Tensor& new_xyz, const Tensor& idx, bool use_xyz,
+                               bool xyz_last) {
+  return std::get<1>(group_concat_meta(xyz, points, new_xyz, idx, use_xyz, xyz_last));
+}
+Tensor group_concat_train_grad_meta(const Tensor& grad, const Tensor& idx, int64_t N, int64_t C,
+                                    int64_t col0) {
+  chk_group_concat_grad(grad, idx, N, C, col0);
+  return at::empty({idx.size(0), N, C}, mf(grad));
+}
+Tensor fp_apply_train_meta(const Tensor& dist, const Tensor& idx,
+                           const std::optional<Tensor>& points1, const Tensor& points2) {
+  chk_fp_apply_train(dist, idx, points1, points2);
+  const int64_t C1 = (points1.has_value() && points1->numel() > 0) ? points1->size(2) : 0;
+  return at::empty({dist.size(0), dist.size(1), points2.size(2) + C1}, mf(dist));
+}
+std::tuple<Tensor, Tensor> fp_apply_train_grad_meta(const Tensor& grad_out, const Tensor& dist,
+                                                    const Tensor& idx, int64_t m, int64_t C2,
+                                                    int64_t C1) {
+  chk_fp_apply_train_grad(grad_out, dist, idx, m, C2, C1);
+  return {at::empty({dist.size(0), m, C2}, mf(grad_out)),
+          at::empty({dist.size(0), dist.size(1), C1}, mf(grad_out))};
+}
 
 // ------------------------------------------------------------------------- autograd (C++)
 // The two ops of the training head carry their autograd here instead of in _torch_ops.py: the
@@ -1298,6 +1432,92 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> softmax_xent_autograd(
   return {o[0], o[1], o[2], o[3]};
 }
 
+// The training-mode geometry ops (csrc/geom_train.hip) likewise: `points` (group_concat_train),
+// `points1` and `points2` (fp_apply_train) get gradients, the coordinates, distances and indices
+// none (pointnet_util keeps the composition of reference ops when xyz asks for one).
+struct GroupConcatTrainFn : public torch::autograd::Function<GroupConcatTrainFn> {
+  static Tensor forward(AutogradContext* ctx, const Tensor& xyz,
+                        const std::optional<Tensor>& points, const Tensor& new_xyz,
+                        const Tensor& idx, bool use_xyz, bool xyz_last) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    const bool has_points = points.has_value() && points->defined() && points->numel() > 0;
+    ctx->saved_data["N"] = xyz.dim() == 3 ? xyz.size(1) : int64_t(0);
+    ctx->saved_data["C"] = has_points && points->dim() == 3 ? points->size(2) : int64_t(0);
+    ctx->saved_data["col0"] = int64_t(has_points && use_xyz && !xyz_last ? 3 : 0);
+    ctx->saved_data["has_points"] = has_points;
+    ctx->save_for_backward({idx});
+    static auto op = c10::Dispatcher::singleton()
+                         .findSchemaOrThrow("pn2::group_concat_train", "")
+                         .typed<Tensor(const Tensor&, const std::optional<Tensor>&, const Tensor&,
+                                       const Tensor&, bool, bool)>();
+    return op.call(xyz, points, new_xyz, idx, use_xyz, xyz_last);
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    variable_list out(6);
+    if (!grads[0].defined() || !ctx->saved_data["has_points"].toBool() ||
+        !ctx->needs_input_grad(1))
+      return out;
+    static auto op = c10::Dispatcher::singleton()
+                         .findSchemaOrThrow("pn2::group_concat_train_grad", "")
+                         .typed<Tensor(const Tensor&, const Tensor&, int64_t, int64_t, int64_t)>();
+    // (a gradient that is not contiguous is made so once; the kernel reads rows in place)
+    out[1] = op.call(grads[0].contiguous(), ctx->get_saved_variables()[0],
+                     ctx->saved_data["N"].toInt(), ctx->saved_data["C"].toInt(),
+                     ctx->saved_data["col0"].toInt());
+    return out;
+  }
+};
+Tensor group_concat_train_autograd(const Tensor& xyz, const std::optional<Tensor>& points,
+                                   const Tensor& new_xyz, const Tensor& idx, bool use_xyz,
+                                   bool xyz_last) {
+  return GroupConcatTrainFn::apply(xyz, points, new_xyz, idx, use_xyz, xyz_last);
+}
+
+struct FpApplyTrainFn : public torch::autograd::Function<FpApplyTrainFn> {
+  static Tensor forward(AutogradContext* ctx, const Tensor& dist, const Tensor& idx,
+                        const std::optional<Tensor>& points1, const Tensor& points2) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    const bool has1 = points1.has_value() && points1->defined() && points1->numel() > 0;
+    ctx->saved_data["m"] = points2.dim() == 3 ? points2.size(1) : int64_t(0);
+    ctx->saved_data["C2"] = points2.dim() == 3 ? points2.size(2) : int64_t(0);
+    ctx->saved_data["C1"] = has1 && points1->dim() == 3 ? points1->size(2) : int64_t(0);
+    ctx->saved_data["has1"] = has1;
+    // (an absent optional tensor is no autograd input: points2's edge index moves down)
+    ctx->saved_data["p2_edge"] = int64_t(points1.has_value() && points1->defined() ? 3 : 2);
+    ctx->save_for_backward({dist, idx});
+    static auto op = c10::Dispatcher::singleton()
+                         .findSchemaOrThrow("pn2::fp_apply_train", "")
+                         .typed<Tensor(const Tensor&, const Tensor&, const std::optional<Tensor>&,
+                                       const Tensor&)>();
+    return op.call(dist, idx, points1, points2);
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    variable_list out(4);
+    if (!grads[0].defined()) return out;
+    const int64_t C2 = ctx->saved_data["C2"].toInt(), C1 = ctx->saved_data["C1"].toInt();
+    const bool need1 = ctx->saved_data["has1"].toBool() && ctx->needs_input_grad(2);
+    if (!ctx->needs_input_grad(ctx->saved_data["p2_edge"].toInt())) {  // points1 alone
+      if (need1) out[2] = grads[0].narrow(2, C2, C1).contiguous();
+      return out;
+    }
+    const variable_list saved = ctx->get_saved_variables();
+    static auto op = c10::Dispatcher::singleton()
+                         .findSchemaOrThrow("pn2::fp_apply_train_grad", "")
+                         .typed<std::tuple<Tensor, Tensor>(const Tensor&, const Tensor&,
+                                                           const Tensor&, int64_t, int64_t,
+                                                           int64_t)>();
+    auto [g2, g1] = op.call(grads[0].contiguous(), saved[0], saved[1],
+                            ctx->saved_data["m"].toInt(), C2, C1);
+    out[3] = g2;
+    if (need1) out[2] = g1;
+    return out;
+  }
+};
+Tensor fp_apply_train_autograd(const Tensor& dist, const Tensor& idx,
+                               const std::optional<Tensor>& points1, const Tensor& points2) {
+  return FpApplyTrainFn::apply(dist, idx, points1, points2);
+}
+
 }  // namespace
 
 // Schemas: the reference op names and argument order (tf_sampling.py, tf_grouping.py,
@@ -1349,6 +1569,13 @@ TORCH_LIBRARY(pn2, m) {
         "(Tensor loss, Tensor lse, Tensor pred, Tensor num_present)");
   m.def("softmax_xent_grad(Tensor grad_loss, Tensor logits, Tensor labels, Tensor? weights, "
         "Tensor lse, Tensor num_present) -> Tensor");
+  m.def("group_concat_train(Tensor xyz, Tensor? points, Tensor new_xyz, Tensor idx, bool use_xyz, "
+        "bool xyz_last) -> Tensor");
+  m.def("group_concat_train_grad(Tensor grad_new_points, Tensor idx, int N, int C, int col0) -> "
+        "Tensor");
+  m.def("fp_apply_train(Tensor dist, Tensor idx, Tensor? points1, Tensor points2) -> Tensor");
+  m.def("fp_apply_train_grad(Tensor grad_out, Tensor dist, Tensor idx, int m, int C2, int C1) -> "
+        "(Tensor, Tensor)");
 }
 
 // ROCm builds of PyTorch dispatch HIP tensors under the CUDA key.
@@ -1383,11 +1610,17 @@ TORCH_LIBRARY_IMPL(pn2, CUDA, m) {
   m.impl("dropout", &dropout_hip);
   m.impl("softmax_xent", &softmax_xent_hip);
   m.impl("softmax_xent_grad", &softmax_xent_grad_hip);
+  m.impl("group_concat_train", &group_concat_train_hip);
+  m.impl("group_concat_train_grad", &group_concat_train_grad_hip);
+  m.impl("fp_apply_train", &fp_apply_train_hip);
+  m.impl("fp_apply_train_grad", &fp_apply_train_grad_hip);
 }
 
 TORCH_LIBRARY_IMPL(pn2, Autograd, m) {
   m.impl("dropout", &dropout_autograd);
   m.impl("softmax_xent", &softmax_xent_autograd);
+  m.impl("group_concat_train", &group_concat_train_autograd);
+  m.impl("fp_apply_train", &fp_apply_train_autograd);
 }
 
 TORCH_LIBRARY_IMPL(pn2, CPU, m) {
@@ -1427,4 +1660,8 @@ TORCH_LIBRARY_IMPL(pn2, Meta, m) {
   m.impl("dropout", &dropout_meta);
   m.impl("softmax_xent", &softmax_xent_meta);
   m.impl("softmax_xent_grad", &softmax_xent_grad_meta);
+  m.impl("group_concat_train", &group_concat_train_meta);
+  m.impl("group_concat_train_grad", &group_concat_train_grad_meta);
+  m.impl("fp_apply_train", &fp_apply_train_meta);
+  m.impl("fp_apply_train_grad", &fp_apply_train_grad_meta);
 }

@@ -17,16 +17,19 @@ The whole layers, shared MLP included (tf_util.py for the par
   pointnet_sa_module_msg    pointnet_util.py:166-201  one fused kernel per scale
   pointnet_fp_module        pointnet_util.py:204-238  interpolation + MLP in one kernel
 
-Without autograd the fused kernels run (fewest launches, one pass over HBM); when a gradient
-is required, the composition of differentiable ops (gather_point, group_point,
-three_interpolate) is used instead so that backward reaches xyz and points like the
-reference's registered gradients.
+Without autograd the fused kernels run (fewest launches, one pass over HBM). When only features
+ask for a gradient (a training step), group_concat and fp_interpolate run the same fused
+kernels with an ordered-gather backward (torch.ops.pn2.group_concat_train / fp_apply_train,
+csrc/geom_train.hip: no float atomics, two runs give equal bits). When a coordinate tensor asks
+for one, the composition of differentiable ops (gather_point, group_point, three_interpolate)
+is used instead so that backward reaches xyz and points like the reference's registered
+gradients.
 """
 import ctypes
 
 import torch
 
-from . import tf_grouping, tf_interpolate, tf_sampling, tf_util
+from . import _torch_ops, tf_grouping, tf_interpolate, tf_sampling, tf_util
 from ._lib import (POOL_MODES, PN2_BQ_MAX_RADII, PN2_ENOTSUP, PN2_FP_MAX_LAYERS, PN2_POOL_NONE,
                    PN2_SA_MAX_LAYERS, PN2_USE_XYZ, PN2_XYZ_LAST, FpLayer, InvalidArgumentError,
                    SaLayer, check, device_tensor, lib, ptr, stream_of)
@@ -41,10 +44,17 @@ def _needs_grad(*ts):
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
 
 
-def group_concat(xyz, points, new_xyz, idx, use_xyz=True, xyz_last=False, want_grouped_xyz=True):
+def group_concat(xyz, points, new_xyz, idx, use_xyz=True, xyz_last=False, want_grouped_xyz=True,
+                 ordered_grad=True):
     """Fused group_point(xyz) - new_xyz, group_point(points) and concat
     (pointnet_util.py:39-56 SSG order [xyz, points]; xyz_last=True gives the MSG order
-    [points, xyz] of :191). Returns (new_points, grouped_xyz or None)."""
+    [points, xyz] of :191). Returns (new_points, grouped_xyz or None).
+
+    When only `points` asks for a gradient, the fused kernel runs here too
+    (torch.ops.pn2.group_concat_train) and its backward is the ordered gather of
+    csrc/geom_train.hip: the same forward bits, and gradients that two runs reproduce bit for
+    bit. A gradient for xyz or new_xyz (or ordered_grad=False) keeps the composition of the
+    reference's ops, whose grouping gradient is a float-atomic scatter."""
     B, N = int(xyz.shape[0]), int(xyz.shape[1])
     M, ns = int(idx.shape[1]), int(idx.shape[2])
     if _is_empty_points(points):
@@ -53,6 +63,18 @@ def group_concat(xyz, points, new_xyz, idx, use_xyz=True, xyz_last=False, want_g
         points = device_tensor(points, "points", torch.float32)
         C = int(points.shape[2])
         Cout = C + 3 if use_xyz else C
+    if ordered_grad and _needs_grad(points) and not _needs_grad(xyz, new_xyz):
+        new_points = _torch_ops.call("group_concat_train", xyz, points, new_xyz, idx, use_xyz,
+                                     xyz_last)
+        grouped_xyz = None
+        if want_grouped_xyz and use_xyz:
+            # the centred coordinates are columns of new_points (no gradient reaches them)
+            grouped_xyz = new_points.detach()[..., C:] if xyz_last else new_points.detach()[..., :3]
+        elif want_grouped_xyz:
+            grouped_xyz = torch.empty((B, M, ns, 3), dtype=torch.float32, device=xyz.device)
+            check(lib().pn2_group_concat(ptr(xyz), None, ptr(new_xyz), ptr(idx), B, N, 0, M, ns, 0,
+                                         None, ptr(grouped_xyz), stream_of(xyz)), "group_concat")
+        return new_points, grouped_xyz
     if _needs_grad(xyz, points, new_xyz):
         grouped_xyz = tf_grouping.group_point(xyz, idx) - new_xyz.unsqueeze(2)
         if points is None:
@@ -225,7 +247,9 @@ def sample_and_group(npoint, radius, nsample, xyz, points, knn=False, use_xyz=Tr
         _, idx = tf_grouping.knn_point(nsample, xyz, new_xyz.detach())
     else:
         idx, _ = tf_grouping.query_ball_point(radius, nsample, xyz, new_xyz.detach())
-    new_points, grouped_xyz = group_concat(xyz, points, new_xyz, idx, use_xyz=use_xyz)
+    # (the kNN grouping of the attention modules keeps the reference's composition)
+    new_points, grouped_xyz = group_concat(xyz, points, new_xyz, idx, use_xyz=use_xyz,
+                                           ordered_grad=not knn)
     return new_xyz, new_points, idx, grouped_xyz
 
 
@@ -297,6 +321,12 @@ def fp_interpolate(xyz1, xyz2, points1, points2, known_grid=None, unknown_grid=N
     xyz1 = device_tensor(xyz1, "xyz1", torch.float32)
     xyz2 = device_tensor(xyz2, "xyz2", torch.float32)
     points2 = device_tensor(points2, "points2", torch.float32)
+    if _needs_grad(points1, points2) and not _needs_grad(xyz1, xyz2):
+        # the fused interpolation kernel with an ordered-gather backward (csrc/geom_train.hip):
+        # today's forward bits, gradients that two runs reproduce bit for bit
+        dist, idx = tf_interpolate.three_nn(xyz1, xyz2, known_grid, unknown_grid)
+        out = _torch_ops.call("fp_apply_train", dist, idx, points1, points2)
+        return (out, (dist, idx)) if return_nn else out
     if _needs_grad(points1, points2):
         dist, idx = tf_interpolate.three_nn(xyz1, xyz2, known_grid, unknown_grid)
         weight = tf_interpolate.idw_weights(dist)
