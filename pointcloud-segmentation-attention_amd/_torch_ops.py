@@ -76,37 +76,23 @@ def _register_autograd():
         Q, K, V = ctx.saved_tensors
         return tuple(torch.ops.pn2.attn_reduce_grad(Q, K, V, grad.contiguous()))
 
-    def mlp_layer_setup(ctx, inputs, output):
+    def mlp_setup(ctx, inputs, output):
+        # mlp_layer_train returns (out, y, mean, var), mlp_layer_train_pool the pool's arg too
         x, weight, bias, gamma, beta, eps, relu = inputs
-        out, y, mean, var = output
-        ctx.mark_non_differentiable(y, mean, var)
-        ctx.save_for_backward(x, weight, y, mean, var, gamma, beta)
+        out, y, mean, var, *arg = output
+        ctx.mark_non_differentiable(y, mean, var, *arg)
+        ctx.save_for_backward(x, weight, y, mean, var, gamma, beta, *arg)
         ctx.eps, ctx.relu, ctx.has_bias = eps, relu, bias is not None
 
-    def mlp_layer_bwd(ctx, grad_out, *_):
-        x, weight, y, mean, var, gamma, beta = ctx.saved_tensors
-        # the input gradient is one more GEMM: skipped when nothing upstream needs it (SA1's
-        # first layer reads coordinates)
-        gx, gw, gb, gg, gbeta = torch.ops.pn2.mlp_layer_train_grad(
-            grad_out.contiguous(), x, weight, y, mean, var, gamma, beta, ctx.eps, ctx.relu,
-            ctx.needs_input_grad[0])
-        bn = gamma is not None
-        return (gx if ctx.needs_input_grad[0] else None, gw, gb if ctx.has_bias else None,
-                gg if bn else None, gbeta if bn else None, None, None)
-
-    def mlp_pool_setup(ctx, inputs, output):
-        x, weight, bias, gamma, beta, eps, relu = inputs
-        out, y, mean, var, arg = output
-        ctx.mark_non_differentiable(y, mean, var, arg)
-        ctx.save_for_backward(x, weight, y, mean, var, arg, gamma, beta)
-        ctx.eps, ctx.relu, ctx.has_bias = eps, relu, bias is not None
-
-    def mlp_pool_bwd(ctx, grad_out, *_):
-        # grad_out is (..., cout): the (..., ns, cout) gradient of the activation never exists
-        x, weight, y, mean, var, arg, gamma, beta = ctx.saved_tensors
-        gx, gw, gb, gg, gbeta = torch.ops.pn2.mlp_layer_train_pool_grad(
-            grad_out.contiguous(), arg, x, weight, y, mean, var, gamma, beta, ctx.eps, ctx.relu,
-            ctx.needs_input_grad[0])
+    def mlp_bwd(ctx, grad_out, *_):
+        x, weight, y, mean, var, gamma, beta, *arg = ctx.saved_tensors
+        # pooled, grad_out is (..., cout): the (..., ns, cout) gradient of the activation never
+        # exists. The input gradient is one more GEMM: skipped when nothing upstream needs it
+        # (SA1's first layer reads coordinates)
+        pn2 = torch.ops.pn2
+        grad = pn2.mlp_layer_train_pool_grad if arg else pn2.mlp_layer_train_grad
+        gx, gw, gb, gg, gbeta = grad(grad_out.contiguous(), *arg, x, weight, y, mean, var, gamma,
+                                     beta, ctx.eps, ctx.relu, ctx.needs_input_grad[0])
         bn = gamma is not None
         return (gx if ctx.needs_input_grad[0] else None, gw, gb if ctx.has_bias else None,
                 gg if bn else None, gbeta if bn else None, None, None)
@@ -142,8 +128,8 @@ def _register_autograd():
 
     reg("pn2::attn_kv_train", attn_kv_bwd, setup_context=attn_kv_setup)
     reg("pn2::bn_train", bn_bwd, setup_context=bn_setup)
-    reg("pn2::mlp_layer_train", mlp_layer_bwd, setup_context=mlp_layer_setup)
-    reg("pn2::mlp_layer_train_pool", mlp_pool_bwd, setup_context=mlp_pool_setup)
+    reg("pn2::mlp_layer_train", mlp_bwd, setup_context=mlp_setup)
+    reg("pn2::mlp_layer_train_pool", mlp_bwd, setup_context=mlp_setup)
     reg("pn2::gather_point", gather_bwd, setup_context=save_all)
     reg("pn2::group_point", group_bwd, setup_context=save_all)
     reg("pn2::three_interpolate", interp_bwd, setup_context=save_all)

@@ -24,13 +24,13 @@
 // order: two runs give equal bits.
 //
 // Also here: pn2_attn_dx_scatter (the query row's and the max pool's gradients added into
-// grad_x at G x C elements) and pn2_col_sum (the bias gradients: a two-stage ordered column sum
-// that writes no rows-sized tensor).
+// grad_x at G x C elements). The bias gradients are pn2_col_sum (mlp_train.hip).
 #include <math.h>
 
 #include <initializer_list>
 
 #include "attn_dev.h"
+#include "chan_rows.h"
 #include "common.h"
 
 namespace pn2 {
@@ -43,14 +43,6 @@ constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kFwdTif = 2;
 constexpr int kBlocksPerCu = 8;
 constexpr int kGenericBlocksPerCu = 16;
-// column sum / scatter: the per-channel layout of mlp_train.hip
-constexpr int kCols = 32;
-constexpr int kRowLanes = kBlock / kCols;
-constexpr int kBatch = 8;
-constexpr int kStep = kRowLanes * kBatch;
-constexpr int kSumRows = PN2_BN_BLOCK_ROWS;  // rows per stage-1 partial
-constexpr long long kMaxRows = 0x7fffffffLL;
-constexpr int kMaxC = 65535 * kCols;
 constexpr long long kScatterMaxBlocks = 256LL * 16;
 
 // Where pseudo-key f4 (in float4 units of the group's flat K matrix) lives in the group's
@@ -349,56 +341,6 @@ __global__ __launch_bounds__(kBlock) void attn_dx_scatter_kernel(
   }
 }
 
-// ---------------------------------------------------------------- column sum -------------
-// stage 1: part[blk * C + c] = sum of x[r][c] over the kSumRows rows of block blk (the layout and
-// order of mlp_train.hip's bn_bwd_partial); stage 2: the blocks in double, in bn_bwd_final's order.
-__global__ __launch_bounds__(kBlock) void col_sum_partial(const float* __restrict__ x,
-                                                          long long rows, int C,
-                                                          float* __restrict__ part) {
-  __shared__ float sh[kRowLanes][kCols];
-  const int cl = threadIdx.x & (kCols - 1), rl = threadIdx.x / kCols;
-  const int c = blockIdx.y * kCols + cl;
-  const long long r0 = (long long)blockIdx.x * kSumRows;
-  const long long left = rows - r0;
-  const int nr = left < kSumRows ? (int)left : kSumRows;
-  float s = 0.f;
-  if (c < C) {
-    const float* p = x + r0 * C + c;
-    for (int base = 0; base + rl < nr; base += kStep) {
-      float v[kBatch];
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) {
-        const int r = base + rl + kRowLanes * u;
-        v[u] = r < nr ? p[(long long)r * C] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) s += v[u];
-    }
-  }
-  sh[rl][cl] = s;
-  __syncthreads();
-  if (rl == 0 && c < C) {
-    for (int k = 1; k < kRowLanes; ++k) s += sh[k][cl];
-    part[(size_t)blockIdx.x * C + c] = s;
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void col_sum_final(const float* __restrict__ part, int C,
-                                                        int nblk, float* __restrict__ out) {
-  __shared__ double sh[kRowLanes][kCols];
-  const int cl = threadIdx.x & (kCols - 1), g = threadIdx.x / kCols;
-  const int c = blockIdx.x * kCols + cl;
-  double s = 0.0;
-  if (c < C)
-    for (int b = g; b < nblk; b += kRowLanes) s += (double)part[(size_t)b * C + c];
-  sh[g][cl] = s;
-  __syncthreads();
-  if (g == 0 && c < C) {
-    for (int k = 1; k < kRowLanes; ++k) s += sh[k][cl];
-    out[c] = (float)s;
-  }
-}
-
 // ---------------------------------------------------------------- launchers --------------
 unsigned grid_for(long long waves, int per_cu) {
   long long blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
@@ -518,31 +460,13 @@ int pn2_attn_dx_scatter(float* grad_x, const float* grad_xq, const float* grad_p
   if (G < 0 || ns <= 0 || C < 0) return PN2_EINVAL;
   if ((grad_pmax != nullptr) != (arg != nullptr)) return PN2_EINVAL;
   if (G == 0 || C == 0) return PN2_OK;
+  using chan_rows::kMaxRows;
   if (!grad_x || !grad_xq || G > kMaxRows || G * ns > kMaxRows) return PN2_EINVAL;
   const long long n = G * C;
   long long blocks = (n + kBlock - 1) / kBlock;
   if (blocks > kScatterMaxBlocks) blocks = kScatterMaxBlocks;  // grid-stride beyond
   hipLaunchKernelGGL(attn_dx_scatter_kernel, dim3((unsigned)blocks), dim3(kBlock), 0,
                      (hipStream_t)stream, grad_x, grad_xq, grad_pmax, arg, n, ns, C);
-  PN2_RETURN_LAUNCH();
-}
-
-size_t pn2_col_sum_workspace_size(long long rows, int C) {
-  if (rows <= 0 || C <= 0) return 0;
-  return (size_t)((rows + pn2::kSumRows - 1) / pn2::kSumRows) * (size_t)C * sizeof(float);
-}
-
-int pn2_col_sum(const float* x, long long rows, int C, float* out, void* workspace,
-                size_t workspace_bytes, pn2_stream_t stream) {
-  using namespace pn2;
-  if (rows <= 0 || C <= 0 || rows > kMaxRows || C > kMaxC) return PN2_EINVAL;
-  if (!x || !out || !workspace) return PN2_EINVAL;
-  if (workspace_bytes < pn2_col_sum_workspace_size(rows, C)) return PN2_EINVAL;
-  const int nblk = (int)((rows + kSumRows - 1) / kSumRows), ct = (C + kCols - 1) / kCols;
-  float* part = static_cast<float*>(workspace);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(col_sum_partial, dim3(nblk, ct), dim3(kBlock), 0, s, x, rows, C, part);
-  hipLaunchKernelGGL(col_sum_final, dim3(ct), dim3(kBlock), 0, s, part, C, nblk, out);
   PN2_RETURN_LAUNCH();
 }
 

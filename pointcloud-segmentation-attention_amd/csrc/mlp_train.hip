@@ -12,14 +12,14 @@
 //              out, arg = max_j act(bn(y))                        pn2_bn_act_pool_fwd
 //              grad_y, grad_gamma, grad_beta from (groups, C) grad_out  pn2_bn_act_pool_bwd
 //
+//   column sum (the attention layer's bias gradients): out = sum_r x[r]   pn2_col_sum
+//
 // Reductions are two-stage and ordered: stage 1 writes one partial per workgroup, stage 2
 // combines the partials in a fixed order in double precision. No floating-point atomics, so
 // two runs give the same bits.
 //
-// Per-channel kernels (stats, activation, its backward) share one layout: a workgroup owns 32
-// channels and a block of rows; thread (cl = tid & 31, rl = tid >> 5) walks rows rl, rl + 8,
-// ... of channel cl, eight rows per step (eight independent loads), so a wave's load covers
-// two 128-byte row segments and the channel's constants stay in registers.
+// Per-channel kernels (stats, activation, its backward, the pooled pair, the column sum) share
+// the layout, the batch-norm element expressions and the ordered sum of chan_rows.h.
 //
 // pn2_mlp_wgrad: v_mfma_f32_32x32x2_f32 takes A[i = lane & 31][k = lane >> 5] and
 // B[k = lane >> 5][j = lane & 31]; with i = input channel, j = output channel and k = row, a
@@ -27,6 +27,7 @@
 // grad_y[r + (lane >> 5)][co0 + (lane & 31)]: two row segments straight from the row-major
 // tensors, no transpose. The four waves of a workgroup interleave the row pairs of a slab and
 // their accumulators are added through LDS in wave order.
+#include "chan_rows.h"
 #include "common.h"
 
 namespace pn2 {
@@ -34,26 +35,14 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kBlock = 256;
-constexpr int kCols = 32;                    // channels per workgroup
-constexpr int kRowLanes = kBlock / kCols;    // 8
-constexpr int kBatch = 8;                    // rows per thread per step
-constexpr int kStep = kRowLanes * kBatch;    // 64 rows per workgroup step
-constexpr int kStatRows = PN2_BN_BLOCK_ROWS;  // rows per stage-1 partial (stats, bwd sums)
+using namespace chan_rows;
+
+constexpr int kStatRows = PN2_BN_BLOCK_ROWS;  // rows per stage-1 partial (stats, sums)
 constexpr int kActRows = 256;                 // rows per workgroup of the element-wise passes
 constexpr int kPoolGroups = PN2_BN_POOL_BLOCK_GROUPS;  // groups per stage-1 partial (pool bwd)
 constexpr int kPoolSplit = 64;                // above this ns a group is split across row lanes
 constexpr int kSlab = PN2_WGRAD_SLAB_ROWS;
 constexpr int kTile = 32 * 32;
-
-// gamma / sqrt(var + eps) and the pre-activation, written once: the forward pass and the
-// backward mask must round identically.
-PN2_DEV float bn_scale(float gamma, float var, float eps) {
-  return __fdiv_rn(gamma, __fsqrt_rn(__fadd_rn(var, eps)));
-}
-PN2_DEV float bn_pre(float y, float mean, float s, float beta) {
-  return __fadd_rn(__fmul_rn(__fsub_rn(y, mean), s), beta);
-}
 
 // Chan et al.: (na, ma, M2a) <- (na, ma, M2a) + (nb, mb, M2b)
 template <typename T>
@@ -67,19 +56,14 @@ PN2_DEV void chan_merge(T& na, T& ma, T& M2a, T nb, T mb, T M2b) {
   na = n;
 }
 
-PN2_DEV int block_rows(long long rows, long long r0, int per) {
-  const long long left = rows - r0;
-  return left < per ? (int)left : per;
-}
-
 // ---------------------------------------------------------------- batch statistics ------
 // stage 1: part[(blk * 2 + 0) * C + c] = mean, [(blk * 2 + 1) * C + c] = M2 of block blk
 __global__ __launch_bounds__(kBlock) void bn_stats_partial(const float* __restrict__ y,
                                                            long long rows, int C,
                                                            float* __restrict__ part) {
   __shared__ float sh[3][kRowLanes][kCols];
-  const int cl = threadIdx.x & (kCols - 1), rl = threadIdx.x / kCols;
-  const int c = blockIdx.y * kCols + cl;
+  const Lane t = lane_of(blockIdx.y);
+  const int cl = t.cl, rl = t.rl, c = t.c;
   const long long r0 = (long long)blockIdx.x * kStatRows;
   const int nr = block_rows(rows, r0, kStatRows);
   float n = 0.f, mean = 0.f, m2 = 0.f;
@@ -87,23 +71,20 @@ __global__ __launch_bounds__(kBlock) void bn_stats_partial(const float* __restri
     const float* p = y + r0 * C + c;
     for (int base = 0; base + rl < nr; base += kStep) {
       float v[kBatch];
+      load_rows(v, p, C, base + rl, nr);
       int cnt = 0;
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) {
-        const int r = base + rl + kRowLanes * u;
-        const bool ok = r < nr;
-        v[u] = ok ? p[(long long)r * C] : 0.f;
-        cnt += ok ? 1 : 0;
-      }
       float s = 0.f;
 #pragma unroll
-      for (int u = 0; u < kBatch; ++u) s += v[u];
+      for (int u = 0; u < kBatch; ++u) {
+        cnt += step_row(base + rl, u) < nr ? 1 : 0;
+        s += v[u];
+      }
       const float mb = s / (float)cnt;
       float qb = 0.f;
 #pragma unroll
       for (int u = 0; u < kBatch; ++u) {
         const float d = v[u] - mb;
-        qb += (base + rl + kRowLanes * u < nr) ? d * d : 0.f;
+        qb += (step_row(base + rl, u) < nr) ? d * d : 0.f;
       }
       chan_merge(n, mean, m2, (float)cnt, mb, qb);
     }
@@ -126,8 +107,8 @@ __global__ __launch_bounds__(kBlock) void bn_stats_final(const float* __restrict
                                                          float* __restrict__ mean_out,
                                                          float* __restrict__ var_out) {
   __shared__ double sh[3][kRowLanes][kCols];
-  const int cl = threadIdx.x & (kCols - 1), g = threadIdx.x / kCols;
-  const int c = blockIdx.x * kCols + cl;
+  const Lane t = lane_of(blockIdx.x);
+  const int cl = t.cl, g = t.rl, c = t.c;
   double n = 0.0, mean = 0.0, m2 = 0.0;
   if (c < C) {
     for (int b = g; b < nblk; b += kRowLanes) {
@@ -149,164 +130,108 @@ __global__ __launch_bounds__(kBlock) void bn_stats_final(const float* __restrict
 
 // ---------------------------------------------------------------- activation forward ----
 template <bool BN>
-__global__ __launch_bounds__(kBlock) void bn_act_fwd_kernel(
-    const float* __restrict__ y, long long rows, int C, const float* __restrict__ mean,
-    const float* __restrict__ var, const float* __restrict__ gamma,
-    const float* __restrict__ beta, float eps, int relu, float* __restrict__ out) {
-  const int cl = threadIdx.x & (kCols - 1), rl = threadIdx.x / kCols;
-  const int c = blockIdx.y * kCols + cl;
-  if (c >= C) return;
+__global__ __launch_bounds__(kBlock) void bn_act_fwd_kernel(const float* __restrict__ y,
+                                                            long long rows, int C, BnArgs bn,
+                                                            int relu, float* __restrict__ out) {
+  const Lane t = lane_of(blockIdx.y);
+  if (t.c >= C) return;
   const long long r0 = (long long)blockIdx.x * kActRows;
   const int nr = block_rows(rows, r0, kActRows);
-  float m = 0.f, s = 1.f, b = 0.f;
-  if (BN) {
-    m = mean[c];
-    s = bn_scale(gamma[c], var[c], eps);
-    b = beta[c];
-  }
-  const float* p = y + r0 * C + c;
-  float* o = out + r0 * C + c;
-  for (int base = 0; base + rl < nr; base += kStep) {
+  const BnConsts k = bn_consts<BN>(t.c, bn);
+  const float* p = y + r0 * C + t.c;
+  float* o = out + r0 * C + t.c;
+  for (int base = 0; base + t.rl < nr; base += kStep) {
     float v[kBatch];
+    load_rows(v, p, C, base + t.rl, nr);
 #pragma unroll
     for (int u = 0; u < kBatch; ++u) {
-      const int r = base + rl + kRowLanes * u;
-      v[u] = r < nr ? p[(long long)r * C] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < kBatch; ++u) {
-      const int r = base + rl + kRowLanes * u;
-      const float pre = BN ? bn_pre(v[u], m, s, b) : v[u];
-      if (r < nr) o[(long long)r * C] = relu ? fmaxf(pre, 0.f) : pre;
+      const int r = step_row(base + t.rl, u);
+      if (r < nr) o[(long long)r * C] = bn_act<BN>(k, v[u], relu);
     }
   }
 }
 
 // ---------------------------------------------------------------- activation backward ---
 // stage 1 of the sums: part[(blk * 2 + 0) * C + c] = sum dz, [(blk * 2 + 1) * C + c] =
-// sum dz * xhat over block blk. Without batch norm grad_y = dz is written here.
+// sum dz * xhat over block blk. Without batch norm grad_y = dz is written here. The second
+// launch bound is the occupancy the kernel is built for: the sixteen loads of a step fit 64
+// registers with batch norm (8 waves per SIMD) and 72 with the grad_y stores of the other path.
 template <bool BN>
-__global__ __launch_bounds__(kBlock) void bn_bwd_partial(
-    const float* __restrict__ go, const float* __restrict__ y, long long rows, int C,
-    const float* __restrict__ mean, const float* __restrict__ var,
-    const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int relu,
-    float* __restrict__ grad_y, float* __restrict__ part) {
-  __shared__ float sh[2][kRowLanes][kCols];
-  const int cl = threadIdx.x & (kCols - 1), rl = threadIdx.x / kCols;
-  const int c = blockIdx.y * kCols + cl;
+__global__ __launch_bounds__(kBlock, BN ? 8 : 7) void bn_bwd_partial(
+    const float* __restrict__ go, const float* __restrict__ y, long long rows, int C, BnArgs bn,
+    int relu, float* __restrict__ grad_y, float* __restrict__ part) {
+  const Lane t = lane_of(blockIdx.y);
   const long long r0 = (long long)blockIdx.x * kStatRows;
   const int nr = block_rows(rows, r0, kStatRows);
-  float db = 0.f, dg = 0.f;
-  if (c < C) {
-    float m = 0.f, s = 1.f, b = 0.f, rstd = 1.f;
-    if (BN) {
-      m = mean[c];
-      s = bn_scale(gamma[c], var[c], eps);
-      b = beta[c];
-      rstd = __fdiv_rn(1.f, __fsqrt_rn(__fadd_rn(var[c], eps)));
-    }
-    const float* py = y + r0 * C + c;
-    const float* pg = go + r0 * C + c;
-    float* pd = BN ? nullptr : grad_y + r0 * C + c;
+  float sum[2] = {0.f, 0.f};  // dz, dz * xhat
+  if (t.c < C) {
+    const BnConsts k = bn_consts<BN>(t.c, bn);
+    const float* py = y + r0 * C + t.c;
+    const float* pg = go + r0 * C + t.c;
+    float* pd = BN ? nullptr : grad_y + r0 * C + t.c;
     const bool need_y = BN || relu;  // no batch norm, no ReLU: grad_y = grad_out, y is not read
-    for (int base = 0; base + rl < nr; base += kStep) {
+    for (int base = 0; base + t.rl < nr; base += kStep) {
       float v[kBatch], g[kBatch];
+      load_rows(v, py, C, base + t.rl, nr, need_y);
+      load_rows(g, pg, C, base + t.rl, nr);
 #pragma unroll
       for (int u = 0; u < kBatch; ++u) {
-        const int r = base + rl + kRowLanes * u;
-        const bool ok = r < nr;
-        v[u] = (ok && need_y) ? py[(long long)r * C] : 0.f;
-        g[u] = ok ? pg[(long long)r * C] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) {
-        const int r = base + rl + kRowLanes * u;
-        const float pre = BN ? bn_pre(v[u], m, s, b) : v[u];
-        const float dz = (r < nr && (!relu || pre > 0.f)) ? g[u] : 0.f;
-        db += dz;
-        if (BN) dg += dz * ((v[u] - m) * rstd);
+        const int r = step_row(base + t.rl, u);
+        const float dz = bn_dz<BN>(k, v[u], r < nr, g[u], relu);
+        sum[0] += dz;
+        if (BN) sum[1] += dz * bn_xhat(k, v[u]);
         else if (r < nr) pd[(long long)r * C] = dz;
       }
     }
   }
-  sh[0][rl][cl] = db;
-  sh[1][rl][cl] = dg;
-  __syncthreads();
-  if (rl == 0 && c < C) {
-    for (int k = 1; k < kRowLanes; ++k) {
-      db += sh[0][k][cl];
-      dg += sh[1][k][cl];
-    }
-    part[((size_t)blockIdx.x * 2 + 0) * C + c] = db;
-    part[((size_t)blockIdx.x * 2 + 1) * C + c] = dg;
-  }
+  lane_sum_store(sum, t, C, part);
 }
 
-// stage 2: block sums added in double, in the order of bn_stats_final
-__global__ __launch_bounds__(kBlock) void bn_bwd_final(const float* __restrict__ part, int C,
-                                                       int nblk, float* __restrict__ grad_gamma,
-                                                       float* __restrict__ grad_beta) {
-  __shared__ double sh[2][kRowLanes][kCols];
-  const int cl = threadIdx.x & (kCols - 1), g = threadIdx.x / kCols;
-  const int c = blockIdx.x * kCols + cl;
-  double db = 0.0, dg = 0.0;
-  if (c < C) {
-    for (int b = g; b < nblk; b += kRowLanes) {
-      db += (double)part[((size_t)b * 2 + 0) * C + c];
-      dg += (double)part[((size_t)b * 2 + 1) * C + c];
-    }
-  }
-  sh[0][g][cl] = db;
-  sh[1][g][cl] = dg;
-  __syncthreads();
-  if (g == 0 && c < C) {
-    for (int k = 1; k < kRowLanes; ++k) {
-      db += sh[0][k][cl];
-      dg += sh[1][k][cl];
-    }
-    grad_beta[c] = (float)db;
-    if (grad_gamma) grad_gamma[c] = (float)dg;
-  }
-}
-
-// grad_y = gamma / sigma * (dz - grad_beta / R - xhat * grad_gamma / R)
+// grad_y of the apply pass (bn_apply), batch norm only: without it bn_bwd_partial wrote grad_y
 __global__ __launch_bounds__(kBlock) void bn_bwd_apply(
-    const float* __restrict__ go, const float* __restrict__ y, long long rows, int C,
-    const float* __restrict__ mean, const float* __restrict__ var,
-    const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int relu,
-    const float* __restrict__ grad_gamma, const float* __restrict__ grad_beta,
+    const float* __restrict__ go, const float* __restrict__ y, long long rows, int C, BnArgs bn,
+    int relu, const float* __restrict__ grad_gamma, const float* __restrict__ grad_beta,
     float* __restrict__ grad_y) {
-  const int cl = threadIdx.x & (kCols - 1), rl = threadIdx.x / kCols;
-  const int c = blockIdx.y * kCols + cl;
-  if (c >= C) return;
+  const Lane t = lane_of(blockIdx.y);
+  if (t.c >= C) return;
   const long long r0 = (long long)blockIdx.x * kActRows;
   const int nr = block_rows(rows, r0, kActRows);
-  const float m = mean[c], b = beta[c];
-  const float s = bn_scale(gamma[c], var[c], eps);
-  const float rstd = __fdiv_rn(1.f, __fsqrt_rn(__fadd_rn(var[c], eps)));
-  const float inv_rows = (float)(1.0 / (double)rows);
-  const float mb = grad_beta[c] * inv_rows, mg = grad_gamma[c] * inv_rows;
-  const float* py = y + r0 * C + c;
-  const float* pg = go + r0 * C + c;
-  float* pd = grad_y + r0 * C + c;
-  for (int base = 0; base + rl < nr; base += kStep) {
+  const BnConsts k = bn_apply_consts<true>(t.c, bn, rows, grad_gamma, grad_beta);
+  const float* py = y + r0 * C + t.c;
+  const float* pg = go + r0 * C + t.c;
+  float* pd = grad_y + r0 * C + t.c;
+  for (int base = 0; base + t.rl < nr; base += kStep) {
     float v[kBatch], g[kBatch];
+    load_rows(v, py, C, base + t.rl, nr);
+    load_rows(g, pg, C, base + t.rl, nr);
 #pragma unroll
     for (int u = 0; u < kBatch; ++u) {
-      const int r = base + rl + kRowLanes * u;
-      const bool ok = r < nr;
-      v[u] = ok ? py[(long long)r * C] : 0.f;
-      g[u] = ok ? pg[(long long)r * C] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < kBatch; ++u) {
-      const int r = base + rl + kRowLanes * u;
-      const float pre = bn_pre(v[u], m, s, b);
-      const float dz = (!relu || pre > 0.f) ? g[u] : 0.f;
-      const float xhat = (v[u] - m) * rstd;
-      if (r < nr) pd[(long long)r * C] = s * ((dz - mb) - xhat * mg);
+      const int r = step_row(base + t.rl, u);
+      if (r < nr) pd[(long long)r * C] = bn_apply<true>(k, v[u], true, g[u], relu);
     }
   }
+}
+
+// ---------------------------------------------------------------- column sum -------------
+// out[c] = sum of x[r][c] over the rows: stage 1 per block of kStatRows rows, stage 2
+// block_sum_final. It writes no rows-sized tensor (the attention layer's bias gradients).
+__global__ __launch_bounds__(kBlock) void col_sum_partial(const float* __restrict__ x,
+                                                          long long rows, int C,
+                                                          float* __restrict__ part) {
+  const Lane t = lane_of(blockIdx.y);
+  const long long r0 = (long long)blockIdx.x * kStatRows;
+  const int nr = block_rows(rows, r0, kStatRows);
+  float sum[1] = {0.f};
+  if (t.c < C) {
+    const float* p = x + r0 * C + t.c;
+    for (int base = 0; base + t.rl < nr; base += kStep) {
+      float v[kBatch];
+      load_rows(v, p, C, base + t.rl, nr);
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) sum[0] += v[u];
+    }
+  }
+  lane_sum_store(sum, t, C, part);
 }
 
 // ---------------------------------------------------------------- activation + max pool --
@@ -324,81 +249,58 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply(
 //     rl + 8, ... and the eight lanes' (value, j) pairs are combined through LDS by
 //     (value descending, j ascending). Parallelism is groups x channel tiles x 256 threads, so
 //     group_all (groups = B, ns = N) still fills the row lanes.
-PN2_DEV float pool_act(float pre, int relu) { return relu ? fmaxf(pre, 0.f) : pre; }
-
 template <bool BN>
 __global__ __launch_bounds__(kBlock) void bn_act_pool_fwd_groups(
-    const float* __restrict__ y, long long groups, int ns, int C, int gpt,
-    const float* __restrict__ mean, const float* __restrict__ var,
-    const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int relu,
+    const float* __restrict__ y, long long groups, int ns, int C, int gpt, BnArgs bn, int relu,
     float* __restrict__ out, int* __restrict__ arg) {
-  const int cl = threadIdx.x & (kCols - 1), rl = threadIdx.x / kCols;
-  const int c = blockIdx.y * kCols + cl;
-  if (c >= C) return;
-  float m = 0.f, s = 1.f, b = 0.f;
-  if (BN) {
-    m = mean[c];
-    s = bn_scale(gamma[c], var[c], eps);
-    b = beta[c];
-  }
+  const Lane t = lane_of(blockIdx.y);
+  if (t.c >= C) return;
+  const BnConsts k = bn_consts<BN>(t.c, bn);
   const long long g0 = (long long)blockIdx.x * (kRowLanes * gpt);
-  for (int t = 0; t < gpt; ++t) {
-    const long long g = g0 + rl + kRowLanes * t;
+  for (int i = 0; i < gpt; ++i) {
+    const long long g = g0 + t.rl + kRowLanes * i;
     if (g >= groups) break;
-    const float* p = y + g * ns * C + c;
+    const float* p = y + g * ns * C + t.c;
     float best = 0.f;
     int bj = 0;
     for (int base = 0; base < ns; base += kBatch) {
       float v[kBatch];
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) v[u] = base + u < ns ? p[(long long)(base + u) * C] : 0.f;
+      load_rows<1>(v, p, C, base, ns);
 #pragma unroll
       for (int u = 0; u < kBatch; ++u) {
-        const int j = base + u;
-        const float a = pool_act(BN ? bn_pre(v[u], m, s, b) : v[u], relu);
+        const int j = step_row<1>(base, u);
+        const float a = bn_act<BN>(k, v[u], relu);
         if (j < ns && (j == 0 || a > best)) {
           best = a;
           bj = j;
         }
       }
     }
-    out[g * C + c] = best;
-    arg[g * C + c] = bj;
+    out[g * C + t.c] = best;
+    arg[g * C + t.c] = bj;
   }
 }
 
 template <bool BN>
 __global__ __launch_bounds__(kBlock) void bn_act_pool_fwd_split(
-    const float* __restrict__ y, int ns, int C, const float* __restrict__ mean,
-    const float* __restrict__ var, const float* __restrict__ gamma,
-    const float* __restrict__ beta, float eps, int relu, float* __restrict__ out,
+    const float* __restrict__ y, int ns, int C, BnArgs bn, int relu, float* __restrict__ out,
     int* __restrict__ arg) {
   __shared__ float shv[kRowLanes][kCols];
   __shared__ int shj[kRowLanes][kCols];
-  const int cl = threadIdx.x & (kCols - 1), rl = threadIdx.x / kCols;
-  const int c = blockIdx.y * kCols + cl;
+  const Lane t = lane_of(blockIdx.y);
   const long long g = blockIdx.x;
   float best = 0.f;
   int bj = -1;  // no sample seen yet
-  if (c < C) {
-    float m = 0.f, s = 1.f, b = 0.f;
-    if (BN) {
-      m = mean[c];
-      s = bn_scale(gamma[c], var[c], eps);
-      b = beta[c];
-    }
-    const float* p = y + g * ns * C + c;
-    for (int base = 0; base + rl < ns; base += kStep) {
+  if (t.c < C) {
+    const BnConsts k = bn_consts<BN>(t.c, bn);
+    const float* p = y + g * ns * C + t.c;
+    for (int base = 0; base + t.rl < ns; base += kStep) {
       float v[kBatch];
+      load_rows(v, p, C, base + t.rl, ns);
 #pragma unroll
       for (int u = 0; u < kBatch; ++u) {
-        const int j = base + rl + kRowLanes * u;
-        v[u] = j < ns ? p[(long long)j * C] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) {
-        const int j = base + rl + kRowLanes * u;
-        const float a = pool_act(BN ? bn_pre(v[u], m, s, b) : v[u], relu);
+        const int j = step_row(base + t.rl, u);
+        const float a = bn_act<BN>(k, v[u], relu);
         if (j < ns && (bj < 0 || a > best)) {
           best = a;
           bj = j;
@@ -406,150 +308,90 @@ __global__ __launch_bounds__(kBlock) void bn_act_pool_fwd_split(
       }
     }
   }
-  shv[rl][cl] = best;
-  shj[rl][cl] = bj;
+  shv[t.rl][t.cl] = best;
+  shj[t.rl][t.cl] = bj;
   __syncthreads();
-  if (rl == 0 && c < C) {  // row lane 0 holds j = 0, so bj >= 0 here
-    for (int k = 1; k < kRowLanes; ++k) {
-      const float v = shv[k][cl];
-      const int j = shj[k][cl];
+  if (t.rl == 0 && t.c < C) {  // row lane 0 holds j = 0, so bj >= 0 here
+    for (int l = 1; l < kRowLanes; ++l) {
+      const float v = shv[l][t.cl];
+      const int j = shj[l][t.cl];
       if (j >= 0 && (v > best || (v == best && j < bj))) {
         best = v;
         bj = j;
       }
     }
-    out[g * C + c] = best;
-    arg[g * C + c] = bj;
+    out[g * C + t.c] = best;
+    arg[g * C + t.c] = bj;
   }
 }
 
 // backward, stage 1 of the sums: dz is grad_out[g][c] at j = arg[g][c] (masked by the
 // recomputed pre-activation) and 0 elsewhere, so the sums read one gathered y element per
 // (group, channel). part[(blk * 2 + 0) * C + c] = sum dz, [(blk * 2 + 1) * C + c] = sum dz *
-// xhat over the kPoolGroups groups of block blk; stage 2 is bn_bwd_final. An arg outside
+// xhat over the kPoolGroups groups of block blk; stage 2 is block_sum_final. An arg outside
 // [0, ns) selects nothing.
 template <bool BN>
 __global__ __launch_bounds__(kBlock) void bn_pool_bwd_partial(
     const float* __restrict__ go, const int* __restrict__ arg, const float* __restrict__ y,
-    long long groups, int ns, int C, const float* __restrict__ mean,
-    const float* __restrict__ var, const float* __restrict__ gamma,
-    const float* __restrict__ beta, float eps, int relu, float* __restrict__ part) {
-  __shared__ float sh[2][kRowLanes][kCols];
-  const int cl = threadIdx.x & (kCols - 1), rl = threadIdx.x / kCols;
-  const int c = blockIdx.y * kCols + cl;
+    long long groups, int ns, int C, BnArgs bn, int relu, float* __restrict__ part) {
+  const Lane t = lane_of(blockIdx.y);
   const long long g0 = (long long)blockIdx.x * kPoolGroups;
   const int ng = block_rows(groups, g0, kPoolGroups);
-  float db = 0.f, dg = 0.f;
-  if (c < C) {
-    float m = 0.f, s = 1.f, b = 0.f, rstd = 1.f;
-    if (BN) {
-      m = mean[c];
-      s = bn_scale(gamma[c], var[c], eps);
-      b = beta[c];
-      rstd = __fdiv_rn(1.f, __fsqrt_rn(__fadd_rn(var[c], eps)));
-    }
+  float sum[2] = {0.f, 0.f};  // dz, dz * xhat
+  if (t.c < C) {
+    const BnConsts k = bn_consts<BN>(t.c, bn);
     const bool need_y = BN || relu;
-    for (int base = 0; base + rl < ng; base += kStep) {
+    for (int base = 0; base + t.rl < ng; base += kStep) {
       float v[kBatch], gr[kBatch];
       int a[kBatch];
       bool ok[kBatch];
+      load_rows(a, arg + g0 * C + t.c, C, base + t.rl, ng, true, -1);
+      load_rows(gr, go + g0 * C + t.c, C, base + t.rl, ng);
 #pragma unroll
       for (int u = 0; u < kBatch; ++u) {
-        const int r = base + rl + kRowLanes * u;
-        const bool in = r < ng;
-        a[u] = in ? arg[(g0 + r) * C + c] : -1;
-        gr[u] = in ? go[(g0 + r) * C + c] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) {
-        const int r = base + rl + kRowLanes * u;
+        const int r = step_row(base + t.rl, u);
         ok[u] = a[u] >= 0 && a[u] < ns;
-        v[u] = (ok[u] && need_y) ? y[((g0 + r) * ns + a[u]) * C + c] : 0.f;
+        v[u] = (ok[u] && need_y) ? y[((g0 + r) * ns + a[u]) * C + t.c] : 0.f;
       }
 #pragma unroll
       for (int u = 0; u < kBatch; ++u) {
-        const float pre = BN ? bn_pre(v[u], m, s, b) : v[u];
-        const float dz = (ok[u] && (!relu || pre > 0.f)) ? gr[u] : 0.f;
-        db += dz;
-        if (BN) dg += dz * ((v[u] - m) * rstd);
+        const float dz = bn_dz<BN>(k, v[u], ok[u], gr[u], relu);
+        sum[0] += dz;
+        if (BN) sum[1] += dz * bn_xhat(k, v[u]);
       }
     }
   }
-  sh[0][rl][cl] = db;
-  sh[1][rl][cl] = dg;
-  __syncthreads();
-  if (rl == 0 && c < C) {
-    for (int k = 1; k < kRowLanes; ++k) {
-      db += sh[0][k][cl];
-      dg += sh[1][k][cl];
-    }
-    part[((size_t)blockIdx.x * 2 + 0) * C + c] = db;
-    part[((size_t)blockIdx.x * 2 + 1) * C + c] = dg;
-  }
+  lane_sum_store(sum, t, C, part);
 }
 
-// per-channel constants of the apply pass and its element: bn_bwd_apply's expression with dz
-// non-zero only at j = arg; without batch norm grad_y = dz
-struct PoolApply {
-  float m, s, b, rstd, mb, mg;
-};
-template <bool BN>
-PN2_DEV PoolApply pool_apply_consts(int c, long long rows, const float* mean, const float* var,
-                                    const float* gamma, const float* beta, float eps,
-                                    const float* grad_gamma, const float* grad_beta) {
-  PoolApply k = {0.f, 1.f, 0.f, 1.f, 0.f, 0.f};
-  if (BN) {
-    k.m = mean[c];
-    k.b = beta[c];
-    k.s = bn_scale(gamma[c], var[c], eps);
-    k.rstd = __fdiv_rn(1.f, __fsqrt_rn(__fadd_rn(var[c], eps)));
-    const float inv_rows = (float)(1.0 / (double)rows);
-    k.mb = grad_beta[c] * inv_rows;
-    k.mg = grad_gamma[c] * inv_rows;
-  }
-  return k;
-}
-template <bool BN>
-PN2_DEV float pool_apply(const PoolApply& k, float v, bool hit, float g, int relu) {
-  const float pre = BN ? bn_pre(v, k.m, k.s, k.b) : v;
-  const float dz = (hit && (!relu || pre > 0.f)) ? g : 0.f;
-  if (!BN) return dz;
-  const float xhat = (v - k.m) * k.rstd;
-  return k.s * ((dz - k.mb) - xhat * k.mg);
-}
-
-// backward, apply pass, the forward's two layouts. split: blockIdx.x = group * nchunk + chunk
-// of kActRows samples (no combine here, so a group may span workgroups).
+// backward, apply pass (bn_apply with dz non-zero only at j = arg), the forward's two layouts.
+// split: blockIdx.x = group * nchunk + chunk of kActRows samples (no combine here, so a group
+// may span workgroups).
 template <bool BN>
 __global__ __launch_bounds__(kBlock) void bn_pool_bwd_apply_groups(
     const float* __restrict__ go, const int* __restrict__ arg, const float* __restrict__ y,
-    long long groups, int ns, int C, int gpt, const float* __restrict__ mean,
-    const float* __restrict__ var, const float* __restrict__ gamma,
-    const float* __restrict__ beta, float eps, int relu, const float* __restrict__ grad_gamma,
-    const float* __restrict__ grad_beta, float* __restrict__ grad_y) {
-  const int cl = threadIdx.x & (kCols - 1), rl = threadIdx.x / kCols;
-  const int c = blockIdx.y * kCols + cl;
-  if (c >= C) return;
-  const PoolApply k = pool_apply_consts<BN>(c, groups * ns, mean, var, gamma, beta, eps,
-                                            grad_gamma, grad_beta);
+    long long groups, int ns, int C, int gpt, BnArgs bn, int relu,
+    const float* __restrict__ grad_gamma, const float* __restrict__ grad_beta,
+    float* __restrict__ grad_y) {
+  const Lane t = lane_of(blockIdx.y);
+  if (t.c >= C) return;
+  const BnConsts k = bn_apply_consts<BN>(t.c, bn, groups * ns, grad_gamma, grad_beta);
   const bool need_y = BN || relu;
   const long long g0 = (long long)blockIdx.x * (kRowLanes * gpt);
-  for (int t = 0; t < gpt; ++t) {
-    const long long g = g0 + rl + kRowLanes * t;
+  for (int i = 0; i < gpt; ++i) {
+    const long long g = g0 + t.rl + kRowLanes * i;
     if (g >= groups) break;
-    const float gr = go[g * C + c];
-    const int a = arg[g * C + c];
-    const float* p = y + g * ns * C + c;
-    float* pd = grad_y + g * ns * C + c;
+    const float gr = go[g * C + t.c];
+    const int a = arg[g * C + t.c];
+    const float* p = y + g * ns * C + t.c;
+    float* pd = grad_y + g * ns * C + t.c;
     for (int base = 0; base < ns; base += kBatch) {
       float v[kBatch];
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u)
-        v[u] = (base + u < ns && need_y) ? p[(long long)(base + u) * C] : 0.f;
+      load_rows<1>(v, p, C, base, ns, need_y);
 #pragma unroll
       for (int u = 0; u < kBatch; ++u) {
-        const int j = base + u;
-        if (j < ns) pd[(long long)j * C] = pool_apply<BN>(k, v[u], j == a, gr, relu);
+        const int j = step_row<1>(base, u);
+        if (j < ns) pd[(long long)j * C] = bn_apply<BN>(k, v[u], j == a, gr, relu);
       }
     }
   }
@@ -558,34 +400,27 @@ __global__ __launch_bounds__(kBlock) void bn_pool_bwd_apply_groups(
 template <bool BN>
 __global__ __launch_bounds__(kBlock) void bn_pool_bwd_apply_split(
     const float* __restrict__ go, const int* __restrict__ arg, const float* __restrict__ y,
-    long long groups, int ns, int C, int nchunk, const float* __restrict__ mean,
-    const float* __restrict__ var, const float* __restrict__ gamma,
-    const float* __restrict__ beta, float eps, int relu, const float* __restrict__ grad_gamma,
-    const float* __restrict__ grad_beta, float* __restrict__ grad_y) {
-  const int cl = threadIdx.x & (kCols - 1), rl = threadIdx.x / kCols;
-  const int c = blockIdx.y * kCols + cl;
-  if (c >= C) return;
-  const PoolApply k = pool_apply_consts<BN>(c, groups * ns, mean, var, gamma, beta, eps,
-                                            grad_gamma, grad_beta);
+    long long groups, int ns, int C, int nchunk, BnArgs bn, int relu,
+    const float* __restrict__ grad_gamma, const float* __restrict__ grad_beta,
+    float* __restrict__ grad_y) {
+  const Lane t = lane_of(blockIdx.y);
+  if (t.c >= C) return;
+  const BnConsts k = bn_apply_consts<BN>(t.c, bn, groups * ns, grad_gamma, grad_beta);
   const bool need_y = BN || relu;
   const long long g = blockIdx.x / nchunk;
   const int j0 = (int)(blockIdx.x % nchunk) * kActRows;
   const int nr = block_rows(ns, j0, kActRows);
-  const float gr = go[g * C + c];
-  const int a = arg[g * C + c] - j0;  // the winner's row within this chunk, if it is here
-  const float* p = y + (g * ns + j0) * C + c;
-  float* pd = grad_y + (g * ns + j0) * C + c;
-  for (int base = 0; base + rl < nr; base += kStep) {
+  const float gr = go[g * C + t.c];
+  const int a = arg[g * C + t.c] - j0;  // the winner's row within this chunk, if it is here
+  const float* p = y + (g * ns + j0) * C + t.c;
+  float* pd = grad_y + (g * ns + j0) * C + t.c;
+  for (int base = 0; base + t.rl < nr; base += kStep) {
     float v[kBatch];
+    load_rows(v, p, C, base + t.rl, nr, need_y);
 #pragma unroll
     for (int u = 0; u < kBatch; ++u) {
-      const int r = base + rl + kRowLanes * u;
-      v[u] = (r < nr && need_y) ? p[(long long)r * C] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < kBatch; ++u) {
-      const int r = base + rl + kRowLanes * u;
-      if (r < nr) pd[(long long)r * C] = pool_apply<BN>(k, v[u], r == a, gr, relu);
+      const int r = step_row(base + t.rl, u);
+      if (r < nr) pd[(long long)r * C] = bn_apply<BN>(k, v[u], r == a, gr, relu);
     }
   }
 }
@@ -695,9 +530,23 @@ __global__ __launch_bounds__(kBlock) void wgrad_final(const float* __restrict__ 
 
 long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
 
-// rows of one launch: the row-block index is blockIdx.x (< 2^31), the channel tile blockIdx.y
-constexpr long long kMaxRows = 0x7fffffffLL;
-constexpr int kMaxC = 65535 * kCols;
+// The batch-norm pointer group: all four or none, eps >= 0 with them, and in a backward pass
+// (grad_gamma given) *grad_gamma present exactly when the group is.
+bool bn_args_ok(const BnArgs& bn, float* const* grad_gamma = nullptr) {
+  const int given = (bn.mean ? 1 : 0) + (bn.var ? 1 : 0) + (bn.gamma ? 1 : 0) + (bn.beta ? 1 : 0);
+  if (given != 0 && given != 4) return false;
+  if (grad_gamma && (given != 0) != (*grad_gamma != nullptr)) return false;
+  return !given || bn.eps >= 0.f;
+}
+
+// kernel<true> with the group, kernel<false> without it, on a kBlock-thread grid
+#define PN2_LAUNCH_BN(bn, kernel, grid, stream, ...)                                        \
+  do {                                                                                      \
+    if ((bn).mean)                                                                          \
+      hipLaunchKernelGGL(kernel<true>, grid, dim3(kBlock), 0, stream, __VA_ARGS__);         \
+    else                                                                                    \
+      hipLaunchKernelGGL(kernel<false>, grid, dim3(kBlock), 0, stream, __VA_ARGS__);        \
+  } while (0)
 
 int wgrad_parts(long long rows, int cin, int cout) {
   const long long ntiles = ceil_div(cin, 32) * ceil_div(cout, 32);
@@ -753,16 +602,11 @@ int pn2_bn_act_fwd(const float* y, long long rows, int C, const float* mean, con
                    pn2_stream_t stream) {
   using namespace pn2;
   if (rows <= 0 || C <= 0 || rows > kMaxRows || C > kMaxC || !y || !out) return PN2_EINVAL;
-  const int given = (mean ? 1 : 0) + (var ? 1 : 0) + (gamma ? 1 : 0) + (beta ? 1 : 0);
-  if (given != 0 && given != 4) return PN2_EINVAL;
-  if (given && !(eps >= 0.f)) return PN2_EINVAL;
+  const BnArgs bn = {mean, var, gamma, beta, eps};
+  if (!bn_args_ok(bn)) return PN2_EINVAL;
   const dim3 grid((unsigned)ceil_div(rows, kActRows), (unsigned)ceil_div(C, kCols));
-  if (given)
-    hipLaunchKernelGGL(bn_act_fwd_kernel<true>, grid, dim3(kBlock), 0, (hipStream_t)stream, y,
-                       rows, C, mean, var, gamma, beta, eps, relu ? 1 : 0, out);
-  else
-    hipLaunchKernelGGL(bn_act_fwd_kernel<false>, grid, dim3(kBlock), 0, (hipStream_t)stream, y,
-                       rows, C, mean, var, gamma, beta, eps, relu ? 1 : 0, out);
+  PN2_LAUNCH_BN(bn, bn_act_fwd_kernel, grid, (hipStream_t)stream, y, rows, C, bn, relu ? 1 : 0,
+                out);
   PN2_RETURN_LAUNCH();
 }
 
@@ -773,28 +617,19 @@ int pn2_bn_act_bwd(const float* grad_out, const float* y, long long rows, int C,
   using namespace pn2;
   if (rows <= 0 || C <= 0 || rows > kMaxRows || C > kMaxC) return PN2_EINVAL;
   if (!grad_out || !y || !grad_y || !grad_beta || !workspace) return PN2_EINVAL;
-  const int given = (mean ? 1 : 0) + (var ? 1 : 0) + (gamma ? 1 : 0) + (beta ? 1 : 0);
-  if (given != 0 && given != 4) return PN2_EINVAL;
-  if ((given != 0) != (grad_gamma != nullptr)) return PN2_EINVAL;
-  if (given && !(eps >= 0.f)) return PN2_EINVAL;
+  const BnArgs bn = {mean, var, gamma, beta, eps};
+  if (!bn_args_ok(bn, &grad_gamma)) return PN2_EINVAL;
   if (workspace_bytes < pn2_bn_workspace_size(rows, C)) return PN2_EINVAL;
   const int nblk = (int)ceil_div(rows, kStatRows), ct = (int)ceil_div(C, kCols);
   float* part = static_cast<float*>(workspace);
   hipStream_t s = (hipStream_t)stream;
-  if (given) {
-    hipLaunchKernelGGL(bn_bwd_partial<true>, dim3(nblk, ct), dim3(kBlock), 0, s, grad_out, y, rows,
-                       C, mean, var, gamma, beta, eps, relu ? 1 : 0, grad_y, part);
-    hipLaunchKernelGGL(bn_bwd_final, dim3(ct), dim3(kBlock), 0, s, part, C, nblk, grad_gamma,
-                       grad_beta);
+  PN2_LAUNCH_BN(bn, bn_bwd_partial, dim3(nblk, ct), s, grad_out, y, rows, C, bn, relu ? 1 : 0,
+                grad_y, part);
+  hipLaunchKernelGGL(block_sum_final<2>, dim3(ct), dim3(kBlock), 0, s, part, C, nblk, grad_beta,
+                     grad_gamma);
+  if (bn.mean)
     hipLaunchKernelGGL(bn_bwd_apply, dim3((unsigned)ceil_div(rows, kActRows), ct), dim3(kBlock), 0,
-                       s, grad_out, y, rows, C, mean, var, gamma, beta, eps, relu ? 1 : 0,
-                       grad_gamma, grad_beta, grad_y);
-  } else {
-    hipLaunchKernelGGL(bn_bwd_partial<false>, dim3(nblk, ct), dim3(kBlock), 0, s, grad_out, y,
-                       rows, C, mean, var, gamma, beta, eps, relu ? 1 : 0, grad_y, part);
-    hipLaunchKernelGGL(bn_bwd_final, dim3(ct), dim3(kBlock), 0, s, part, C, nblk, grad_gamma,
-                       grad_beta);
-  }
+                       s, grad_out, y, rows, C, bn, relu ? 1 : 0, grad_gamma, grad_beta, grad_y);
   PN2_RETURN_LAUNCH();
 }
 
@@ -804,29 +639,18 @@ int pn2_bn_act_pool_fwd(const float* y, long long groups, int ns, int C, const f
   using namespace pn2;
   long long rows;
   if (!pool_shape_ok(groups, ns, C, &rows) || !y || !out || !arg) return PN2_EINVAL;
-  const int given = (mean ? 1 : 0) + (var ? 1 : 0) + (gamma ? 1 : 0) + (beta ? 1 : 0);
-  if (given != 0 && given != 4) return PN2_EINVAL;
-  if (given && !(eps >= 0.f)) return PN2_EINVAL;
+  const BnArgs bn = {mean, var, gamma, beta, eps};
+  if (!bn_args_ok(bn)) return PN2_EINVAL;
   const unsigned ct = (unsigned)ceil_div(C, kCols);
   hipStream_t s = (hipStream_t)stream;
   const int r = relu ? 1 : 0;
   if (ns <= kPoolSplit) {
     const int gpt = pool_gpt(ns);
     const dim3 grid((unsigned)ceil_div(groups, (long long)kRowLanes * gpt), ct);
-    if (given)
-      hipLaunchKernelGGL(bn_act_pool_fwd_groups<true>, grid, dim3(kBlock), 0, s, y, groups, ns, C,
-                         gpt, mean, var, gamma, beta, eps, r, out, arg);
-    else
-      hipLaunchKernelGGL(bn_act_pool_fwd_groups<false>, grid, dim3(kBlock), 0, s, y, groups, ns, C,
-                         gpt, mean, var, gamma, beta, eps, r, out, arg);
+    PN2_LAUNCH_BN(bn, bn_act_pool_fwd_groups, grid, s, y, groups, ns, C, gpt, bn, r, out, arg);
   } else {
-    const dim3 grid((unsigned)groups, ct);
-    if (given)
-      hipLaunchKernelGGL(bn_act_pool_fwd_split<true>, grid, dim3(kBlock), 0, s, y, ns, C, mean,
-                         var, gamma, beta, eps, r, out, arg);
-    else
-      hipLaunchKernelGGL(bn_act_pool_fwd_split<false>, grid, dim3(kBlock), 0, s, y, ns, C, mean,
-                         var, gamma, beta, eps, r, out, arg);
+    PN2_LAUNCH_BN(bn, bn_act_pool_fwd_split, dim3((unsigned)groups, ct), s, y, ns, C, bn, r, out,
+                  arg);
   }
   PN2_RETURN_LAUNCH();
 }
@@ -845,47 +669,48 @@ int pn2_bn_act_pool_bwd(const float* grad_out, const int* arg, const float* y, l
   long long rows;
   if (!pool_shape_ok(groups, ns, C, &rows)) return PN2_EINVAL;
   if (!grad_out || !arg || !y || !grad_y || !grad_beta || !workspace) return PN2_EINVAL;
-  const int given = (mean ? 1 : 0) + (var ? 1 : 0) + (gamma ? 1 : 0) + (beta ? 1 : 0);
-  if (given != 0 && given != 4) return PN2_EINVAL;
-  if ((given != 0) != (grad_gamma != nullptr)) return PN2_EINVAL;
-  if (given && !(eps >= 0.f)) return PN2_EINVAL;
+  const BnArgs bn = {mean, var, gamma, beta, eps};
+  if (!bn_args_ok(bn, &grad_gamma)) return PN2_EINVAL;
   if (workspace_bytes < pn2_bn_pool_workspace_size(groups, C)) return PN2_EINVAL;
   const int nblk = (int)ceil_div(groups, kPoolGroups);
   const unsigned ct = (unsigned)ceil_div(C, kCols);
   float* part = static_cast<float*>(workspace);
   hipStream_t s = (hipStream_t)stream;
   const int r = relu ? 1 : 0;
-  if (given)
-    hipLaunchKernelGGL(bn_pool_bwd_partial<true>, dim3(nblk, ct), dim3(kBlock), 0, s, grad_out,
-                       arg, y, groups, ns, C, mean, var, gamma, beta, eps, r, part);
-  else
-    hipLaunchKernelGGL(bn_pool_bwd_partial<false>, dim3(nblk, ct), dim3(kBlock), 0, s, grad_out,
-                       arg, y, groups, ns, C, mean, var, gamma, beta, eps, r, part);
-  hipLaunchKernelGGL(bn_bwd_final, dim3(ct), dim3(kBlock), 0, s, part, C, nblk, grad_gamma,
-                     grad_beta);
+  PN2_LAUNCH_BN(bn, bn_pool_bwd_partial, dim3(nblk, ct), s, grad_out, arg, y, groups, ns, C, bn, r,
+                part);
+  hipLaunchKernelGGL(block_sum_final<2>, dim3(ct), dim3(kBlock), 0, s, part, C, nblk, grad_beta,
+                     grad_gamma);
   if (ns <= kPoolSplit) {
     const int gpt = pool_gpt(ns);
     const dim3 grid((unsigned)ceil_div(groups, (long long)kRowLanes * gpt), ct);
-    if (given)
-      hipLaunchKernelGGL(bn_pool_bwd_apply_groups<true>, grid, dim3(kBlock), 0, s, grad_out, arg,
-                         y, groups, ns, C, gpt, mean, var, gamma, beta, eps, r, grad_gamma,
-                         grad_beta, grad_y);
-    else
-      hipLaunchKernelGGL(bn_pool_bwd_apply_groups<false>, grid, dim3(kBlock), 0, s, grad_out, arg,
-                         y, groups, ns, C, gpt, mean, var, gamma, beta, eps, r, grad_gamma,
-                         grad_beta, grad_y);
+    PN2_LAUNCH_BN(bn, bn_pool_bwd_apply_groups, grid, s, grad_out, arg, y, groups, ns, C, gpt, bn,
+                  r, grad_gamma, grad_beta, grad_y);
   } else {
     const int nchunk = (int)ceil_div(ns, kActRows);
-    const dim3 grid((unsigned)(groups * nchunk), ct);
-    if (given)
-      hipLaunchKernelGGL(bn_pool_bwd_apply_split<true>, grid, dim3(kBlock), 0, s, grad_out, arg, y,
-                         groups, ns, C, nchunk, mean, var, gamma, beta, eps, r, grad_gamma,
-                         grad_beta, grad_y);
-    else
-      hipLaunchKernelGGL(bn_pool_bwd_apply_split<false>, grid, dim3(kBlock), 0, s, grad_out, arg,
-                         y, groups, ns, C, nchunk, mean, var, gamma, beta, eps, r, grad_gamma,
-                         grad_beta, grad_y);
+    PN2_LAUNCH_BN(bn, bn_pool_bwd_apply_split, dim3((unsigned)(groups * nchunk), ct), s, grad_out,
+                  arg, y, groups, ns, C, nchunk, bn, r, grad_gamma, grad_beta, grad_y);
   }
+  PN2_RETURN_LAUNCH();
+}
+
+size_t pn2_col_sum_workspace_size(long long rows, int C) {
+  if (rows <= 0 || C <= 0) return 0;
+  return (size_t)pn2::ceil_div(rows, pn2::kStatRows) * (size_t)C * sizeof(float);
+}
+
+int pn2_col_sum(const float* x, long long rows, int C, float* out, void* workspace,
+                size_t workspace_bytes, pn2_stream_t stream) {
+  using namespace pn2;
+  if (rows <= 0 || C <= 0 || rows > kMaxRows || C > kMaxC) return PN2_EINVAL;
+  if (!x || !out || !workspace) return PN2_EINVAL;
+  if (workspace_bytes < pn2_col_sum_workspace_size(rows, C)) return PN2_EINVAL;
+  const int nblk = (int)ceil_div(rows, kStatRows), ct = (int)ceil_div(C, kCols);
+  float* part = static_cast<float*>(workspace);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(col_sum_partial, dim3(nblk, ct), dim3(kBlock), 0, s, x, rows, C, part);
+  hipLaunchKernelGGL(block_sum_final<1>, dim3(ct), dim3(kBlock), 0, s, part, C, nblk, out,
+                     (float*)nullptr);
   PN2_RETURN_LAUNCH();
 }
 

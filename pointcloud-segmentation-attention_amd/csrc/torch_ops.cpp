@@ -27,6 +27,7 @@
 #include <torch/csrc/autograd/custom_function.h>
 #include <torch/library.h>
 
+#include <initializer_list>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -490,105 +491,7 @@ void linear_rows(const Tensor& in, const Tensor& w, const Tensor& bias, int64_t 
   check_rc(pn2_shared_mlp(F(in), rows, cin, 1, &layer, out.data_ptr<float>(), stream_of(in)), op);
 }
 
-std::tuple<Tensor, Tensor, Tensor, Tensor> mlp_layer_train_hip(
-    const Tensor& x_, const Tensor& weight_, const std::optional<Tensor>& bias_,
-    const std::optional<Tensor>& gamma_, const std::optional<Tensor>& beta_, double eps,
-    bool relu) {
-  const char* op = "mlp_layer_train";
-  chk_mlp_layer(x_, weight_, bias_, gamma_, beta_, op);
-  Tensor x = dev(x_, "x", at::kFloat), weight = dev(weight_, "weight", at::kFloat);
-  Tensor bias, gamma, beta;
-  if (has(bias_)) bias = dev(*bias_, "bias", at::kFloat);
-  const bool bn = has(gamma_);
-  if (bn) {
-    gamma = dev(*gamma_, "gamma", at::kFloat);
-    beta = dev(*beta_, "beta", at::kFloat);
-  }
-  c10::hip::HIPGuard g(x.device().index());
-  const int cin = I(weight.size(0)), cout = I(weight.size(1));
-  const int64_t rows = x.numel() / cin;
-  Tensor out = at::empty(with_last(x, cout), f32(x));
-  Tensor y = at::empty(with_last(x, cout), f32(x));
-  Tensor mean = at::empty({bn ? cout : 0}, f32(x)), var = at::empty({bn ? cout : 0}, f32(x));
-  if (rows == 0) {  // no rows, no statistics: defined values (tf_util.mlp_train skips its update)
-    mean.zero_();
-    var.zero_();
-    return {out, y, mean, var};
-  }
-  linear_rows(x, weight, bias, rows, y, op);
-  if (bn) {
-    const size_t ws = pn2_bn_workspace_size(rows, cout);
-    Tensor w = workspace(x, ws);
-    check_rc(pn2_bn_stats(F(y), rows, cout, mean.data_ptr<float>(), var.data_ptr<float>(), P(w),
-                          ws, stream_of(x)), op);
-  }
-  check_rc(pn2_bn_act_fwd(F(y), rows, cout, bn ? F(mean) : nullptr, bn ? F(var) : nullptr, F(gamma),
-                          F(beta), static_cast<float>(eps), relu ? 1 : 0, out.data_ptr<float>(),
-                          stream_of(x)), op);
-  return {out, y, mean, var};
-}
-
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_grad_hip(
-    const Tensor& grad_out_, const Tensor& x_, const Tensor& weight_, const Tensor& y_,
-    const std::optional<Tensor>& mean_, const std::optional<Tensor>& var_,
-    const std::optional<Tensor>& gamma_, const std::optional<Tensor>& beta_, double eps, bool relu,
-    bool need_grad_x) {
-  const char* op = "mlp_layer_train_grad";
-  chk_mlp_layer(x_, weight_, std::nullopt, gamma_, beta_, op);
-  const bool bn = has(gamma_);
-  const int cin = I(weight_.size(0)), cout = I(weight_.size(1));
-  TORCH_CHECK_VALUE(y_.sizes() == grad_out_.sizes() && y_.dim() == x_.dim() && y_.size(-1) == cout &&
-                        y_.numel() / cout == x_.numel() / cin,
-                    op, " expects (..., cout) grad_out and y for (..., cin) x");
-  if (bn)
-    TORCH_CHECK_VALUE(has(mean_) && has(var_) && mean_->dim() == 1 && mean_->size(0) == cout &&
-                          var_->dim() == 1 && var_->size(0) == cout,
-                      op, " expects (cout) mean and var with gamma and beta");
-  Tensor go = dev(grad_out_, "grad_out", at::kFloat), x = dev(x_, "x", at::kFloat);
-  Tensor weight = dev(weight_, "weight", at::kFloat), y = dev(y_, "y", at::kFloat);
-  Tensor mean, var, gamma, beta;
-  if (bn) {
-    mean = dev(*mean_, "mean", at::kFloat);
-    var = dev(*var_, "var", at::kFloat);
-    gamma = dev(*gamma_, "gamma", at::kFloat);
-    beta = dev(*beta_, "beta", at::kFloat);
-  }
-  c10::hip::HIPGuard g(x.device().index());
-  const int64_t rows = x.numel() / cin;
-  Tensor grad_x = need_grad_x ? at::empty(x.sizes(), f32(x)) : at::empty({0}, f32(x));
-  Tensor grad_w = at::empty({cin, cout}, f32(x));
-  // under batch norm the bias shifts the batch mean with it: its gradient is identically zero
-  Tensor grad_b = bn ? at::zeros({cout}, f32(x)) : at::empty({cout}, f32(x));
-  Tensor grad_gamma = at::empty({bn ? cout : 0}, f32(x));
-  Tensor grad_beta = at::empty({bn ? cout : 0}, f32(x));
-  if (rows == 0) {
-    grad_w.zero_();
-    grad_b.zero_();
-    grad_gamma.zero_();
-    grad_beta.zero_();
-    return {grad_x, grad_w, grad_b, grad_gamma, grad_beta};
-  }
-  Tensor grad_y = at::empty(y.sizes(), f32(x));
-  {
-    const size_t ws = pn2_bn_workspace_size(rows, cout);
-    Tensor w = workspace(x, ws);
-    check_rc(pn2_bn_act_bwd(F(go), F(y), rows, cout, F(mean), F(var), F(gamma), F(beta),
-                            static_cast<float>(eps), relu ? 1 : 0, grad_y.data_ptr<float>(),
-                            bn ? grad_gamma.data_ptr<float>() : nullptr,
-                            bn ? grad_beta.data_ptr<float>() : grad_b.data_ptr<float>(), P(w), ws,
-                            stream_of(x)), op);
-  }
-  {
-    const size_t ws = pn2_mlp_wgrad_workspace_size(rows, cin, cout);
-    Tensor w = workspace(x, ws);
-    check_rc(pn2_mlp_wgrad(F(x), F(grad_y), rows, cin, cout, grad_w.data_ptr<float>(), P(w), ws,
-                           stream_of(x)), op);
-  }
-  if (need_grad_x) linear_rows(grad_y, weight.t().contiguous(), Tensor(), rows, grad_x, op);
-  return {grad_x, grad_w, grad_b, grad_gamma, grad_beta};
-}
-
-// ---- the last layer of a set-abstraction MLP fused with the max pool over nsample
+// the last layer of a set-abstraction MLP fused with the max pool over nsample
 // (pn2_bn_act_pool_fwd / _bwd): x (..., ns, cin) -> out, arg (..., cout); the (..., ns, cout)
 // activation is never allocated
 void chk_mlp_pool(const Tensor& x, const Tensor& weight, const std::optional<Tensor>& bias,
@@ -603,6 +506,24 @@ std::vector<int64_t> pooled_sizes(const Tensor& x, int64_t c) {
   s.push_back(c);
   return s;
 }
+void chk_mean_var(const std::optional<Tensor>& mean, const std::optional<Tensor>& var,
+                  const std::optional<Tensor>& gamma, int64_t cout, const char* op) {
+  if (has(gamma))
+    TORCH_CHECK_VALUE(has(mean) && has(var) && mean->dim() == 1 && mean->size(0) == cout &&
+                          var->dim() == 1 && var->size(0) == cout,
+                      op, " expects (cout) mean and var with gamma and beta");
+}
+void chk_mlp_layer_grad(const Tensor& grad_out, const Tensor& x, const Tensor& weight,
+                        const Tensor& y, const std::optional<Tensor>& mean,
+                        const std::optional<Tensor>& var, const std::optional<Tensor>& gamma,
+                        const std::optional<Tensor>& beta, const char* op) {
+  chk_mlp_layer(x, weight, std::nullopt, gamma, beta, op);
+  const int64_t cin = weight.size(0), cout = weight.size(1);
+  TORCH_CHECK_VALUE(y.sizes() == grad_out.sizes() && y.dim() == x.dim() && y.size(-1) == cout &&
+                        y.numel() / cout == x.numel() / cin,
+                    op, " expects (..., cout) grad_out and y for (..., cin) x");
+  chk_mean_var(mean, var, gamma, cout, op);
+}
 void chk_mlp_pool_grad(const Tensor& grad_out, const Tensor& arg, const Tensor& x,
                        const Tensor& weight, const Tensor& y, const std::optional<Tensor>& mean,
                        const std::optional<Tensor>& var, const std::optional<Tensor>& gamma,
@@ -614,105 +535,148 @@ void chk_mlp_pool_grad(const Tensor& grad_out, const Tensor& arg, const Tensor& 
   TORCH_CHECK_VALUE(grad_out.sizes() == c10::IntArrayRef(pooled_sizes(x, cout)) &&
                         arg.sizes() == grad_out.sizes(),
                     op, " expects (..., cout) grad_out and arg for (..., ns, cin) x");
-  if (has(gamma))
-    TORCH_CHECK_VALUE(has(mean) && has(var) && mean->dim() == 1 && mean->size(0) == cout &&
-                          var->dim() == 1 && var->size(0) == cout,
-                      op, " expects (cout) mean and var with gamma and beta");
+  chk_mean_var(mean, var, gamma, cout, op);
 }
 
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_pool_hip(
+// an optional per-channel vector on the device; undefined (a null pointer under F) if absent
+Tensor dev_opt(const std::optional<Tensor>& t, const char* name, bool wanted = true) {
+  return wanted && has(t) ? dev(*t, name, at::kFloat) : Tensor();
+}
+// no rows, no statistics and no sums: defined values (tf_util.mlp_train skips its update)
+bool no_rows(int64_t rows, std::initializer_list<Tensor*> zeroed) {
+  if (rows != 0) return false;
+  for (Tensor* t : zeroed) t->zero_();
+  return true;
+}
+void bn_stats(const Tensor& y, int64_t rows, int C, Tensor& mean, Tensor& var, const char* op) {
+  const size_t ws = pn2_bn_workspace_size(rows, C);
+  Tensor w = workspace(y, ws);
+  check_rc(pn2_bn_stats(F(y), rows, C, mean.data_ptr<float>(), var.data_ptr<float>(), P(w), ws,
+                        stream_of(y)), op);
+}
+// pn2_bn_act_bwd, or with arg pn2_bn_act_pool_bwd over groups of ns rows; mean, var, gamma, beta
+// and grad_gamma are undefined without batch norm
+void bn_act_bwd(const Tensor& go, const Tensor* arg, const Tensor& y, int64_t rows, int64_t ns,
+                int C, const Tensor& mean, const Tensor& var, const Tensor& gamma,
+                const Tensor& beta, double eps, bool relu, Tensor& grad_y,
+                const Tensor& grad_gamma, Tensor& grad_beta, const char* op) {
+  const size_t ws = arg ? pn2_bn_pool_workspace_size(rows / ns, C) : pn2_bn_workspace_size(rows, C);
+  Tensor w = workspace(y, ws);
+  float* gg = grad_gamma.defined() ? grad_gamma.data_ptr<float>() : nullptr;
+  const float e = static_cast<float>(eps);
+  const int r = relu ? 1 : 0;
+  check_rc(arg ? pn2_bn_act_pool_bwd(F(go), Ii(*arg), F(y), rows / ns, I(ns), C, F(mean), F(var),
+                                     F(gamma), F(beta), e, r, grad_y.data_ptr<float>(), gg,
+                                     grad_beta.data_ptr<float>(), P(w), ws, stream_of(y))
+               : pn2_bn_act_bwd(F(go), F(y), rows, C, F(mean), F(var), F(gamma), F(beta), e, r,
+                                grad_y.data_ptr<float>(), gg, grad_beta.data_ptr<float>(), P(w),
+                                ws, stream_of(y)), op);
+}
+void wgrad(const Tensor& x, const Tensor& grad_y, int64_t rows, int cin, int cout, Tensor& grad_w,
+           const char* op) {
+  const size_t ws = pn2_mlp_wgrad_workspace_size(rows, cin, cout);
+  Tensor w = workspace(x, ws);
+  check_rc(pn2_mlp_wgrad(F(x), F(grad_y), rows, cin, cout, grad_w.data_ptr<float>(), P(w), ws,
+                         stream_of(x)), op);
+}
+
+// mlp_layer_train and, pooled, mlp_layer_train_pool: out, y, mean, var and (pooled) arg
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_train_fwd(
     const Tensor& x_, const Tensor& weight_, const std::optional<Tensor>& bias_,
-    const std::optional<Tensor>& gamma_, const std::optional<Tensor>& beta_, double eps,
-    bool relu) {
-  const char* op = "mlp_layer_train_pool";
-  chk_mlp_pool(x_, weight_, bias_, gamma_, beta_, op);
+    const std::optional<Tensor>& gamma_, const std::optional<Tensor>& beta_, double eps, bool relu,
+    bool pooled, const char* op) {
+  (pooled ? chk_mlp_pool : chk_mlp_layer)(x_, weight_, bias_, gamma_, beta_, op);
   Tensor x = dev(x_, "x", at::kFloat), weight = dev(weight_, "weight", at::kFloat);
-  Tensor bias, gamma, beta;
-  if (has(bias_)) bias = dev(*bias_, "bias", at::kFloat);
-  const bool bn = has(gamma_);
-  if (bn) {
-    gamma = dev(*gamma_, "gamma", at::kFloat);
-    beta = dev(*beta_, "beta", at::kFloat);
-  }
+  Tensor bias = dev_opt(bias_, "bias"), gamma = dev_opt(gamma_, "gamma");
+  Tensor beta = dev_opt(beta_, "beta");
+  const bool bn = gamma.defined();
   c10::hip::HIPGuard g(x.device().index());
   const int cin = I(weight.size(0)), cout = I(weight.size(1));
-  const int64_t rows = x.numel() / cin, ns = x.size(-2), groups = rows / ns;
-  Tensor out = at::empty(pooled_sizes(x, cout), f32(x));
-  Tensor arg = at::empty(pooled_sizes(x, cout), i32(x));
+  const int64_t rows = x.numel() / cin;
+  const std::vector<int64_t> out_sizes = pooled ? pooled_sizes(x, cout) : with_last(x, cout);
+  Tensor out = at::empty(out_sizes, f32(x)), arg;
+  if (pooled) arg = at::empty(out_sizes, i32(x));
   Tensor y = at::empty(with_last(x, cout), f32(x));
   Tensor mean = at::empty({bn ? cout : 0}, f32(x)), var = at::empty({bn ? cout : 0}, f32(x));
-  if (rows == 0) {
-    mean.zero_();
-    var.zero_();
-    return {out, y, mean, var, arg};
-  }
-  // y, mean and var by the calls of mlp_layer_train: the same bits
+  if (no_rows(rows, {&mean, &var})) return {out, y, mean, var, arg};
   linear_rows(x, weight, bias, rows, y, op);
-  if (bn) {
-    const size_t ws = pn2_bn_workspace_size(rows, cout);
-    Tensor w = workspace(x, ws);
-    check_rc(pn2_bn_stats(F(y), rows, cout, mean.data_ptr<float>(), var.data_ptr<float>(), P(w),
-                          ws, stream_of(x)), op);
+  if (bn) bn_stats(y, rows, cout, mean, var, op);
+  const float* m = bn ? F(mean) : nullptr;
+  const float* v = bn ? F(var) : nullptr;
+  const float e = static_cast<float>(eps);
+  if (pooled) {
+    const int64_t ns = x.size(-2);
+    check_rc(pn2_bn_act_pool_fwd(F(y), rows / ns, I(ns), cout, m, v, F(gamma), F(beta), e,
+                                 relu ? 1 : 0, out.data_ptr<float>(), arg.data_ptr<int32_t>(),
+                                 stream_of(x)), op);
+  } else {
+    check_rc(pn2_bn_act_fwd(F(y), rows, cout, m, v, F(gamma), F(beta), e, relu ? 1 : 0,
+                            out.data_ptr<float>(), stream_of(x)), op);
   }
-  check_rc(pn2_bn_act_pool_fwd(F(y), groups, I(ns), cout, bn ? F(mean) : nullptr,
-                               bn ? F(var) : nullptr, F(gamma), F(beta), static_cast<float>(eps),
-                               relu ? 1 : 0, out.data_ptr<float>(), arg.data_ptr<int32_t>(),
-                               stream_of(x)), op);
   return {out, y, mean, var, arg};
 }
 
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_pool_grad_hip(
-    const Tensor& grad_out_, const Tensor& arg_, const Tensor& x_, const Tensor& weight_,
+// mlp_layer_train_grad and, with arg, mlp_layer_train_pool_grad (grad_out is then (..., cout))
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_train_bwd(
+    const Tensor& grad_out_, const Tensor* arg_, const Tensor& x_, const Tensor& weight_,
     const Tensor& y_, const std::optional<Tensor>& mean_, const std::optional<Tensor>& var_,
     const std::optional<Tensor>& gamma_, const std::optional<Tensor>& beta_, double eps, bool relu,
-    bool need_grad_x) {
-  const char* op = "mlp_layer_train_pool_grad";
-  chk_mlp_pool_grad(grad_out_, arg_, x_, weight_, y_, mean_, var_, gamma_, beta_, op);
+    bool need_grad_x, const char* op) {
+  if (arg_) chk_mlp_pool_grad(grad_out_, *arg_, x_, weight_, y_, mean_, var_, gamma_, beta_, op);
+  else chk_mlp_layer_grad(grad_out_, x_, weight_, y_, mean_, var_, gamma_, beta_, op);
   const bool bn = has(gamma_);
-  const int cin = I(weight_.size(0)), cout = I(weight_.size(1));
-  Tensor go = dev(grad_out_, "grad_out", at::kFloat), arg = dev(arg_, "arg", at::kInt);
+  Tensor go = dev(grad_out_, "grad_out", at::kFloat), arg;
+  if (arg_) arg = dev(*arg_, "arg", at::kInt);
   Tensor x = dev(x_, "x", at::kFloat), weight = dev(weight_, "weight", at::kFloat);
   Tensor y = dev(y_, "y", at::kFloat);
-  Tensor mean, var, gamma, beta;
-  if (bn) {
-    mean = dev(*mean_, "mean", at::kFloat);
-    var = dev(*var_, "var", at::kFloat);
-    gamma = dev(*gamma_, "gamma", at::kFloat);
-    beta = dev(*beta_, "beta", at::kFloat);
-  }
+  Tensor mean = dev_opt(mean_, "mean", bn), var = dev_opt(var_, "var", bn);
+  Tensor gamma = dev_opt(gamma_, "gamma"), beta = dev_opt(beta_, "beta");
   c10::hip::HIPGuard g(x.device().index());
-  const int64_t rows = x.numel() / cin, ns = x.size(-2), groups = rows / ns;
+  const int cin = I(weight.size(0)), cout = I(weight.size(1));
+  const int64_t rows = x.numel() / cin;
   Tensor grad_x = need_grad_x ? at::empty(x.sizes(), f32(x)) : at::empty({0}, f32(x));
   Tensor grad_w = at::empty({cin, cout}, f32(x));
+  // under batch norm the bias shifts the batch mean with it: its gradient is identically zero
   Tensor grad_b = bn ? at::zeros({cout}, f32(x)) : at::empty({cout}, f32(x));
   Tensor grad_gamma = at::empty({bn ? cout : 0}, f32(x));
   Tensor grad_beta = at::empty({bn ? cout : 0}, f32(x));
-  if (rows == 0) {
-    grad_w.zero_();
-    grad_b.zero_();
-    grad_gamma.zero_();
-    grad_beta.zero_();
+  if (no_rows(rows, {&grad_w, &grad_b, &grad_gamma, &grad_beta}))
     return {grad_x, grad_w, grad_b, grad_gamma, grad_beta};
-  }
   Tensor grad_y = at::empty(y.sizes(), f32(x));
-  {
-    const size_t ws = pn2_bn_pool_workspace_size(groups, cout);
-    Tensor w = workspace(x, ws);
-    check_rc(pn2_bn_act_pool_bwd(F(go), Ii(arg), F(y), groups, I(ns), cout, F(mean), F(var),
-                                 F(gamma), F(beta), static_cast<float>(eps), relu ? 1 : 0,
-                                 grad_y.data_ptr<float>(),
-                                 bn ? grad_gamma.data_ptr<float>() : nullptr,
-                                 bn ? grad_beta.data_ptr<float>() : grad_b.data_ptr<float>(),
-                                 P(w), ws, stream_of(x)), op);
-  }
-  {
-    const size_t ws = pn2_mlp_wgrad_workspace_size(rows, cin, cout);
-    Tensor w = workspace(x, ws);
-    check_rc(pn2_mlp_wgrad(F(x), F(grad_y), rows, cin, cout, grad_w.data_ptr<float>(), P(w), ws,
-                           stream_of(x)), op);
-  }
+  bn_act_bwd(go, arg_ ? &arg : nullptr, y, rows, arg_ ? x.size(-2) : 1, cout, mean, var, gamma,
+             beta, eps, relu, grad_y, bn ? grad_gamma : Tensor(), bn ? grad_beta : grad_b, op);
+  wgrad(x, grad_y, rows, cin, cout, grad_w, op);
   if (need_grad_x) linear_rows(grad_y, weight.t().contiguous(), Tensor(), rows, grad_x, op);
   return {grad_x, grad_w, grad_b, grad_gamma, grad_beta};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> mlp_layer_train_hip(
+    const Tensor& x, const Tensor& weight, const std::optional<Tensor>& bias,
+    const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta, double eps, bool relu) {
+  auto [out, y, mean, var, arg] =
+      mlp_train_fwd(x, weight, bias, gamma, beta, eps, relu, false, "mlp_layer_train");
+  return {out, y, mean, var};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_pool_hip(
+    const Tensor& x, const Tensor& weight, const std::optional<Tensor>& bias,
+    const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta, double eps, bool relu) {
+  return mlp_train_fwd(x, weight, bias, gamma, beta, eps, relu, true, "mlp_layer_train_pool");
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_grad_hip(
+    const Tensor& grad_out, const Tensor& x, const Tensor& weight, const Tensor& y,
+    const std::optional<Tensor>& mean, const std::optional<Tensor>& var,
+    const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta, double eps, bool relu,
+    bool need_grad_x) {
+  return mlp_train_bwd(grad_out, nullptr, x, weight, y, mean, var, gamma, beta, eps, relu,
+                       need_grad_x, "mlp_layer_train_grad");
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_pool_grad_hip(
+    const Tensor& grad_out, const Tensor& arg, const Tensor& x, const Tensor& weight,
+    const Tensor& y, const std::optional<Tensor>& mean, const std::optional<Tensor>& var,
+    const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta, double eps, bool relu,
+    bool need_grad_x) {
+  return mlp_train_bwd(grad_out, &arg, x, weight, y, mean, var, gamma, beta, eps, relu,
+                       need_grad_x, "mlp_layer_train_pool_grad");
 }
 
 // ---- training-mode AttentionLayer of the attention SA modules (csrc/attn_train.hip;
@@ -754,13 +718,6 @@ void col_sum(const Tensor& x, int64_t rows, int C, Tensor& out, const char* op) 
   const size_t ws = pn2_col_sum_workspace_size(rows, C);
   Tensor w = workspace(x, ws);
   check_rc(pn2_col_sum(F(x), rows, C, out.data_ptr<float>(), P(w), ws, stream_of(x)), op);
-}
-void wgrad(const Tensor& x, const Tensor& grad_y, int64_t rows, int cin, int cout, Tensor& grad_w,
-           const char* op) {
-  const size_t ws = pn2_mlp_wgrad_workspace_size(rows, cin, cout);
-  Tensor w = workspace(x, ws);
-  check_rc(pn2_mlp_wgrad(F(x), F(grad_y), rows, cin, cout, grad_w.data_ptr<float>(), P(w), ws,
-                         stream_of(x)), op);
 }
 
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> attn_kv_train_hip(
@@ -862,15 +819,8 @@ std::tuple<Tensor, Tensor, Tensor> bn_train_hip(const Tensor& x_, const Tensor& 
   const int64_t rows = x.numel() / C;
   Tensor out = at::empty(x.sizes(), f32(x));
   Tensor mean = at::empty({C}, f32(x)), var = at::empty({C}, f32(x));
-  if (rows == 0) {
-    mean.zero_();
-    var.zero_();
-    return {out, mean, var};
-  }
-  const size_t ws = pn2_bn_workspace_size(rows, C);
-  Tensor w = workspace(x, ws);
-  check_rc(pn2_bn_stats(F(x), rows, C, mean.data_ptr<float>(), var.data_ptr<float>(), P(w), ws,
-                        stream_of(x)), op);
+  if (no_rows(rows, {&mean, &var})) return {out, mean, var};
+  bn_stats(x, rows, C, mean, var, op);
   check_rc(pn2_bn_act_fwd(F(x), rows, C, F(mean), F(var), F(gamma), F(beta),
                           static_cast<float>(eps), relu ? 1 : 0, out.data_ptr<float>(),
                           stream_of(x)), op);
@@ -894,17 +844,9 @@ std::tuple<Tensor, Tensor, Tensor> bn_train_grad_hip(const Tensor& grad_out_, co
   const int64_t rows = x.numel() / C;
   Tensor grad_x = at::empty(x.sizes(), f32(x));
   Tensor grad_gamma = at::empty({C}, f32(x)), grad_beta = at::empty({C}, f32(x));
-  if (rows == 0) {
-    grad_gamma.zero_();
-    grad_beta.zero_();
-    return {grad_x, grad_gamma, grad_beta};
-  }
-  const size_t ws = pn2_bn_workspace_size(rows, C);
-  Tensor w = workspace(x, ws);
-  check_rc(pn2_bn_act_bwd(F(go), F(x), rows, C, F(mean), F(var), F(gamma), F(beta),
-                          static_cast<float>(eps), relu ? 1 : 0, grad_x.data_ptr<float>(),
-                          grad_gamma.data_ptr<float>(), grad_beta.data_ptr<float>(), P(w), ws,
-                          stream_of(x)), op);
+  if (no_rows(rows, {&grad_gamma, &grad_beta})) return {grad_x, grad_gamma, grad_beta};
+  bn_act_bwd(go, nullptr, x, rows, 1, C, mean, var, gamma, beta, eps, relu, grad_x, grad_gamma,
+             grad_beta, op);
   return {grad_x, grad_gamma, grad_beta};
 }
 

@@ -1,6 +1,6 @@
 """GPU: the training-mode attention layer (torch.ops.pn2.attn_kv_train / _grad, bn_train / _grad;
-pn2_attn_kv_reduce, pn2_attn_kv_reduce_grad, pn2_attn_dx_scatter, pn2_col_sum in
-csrc/attn_train.hip) through torch.ops.pn2, the C ABI and the public attention_layer interfaces.
+pn2_attn_kv_reduce, pn2_attn_kv_reduce_grad, pn2_attn_dx_scatter in csrc/attn_train.hip,
+pn2_col_sum in csrc/mlp_train.hip) through torch.ops.pn2, the C ABI and the public attention_layer interfaces.
 
 Forward: exact. kv must have the bits of torch.ops.pn2.mlp_layer_train on [wk | wv], att the bits
 of torch.ops.pn2.attn_reduce on de-interleaved copies of kv, pmax the bits of x.max(-2), arg the
