@@ -167,7 +167,7 @@ constexpr int kChainNext = 1024;  // points per fused stage (LDS: input copy + 2
 
 struct FpsChain {
   int stages;
-  int verdicts;  // > 0: fps_prefix_check_kernel's verdict words at the head of each idx[0] row
+  int verdicts;  // > 0 (two-launch build only): verdict words at the head of each idx[0] row
   int* fault;  // the device fault word (fault_word_dev)
   int n[kChainMax], m[kChainMax];
   int32_t* idx[kChainMax];
@@ -571,6 +571,18 @@ PN2_DEV void fps_hot_body(const float* CXYZ, int N, int M, int32_t* I, float* NX
   }
 }
 
+// one stage (N <= kChainNext) on the block-scan bodies (fps_impl's per-size table), by threads
+// 0 .. kChainBlock - 1: wave 0 alone up to 512 points, else all four waves
+PN2_DEV void chain_stage_scan(const float* P, int N, int M, const float* CXYZ, int32_t* I,
+                              float* NX, float* SNEXT, uint2 (*red)[8]) {
+  const bool w0 = threadIdx.x < kWave;
+  if (N <= 64) { if (w0) fps_v9_body<64, 1, 1>(P, N, M, CXYZ, I, NX, SNEXT, red); }
+  else if (N <= 128) { if (w0) fps_v9_body<64, 2, 2>(P, N, M, CXYZ, I, NX, SNEXT, red); }
+  else if (N <= 256) { if (w0) fps_v9_body<64, 4, 4, false, true>(P, N, M, CXYZ, I, NX, SNEXT, red); }
+  else if (N <= 512) { if (w0) fps_v9_body<64, 8, 4, false, true>(P, N, M, CXYZ, I, NX, SNEXT, red); }
+  else fps_v9_body<256, 4, 2, false, true>(P, N, M, CXYZ, I, NX, SNEXT, red);
+}
+
 // one stage (N <= kChainNext) for one cloud, every thread of the workgroup: the hot-set
 // schedule (cold points per thread: 2 up to 384 points, 3 up to 512, 6 up to 1,024).
 // (Measured and not kept, profiles/r5/chain: the 1,024-point stage on ONE wave, 16 points a
@@ -595,12 +607,7 @@ PN2_DEV void chain_stage(const float* P, int N, int M, const float* CXYZ, int32_
   (void)tag0;
   (void)fault;
 #endif
-  const bool w0 = threadIdx.x < kWave;
-  if (N <= 64) { if (w0) fps_v9_body<64, 1, 1>(P, N, M, CXYZ, I, NX, SNEXT, red); }
-  else if (N <= 128) { if (w0) fps_v9_body<64, 2, 2>(P, N, M, CXYZ, I, NX, SNEXT, red); }
-  else if (N <= 256) { if (w0) fps_v9_body<64, 4, 4, false, true>(P, N, M, CXYZ, I, NX, SNEXT, red); }
-  else if (N <= 512) { if (w0) fps_v9_body<64, 8, 4, false, true>(P, N, M, CXYZ, I, NX, SNEXT, red); }
-  else fps_v9_body<256, 4, 2, false, true>(P, N, M, CXYZ, I, NX, SNEXT, red);
+  chain_stage_scan(P, N, M, CXYZ, I, NX, SNEXT, red);
 }
 
 // ---- a chain over an earlier sampler's output: its stages are prefixes ---------------------
@@ -618,46 +625,46 @@ PN2_DEV void chain_stage(const float* P, int N, int M, const float* CXYZ, int32_
 // samplers. A quick test of pick 1 first (the unique farthest point from pick 0), so an
 // arbitrary input (a chain whose first stage samples a raw cloud) is rejected in one pass.
 //
-// fps_prefix_check_kernel: one workgroup per (slice of kPrefixPts points, cloud); each checks
-// its points against every M_j (computed by every workgroup: no exchange) and stores its
-// verdict, 0 (holds) or -1, in word `slice` of the cloud's stage-0 idx row, which the chain
-// kernel reads before it writes that row. The work is ~n x m independent distance updates per
-// cloud, spread over the chip instead of the chain's one workgroup per cloud.
-constexpr int kPrefixPts = 256;
+// prefix_check_fails: the check of points base + t + BLOCK * q (q < PPT) of one cloud by a
+// workgroup of BLOCK threads, against every M_j (computed by the workgroup itself). Returns
+// the workgroup's verdict on every thread: true if any of its points, or any M_j, fails. The
+// work is ~n x m independent distance updates per cloud.
+// LDS of the check: picks 0 .. m - 1 as x, y, z arrays (a pair of consecutive picks from an
+// even index is one 8-byte read); smm[j + 1] = M_j (a pair M_j, M_j+1 from an odd j likewise)
+constexpr int kPrefixRow = kChainNext + 4;  // floats per array (pair tails included)
+constexpr int kPrefixLds = 4 * kPrefixRow;  // sx, sy, sz, smm
 using pf2 = float __attribute__((ext_vector_type(2)));
 
-__global__ __launch_bounds__(kPrefixPts) void fps_prefix_check_kernel(
-    const float* __restrict__ xyz, int n, int m, int32_t* __restrict__ verdict) {
-  // picks 0 .. m - 1 as x, y, z arrays (a pair of consecutive picks from an even index is one
-  // 8-byte read); smm[j + 1] = M_j (a pair M_j, M_j+1 from an odd j likewise)
-  __shared__ __attribute__((aligned(16))) float sx[kChainNext + 2], sy[kChainNext + 2],
-      sz[kChainNext + 2], smm[kChainNext + 4];
-  const int b = blockIdx.y, slice = blockIdx.x, t = threadIdx.x;
-  const float* __restrict__ P = xyz + (size_t)b * n * 3;
-  for (int e = t; e < m; e += kPrefixPts) {
+template <int BLOCK, int PPT>
+PN2_DEV bool prefix_check_fails(const float* __restrict__ P, int n, int m, int base,
+                                float* lds) {
+  float *sx = lds, *sy = lds + kPrefixRow, *sz = lds + 2 * kPrefixRow, *smm = lds + 3 * kPrefixRow;
+  const int t = threadIdx.x;
+  for (int e = t; e < m; e += BLOCK) {
     sx[e] = P[3 * e];
     sy[e] = P[3 * e + 1];
     sz[e] = P[3 * e + 2];
   }
   if (t < 2) sx[m + t] = sy[m + t] = sz[m + t] = 0.0f;  // (pair tails)
   __syncthreads();
-  const int s = slice * kPrefixPts + t;
-  const bool in = s < n;
-  // a point past n stands in as a copy of pick 0: its running min is 0 from step 1 on
-  const float px = in ? P[3 * s] : sx[0], py = in ? P[3 * s + 1] : sy[0],
-              pz = in ? P[3 * s + 2] : sz[0];
-  bool bad = !(__builtin_isfinite(px) && __builtin_isfinite(py) && __builtin_isfinite(pz));
-  {
-    const float m1 = fminf(1e38f, sqdist(sx[1], sy[1], sz[1], sx[0], sy[0], sz[0]));
-    bad = bad || !(m1 > 0.0f) ||
-          (s != 1 && !(fminf(1e38f, sqdist(px, py, pz, sx[0], sy[0], sz[0])) < m1));
+  float px[PPT], py[PPT], pz[PPT];
+  const float m1 = fminf(1e38f, sqdist(sx[1], sy[1], sz[1], sx[0], sy[0], sz[0]));
+  bool bad = !(m1 > 0.0f);
+#pragma unroll
+  for (int q = 0; q < PPT; ++q) {
+    const int s = base + t + BLOCK * q;
+    const bool in = s < n;
+    // a point past n stands in as a copy of pick 0: its running min is 0 from step 1 on
+    px[q] = in ? P[3 * s] : sx[0];
+    py[q] = in ? P[3 * s + 1] : sy[0];
+    pz[q] = in ? P[3 * s + 2] : sz[0];
+    bad = bad ||
+          !(__builtin_isfinite(px[q]) && __builtin_isfinite(py[q]) && __builtin_isfinite(pz[q])) ||
+          (s != 1 && !(fminf(1e38f, sqdist(px[q], py[q], pz[q], sx[0], sy[0], sz[0])) < m1));
   }
-  if (__syncthreads_or(bad)) {
-    if (t == 0) verdict[(size_t)b * m + slice] = -1;
-    return;
-  }
+  if (__syncthreads_or(bad)) return true;
   // M_j = temp_j(j), two picks' distances per packed step
-  for (int j = t; j < m; j += kPrefixPts) {
+  for (int j = t; j < m; j += BLOCK) {
     const pf2 qx = {sx[j], sx[j]}, qy = {sy[j], sy[j]}, qz = {sz[j], sz[j]};
     float v = 1e38f;
     int i = 0;
@@ -675,39 +682,124 @@ __global__ __launch_bounds__(kPrefixPts) void fps_prefix_check_kernel(
     bad = bad || (j > 0 && !(v > 0.0f));
   }
   if (t == 0) smm[m + 1] = 0.0f;  // (pair tail)
-  if (__syncthreads_or(bad)) {
-    if (t == 0) verdict[(size_t)b * m + slice] = -1;
-    return;
-  }
+  if (__syncthreads_or(bad)) return true;
   // every point's running min against each M_j; the one hit allowed is s's own step (j = s,
   // where temp_s(s) is M_s bit for bit: the same distances, and min is exact)
   {
-    const pf2 qx = {px, px}, qy = {py, py}, qz = {pz, pz};
-    float v = 1e38f;
-    int hits = in && s >= 1 && s < m ? -1 : 0;
+    float v[PPT];
+    int hits[PPT];
+#pragma unroll
+    for (int q = 0; q < PPT; ++q) {
+      const int s = base + t + BLOCK * q;
+      v[q] = 1e38f;
+      hits[q] = s < n && s >= 1 && s < m ? -1 : 0;
+    }
     int j = 1;
-#pragma unroll 4
+    constexpr int kUnroll = PPT == 1 ? 4 : 2;
+#pragma unroll kUnroll
     for (; j + 1 < m; j += 2) {  // steps j and j + 1: picks j - 1 and j
       const pf2 cx = *reinterpret_cast<const pf2*>(&sx[j - 1]),
                 cy = *reinterpret_cast<const pf2*>(&sy[j - 1]),
                 cz = *reinterpret_cast<const pf2*>(&sz[j - 1]),
                 mm = *reinterpret_cast<const pf2*>(&smm[j + 1]);
-      const pf2 dx = qx - cx, dy = qy - cy, dz = qz - cz;
-      const pf2 d = (dx * dx + dy * dy) + dz * dz;
-      v = fminf(v, d.x);
-      hits += v >= mm.x ? 1 : 0;
-      v = fminf(v, d.y);
-      hits += v >= mm.y ? 1 : 0;
+#pragma unroll
+      for (int q = 0; q < PPT; ++q) {
+        const pf2 qx = {px[q], px[q]}, qy = {py[q], py[q]}, qz = {pz[q], pz[q]};
+        const pf2 dx = qx - cx, dy = qy - cy, dz = qz - cz;
+        const pf2 d = (dx * dx + dy * dy) + dz * dz;
+        v[q] = fminf(v[q], d.x);
+        hits[q] += v[q] >= mm.x ? 1 : 0;
+        v[q] = fminf(v[q], d.y);
+        hits[q] += v[q] >= mm.y ? 1 : 0;
+      }
     }
-    if (j < m) {
-      v = fminf(v, sqdist(px, py, pz, sx[j - 1], sy[j - 1], sz[j - 1]));
-      hits += v >= smm[j + 1] ? 1 : 0;
+#pragma unroll
+    for (int q = 0; q < PPT; ++q) {
+      if (j < m) {
+        v[q] = fminf(v[q], sqdist(px[q], py[q], pz[q], sx[j - 1], sy[j - 1], sz[j - 1]));
+        hits[q] += v[q] >= smm[j + 1] ? 1 : 0;
+      }
+      bad = bad || hits[q] != 0;
     }
-    bad = hits != 0;
   }
-  bad = __syncthreads_or(bad);
-  if (t == 0) verdict[(size_t)b * m + slice] = bad ? -1 : 0;
+  return __syncthreads_or(bad) != 0;
 }
+
+// A/B and test builds (-DPN2_CHAIN_ONE_LAUNCH=0): the check as a launch of its own before
+// fps_chain_kernel, whose hot-set stages then sample the clouds that fail it. One workgroup
+// per (slice of kPrefixPts points, cloud) stores its verdict, 0 (holds) or -1, in word `slice`
+// of the cloud's stage-0 idx row, which the chain kernel reads before it writes that row.
+#ifndef PN2_CHAIN_ONE_LAUNCH
+#define PN2_CHAIN_ONE_LAUNCH 1
+#endif
+#if !PN2_CHAIN_ONE_LAUNCH
+constexpr int kPrefixPts = 256;
+
+__global__ __launch_bounds__(kPrefixPts) void fps_prefix_check_kernel(
+    const float* __restrict__ xyz, int n, int m, int32_t* __restrict__ verdict) {
+  __shared__ __attribute__((aligned(16))) float lds[kPrefixLds];
+  const int b = blockIdx.y, slice = blockIdx.x;
+  const bool bad = prefix_check_fails<kPrefixPts, 1>(xyz + (size_t)b * n * 3, n, m,
+                                                     slice * kPrefixPts, lds);
+  if (threadIdx.x == 0) verdict[(size_t)b * m + slice] = bad ? -1 : 0;
+}
+#else
+
+// ---- the chain over sampler output in ONE launch: check, then copies or samplers ----------
+// One workgroup of kPrefixBlock threads per cloud, no state outside it. The whole cloud's
+// check (prefix_check_fails, kChainNext / kPrefixBlock points a thread); if it holds, every
+// stage's idx = 0 .. m - 1 and new_xyz = the input's first m points. If it fails, the stages
+// run as samplers on the block-scan bodies (chain_stage_scan: the picks of the hot-set
+// schedule bit for bit) by the first kChainBlock threads -- the other waves end first, and a
+// barrier counts only the waves still running. Stage 0 samples an LDS copy of the cloud in
+// the check's arrays (dead by then); a later stage samples the previous stage's picks from the
+// other part of those arrays when they fit (else from that stage's new_xyz in global memory,
+// written by this workgroup before the barrier between the stages). Slower than the hot-set
+// chain, and run only by clouds with ties, duplicates or non-finite coordinates.
+#ifndef PN2_PREFIX_BLOCK
+#define PN2_PREFIX_BLOCK 512
+#endif
+constexpr int kPrefixBlock = PN2_PREFIX_BLOCK;
+static_assert(kPrefixBlock >= kChainBlock && kPrefixBlock <= kChainNext &&
+                  kChainNext % kPrefixBlock == 0 && kPrefixBlock % kWave == 0,
+              "whole waves, every point of a cloud on one thread");
+
+// (8 waves a SIMD = 64 VGPRs, so that a workgroup fits beside the side kernels' on a busy CU;
+// four points a thread need more)
+constexpr int kPrefixWaves = kPrefixBlock >= 512 ? 8 : 5;
+
+__global__ __launch_bounds__(kPrefixBlock, kPrefixWaves) void fps_chain_prefix_kernel(
+    const float* __restrict__ xyz, FpsChain c) {
+  __shared__ __attribute__((aligned(16))) float lds[kPrefixLds];
+  __shared__ uint2 red[2][8];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const float* __restrict__ P = xyz + (size_t)b * c.n[0] * 3;
+  if (!prefix_check_fails<kPrefixBlock, kChainNext / kPrefixBlock>(P, c.n[0], c.m[0], 0, lds)) {
+    for (int i = 0; i < c.stages; ++i) {
+      int32_t* I = c.idx[i] + (size_t)b * c.m[i];
+      float* NX = c.nx[i] + (size_t)b * c.m[i] * 3;
+      for (int e = t; e < c.m[i]; e += kPrefixBlock) I[e] = e;
+      for (int e = t; e < 3 * c.m[i]; e += kPrefixBlock) NX[e] = P[e];
+    }
+    return;
+  }
+  if (t >= kChainBlock) return;
+  float* sa = lds;                    // a stage's input: up to kChainNext points
+  float* sb = lds + 3 * kChainNext;   // ... or up to kSbPts
+  constexpr int kSbPts = (kPrefixLds - 3 * kChainNext) / 3;
+  for (int e = t; e < 3 * c.n[0]; e += kChainBlock) sa[e] = P[e];
+  __syncthreads();
+  const float* in = sa;
+  for (int i = 0; i < c.stages; ++i) {
+    float* NX = c.nx[i] + (size_t)b * c.m[i] * 3;
+    float* next = nullptr;  // stage i + 1's input in LDS: the array stage i does not read
+    if (i + 1 < c.stages) next = in != sa ? sa : c.m[i] <= kSbPts ? sb : nullptr;
+    chain_stage_scan(in, c.n[i], c.m[i], in, c.idx[i] + (size_t)b * c.m[i], NX, next, red);
+    __syncthreads();  // stage i's output complete before stage i + 1 reads it
+    in = next ? next : NX;
+  }
+}
+#endif
 
 __global__ __launch_bounds__(kChainBlock) void fps_chain_kernel(const float* __restrict__ xyz,
                                                                 FpsChain c) {
@@ -884,6 +976,14 @@ int fps_chain_launch(const float* xyz, int B, int N, int nstages, const int* npo
       n = c.m[i];
     }
   }
+#if PN2_CHAIN_ONE_LAUNCH
+  // stages that can be prefixes of their input: the check and its outcome in one launch
+  c.verdicts = 0;
+  if (nested && c.m[0] >= 2)
+    hipLaunchKernelGGL(fps_chain_prefix_kernel, dim3(B), dim3(kPrefixBlock), 0, s, xyz, c);
+  else
+    hipLaunchKernelGGL(fps_chain_kernel, dim3(B), dim3(kChainBlock), 0, s, xyz, c);
+#else
   // the prefix check (fps_prefix_check_kernel) when the verdict words fit the stage-0 row
   const int slices = (c.n[0] + kPrefixPts - 1) / kPrefixPts;
   c.verdicts = nested && c.m[0] >= 2 && c.m[0] >= slices ? slices : 0;
@@ -891,6 +991,7 @@ int fps_chain_launch(const float* xyz, int B, int N, int nstages, const int* npo
     hipLaunchKernelGGL(fps_prefix_check_kernel, dim3(slices, B), dim3(kPrefixPts), 0, s, xyz,
                        c.n[0], c.m[0], c.idx[0]);
   hipLaunchKernelGGL(fps_chain_kernel, dim3(B), dim3(kChainBlock), 0, s, xyz, c);
+#endif
   if (grid0) {  // stage 0 ran inside the chain kernel: its picks' grid as a launch after it
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;

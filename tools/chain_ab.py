@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """A/B of the fused SSG sampler chain's tail (pn2_fps_chain on the SA1 output: 1024 -> 256 ->
 64 -> 16, what the step's lane-4 task runs) for alternative builds of libpn2hip.so (--lib
-NAME=PATH), index-exact against the product build, HIP events, B = 16 ScanNet crops."""
+NAME=PATH), index-exact against the product build, HIP events, B = 16 ScanNet crops.
+--ties: point 700 of every cloud a copy of pick 200, so every cloud fails the prefix check and
+its stages run as samplers (the fallback's cost)."""
 import argparse, ctypes, importlib, json, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -11,6 +13,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", action="append", default=[])
     ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--ties", action="store_true")
     args = ap.parse_args()
     import torch
     pkg = importlib.import_module("pointcloud-segmentation-attention_amd")
@@ -18,6 +21,8 @@ def main():
     B = 16
     x = torch.from_numpy(pkg.synth.batch(range(B), 8192, "scannet")[0]).to(dev)
     _, x1 = pkg.tf_sampling.farthest_point_sample_and_gather(1024, x)
+    if args.ties:
+        x1[:, 700] = x1[:, 200]
     libs = {"product": pkg._lib.lib()}
     for spec in args.lib:
         n, pth = spec.split("=", 1)
@@ -53,7 +58,8 @@ def main():
             b.synchronize()
             if r >= 3:
                 times[n].append(a.elapsed_time(b) * 1e3)
-    print(json.dumps({"us": {n: round(statistics.median(v), 1) for n, v in times.items()},
+    print(json.dumps({"ties": args.ties, "us": {n: round(statistics.median(v), 1) for n, v in times.items()},
+                      "min_us": {n: round(min(v), 1) for n, v in times.items()},
                       "exact_vs_product": exact}))
     return 0 if exact else 1
 
