@@ -50,6 +50,12 @@
  *                                                                  pn2cpu_dropout (host)
  *   get_loss             pointnet2_sem_seg.py:62-69 (tf.losses.    → pn2_softmax_xent_fwd,
  *                        sparse_softmax_cross_entropy + weights)   pn2_softmax_xent_bwd
+ *   tf.train.AdamOptimizer attention_points/train.py:318-319 (TF 1.x → pn2_adam_step,
+ *                        ApplyAdam, no Nesterov)                   pn2cpu_adam_step (host)
+ *   get_metrics          attention_points/train.py:145-163         → pn2_seg_confusion,
+ *                        (accuracy over the annotated points,      pn2_mean_iou,
+ *                        streaming tf.metrics.mean_iou)            pn2cpu_seg_confusion,
+ *                                                                  pn2cpu_mean_iou (host)
  *   get_subset          scannet_dataset/data_transformation.py  → pn2_scene_bbox,
  *                        :70-154 (training crop sampler)           pn2_crop_sample
  *   whole-scene chunker  scannet_dataset/complete_scene_loader.py → pn2_subvolume_select,
@@ -669,6 +675,79 @@ int pn2_softmax_xent_fwd(const float* logits, const int32_t* labels, const float
 int pn2_softmax_xent_bwd(const float* grad_loss, const float* logits, const int32_t* labels,
                          const float* weights, const float* lse, const int32_t* num_present,
                          long long rows, int C, float* grad_logits, pn2_stream_t stream);
+
+/* ---------------------------------------------------------------- optimiser and metrics ---- */
+/* What the reference's training loop (attention_points/train.py:288-387) runs once the
+ * gradients exist: tf.train.AdamOptimizer and get_metrics. csrc/optim.hip, with host twins in
+ * csrc/cpu_optim.cpp. */
+
+/* One variable of an Adam step: the parameter p, its gradient g and the two slot variables
+ * m (<var>/Adam) and v (<var>/Adam_1), n floats each. */
+typedef struct {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  long long n;
+} pn2_adam_slot;
+#define PN2_ADAM_SLOTS 64   /* slots per launch: the by-value argument block stays <= 4096 bytes */
+#define PN2_ADAM_CHUNK 2048 /* elements one workgroup updates                                    */
+#define PN2_ADAM_MAX_N (1LL << 35) /* largest n of one slot                                      */
+
+/* TF 1.x ApplyAdam without Nesterov (training_ops.cc), over `nslots` variables. Per element, in
+ * fp32, every operation rounded on its own (no contraction), in this order:
+ *   omb1 = 1 - beta1;  omb2 = 1 - beta2
+ *   m' = m + (g - m) * omb1
+ *   v' = v + (g * g - v) * omb2
+ *   p' = p - (alpha * m') / (sqrt(v') + epsilon)
+ * The caller folds both bias corrections into the step size, alpha = lr * sqrt(1 - beta2^t) /
+ * (1 - beta1^t), so epsilon is added to the uncorrected sqrt(v') (TF's "epsilon hat"; not
+ * torch.optim.Adam's arithmetic). The division and the square root are correctly rounded and
+ * denormals are kept, so the device result equals the host twin bit for bit and does not depend
+ * on the launch shape.
+ * `slots` is a HOST array of device pointers. It travels by value in the kernel arguments,
+ * PN2_ADAM_SLOTS slots per launch: a step is ceil(nslots / PN2_ADAM_SLOTS) launches, with no
+ * device-side table, no allocation, no copy and no synchronisation. A workgroup updates one
+ * PN2_ADAM_CHUNK-element chunk of one slot, with 16-byte loads and stores when the slot's four
+ * pointers are 16-byte aligned and a scalar path when one is not. Slots must not overlap. n = 0
+ * slots are skipped (their pointers may be NULL); nslots = 0 returns 0 without a launch.
+ * PN2_EINVAL, checked before any launch: slots NULL with nslots > 0, nslots < 0, a NULL pointer
+ * in a slot with n > 0, n < 0 or n > PN2_ADAM_MAX_N, beta1 or beta2 outside [0, 1), epsilon < 0
+ * (or NaN), a non-finite alpha. */
+int pn2_adam_step(const pn2_adam_slot* slots, int nslots, float alpha, float beta1, float beta2,
+                  float epsilon, pn2_stream_t stream);
+/* The same function on HOST pointers in plain C++, synchronous: the GPU result equals it bit
+ * for bit. */
+int pn2cpu_adam_step(const pn2_adam_slot* slots, int nslots, float alpha, float beta1,
+                     float beta2, float epsilon);
+
+/* get_metrics (attention_points/train.py:145-163): labels and pred (rows) int32, pred the
+ * argmax that pn2_softmax_xent_fwd returns. For every row with 0 < label < C and 0 <= pred < C:
+ *   confusion[label][pred] += 1      (C,C) int64, the total of tf.metrics.mean_iou
+ *   counts[1] += 1                   the assigned points
+ *   counts[0] += (pred == label)     the correct ones: accuracy = counts[0] / counts[1]
+ * Other rows are ignored: label 0 is "unannotated", and a value out of range is never used as
+ * an index. Both outputs are ADDED to (the caller zeroes them). Each workgroup counts
+ * PN2_CONFUSION_BLOCK_ROWS rows into a C x C histogram of 32-bit counters in LDS and adds its
+ * non-zero cells with 64-bit integer atomic adds: integer adds commute, two runs give equal
+ * bits. 0 < C <= PN2_METRICS_MAX_C, 0 <= rows (below 2^31 workgroups' worth); rows = 0 returns
+ * 0 without a launch. */
+#define PN2_METRICS_MAX_C 64
+#define PN2_CONFUSION_BLOCK_ROWS 2048
+int pn2_seg_confusion(const int32_t* labels, const int32_t* pred, long long rows, int C,
+                      long long* confusion, long long* counts, pn2_stream_t stream);
+/* tf.metrics.mean_iou's value of a (C,C) confusion matrix, one small launch: per class c, den =
+ * row_sum[c] + col_sum[c] - cm[c][c]; classes with den = 0 are left out; iou_c = cm[c][c] / den
+ * in double; *iou = the double sum in class order over the number of classes with den > 0,
+ * rounded to fp32, or 0 when there is none; per_class[c] (C floats, may be NULL) = iou_c as
+ * fp32, 0 where den = 0. TensorFlow divides in fp32, so its last bit can differ. */
+int pn2_mean_iou(const long long* confusion, int C, float* iou, float* per_class,
+                 pn2_stream_t stream);
+/* The same two functions on HOST pointers in plain C++, synchronous: equal integers, equal
+ * fp32 bits. */
+int pn2cpu_seg_confusion(const int32_t* labels, const int32_t* pred, long long rows, int C,
+                         long long* confusion, long long* counts);
+int pn2cpu_mean_iou(const long long* confusion, int C, float* iou, float* per_class);
 
 /* ---------------------------------------------------------------- scene crops ---------- */
 

@@ -29,7 +29,7 @@ _impl = importlib.import_module("pointcloud-segmentation-attention_amd")
 
 MODULES = ("tf_sampling", "tf_grouping", "tf_interpolate", "pointnet_util", "tf_util",
            "attention_layer", "data_transformation", "complete_scene_loader", "grid", "stack",
-           "shard", "synth")
+           "shard", "synth", "pointnet2_sem_seg", "pointnet2_sem_seg_features", "train")
 for _name in MODULES:
     _mod = getattr(_impl, _name)
     globals()[_name] = _mod
@@ -39,7 +39,10 @@ lib = _impl.lib
 LIB_PATH = _impl.LIB_PATH
 InvalidArgumentError = _impl.InvalidArgumentError
 Pn2RuntimeError = _impl.Pn2RuntimeError
-
+# the training loop's names (train.py): pn2hip.AdamOptimizer, pn2hip.train_step, ...
+TRAIN_NAMES = ("AdamOptimizer", "SegMetrics", "get_learning_rate", "get_bn_decay", "train_step")
+for _name in TRAIN_NAMES:
+    globals()[_name] = getattr(_impl.train, _name)
 
 
 def __getattr__(name):
@@ -66,5 +69,5 @@ def install_reference_names():
     return done
 
 
-__all__ = list(MODULES) + ["ops", "lib", "LIB_PATH", "InvalidArgumentError", "Pn2RuntimeError",
+__all__ = list(MODULES) + list(TRAIN_NAMES) + ["ops", "lib", "LIB_PATH", "InvalidArgumentError", "Pn2RuntimeError",
                            "install_reference_names"]

@@ -65,6 +65,17 @@ bits); autograd is registered for `points`, `points1` and `points2`, never for c
     fp_apply_train_grad(grad_out, dist, idx, m, C2, C1) -> (grad_points2 (B, m, C2),
                          grad_points1 (B, n, C1)); bit-equal to the reference's CPU
                          ThreeInterpolateGrad loop
+
+and what the training loop runs once the gradients exist (csrc/optim.hip; attention_points/
+train.py:145-163, :337), none of it differentiable:
+
+    adam_step(params, grads, exp_avg, exp_avg_sq, alpha, beta1, beta2, epsilon)   TF 1.x ApplyAdam
+                         over the four tensor lists, in place, alpha = lr * sqrt(1 - beta2^t) /
+                         (1 - beta1^t): ceil(len / 64) launches
+    seg_confusion(labels, pred, confusion, counts)      adds the rows with 0 < label < C to the
+                         int64 (C, C) confusion matrix and to counts = (correct, assigned)
+    mean_iou(confusion)                                 tf.metrics.mean_iou's value
+                                                         -> (iou, per_class)
 """
 import importlib
 
@@ -77,7 +88,8 @@ NAMES = ("farthest_point_sample", "farthest_point_sample_and_gather", "gather_po
          "group_pool", "mlp_layer_train", "mlp_layer_train_grad", "mlp_layer_train_pool",
          "mlp_layer_train_pool_grad", "attn_kv_train", "attn_kv_train_grad", "bn_train",
          "bn_train_grad", "dropout", "softmax_xent", "softmax_xent_grad", "group_concat_train",
-         "group_concat_train_grad", "fp_apply_train", "fp_apply_train_grad")
+         "group_concat_train_grad", "fp_apply_train", "fp_apply_train_grad", "adam_step",
+         "seg_confusion", "mean_iou")
 for _n in NAMES:
     globals()[_n] = getattr(_ops, _n)
 

@@ -10,6 +10,10 @@ Drop-in modules (reference names, argument order, shapes, dtypes, error messages
   tf_util         conv2d / conv1d (1x1), dropout, sparse_softmax_cross_entropy, ParamStore,
                   SharedMLP
   pointnet2_sem_seg      get_model, get_loss (the SSG segmentation model and its weighted loss)
+  pointnet2_sem_seg_features  get_model(point_cloud, features, ...): the same model on points
+                         that carry features
+  train                  get_learning_rate, get_bn_decay, AdamOptimizer, SegMetrics, train_step
+                         (attention_points/train.py's optimiser, schedules and metrics)
   data_transformation    get_subset (the ScanNet crop sampler) on the GPU
   complete_scene_loader  the whole-scene chunker (selection + gathers on the GPU)
   attention_layer attention_reduce, AttentionLayer
@@ -19,8 +23,11 @@ The directory name has hyphens, so import it with importlib:
     pn2 = importlib.import_module("pointcloud-segmentation-attention_amd")
 """
 from . import attention_layer, complete_scene_loader, data_transformation, grid, plan, pointnet2_sem_seg, \
-    pointnet_util, shard, stack, synth, tf_grouping, tf_interpolate, tf_sampling, tf_util
+    pointnet2_sem_seg_features, pointnet_util, shard, stack, synth, tf_grouping, tf_interpolate, tf_sampling, \
+    tf_util, train
+from .train import AdamOptimizer, SegMetrics, get_bn_decay, get_learning_rate, train_step
 from ._lib import LIB_PATH, InvalidArgumentError, Pn2RuntimeError, lib
 
 __all__ = ["tf_sampling", "tf_grouping", "tf_interpolate", "pointnet_util", "attention_layer", "grid", "tf_util", "data_transformation", "complete_scene_loader",
-           "synth", "stack", "shard", "plan", "pointnet2_sem_seg", "lib", "LIB_PATH", "InvalidArgumentError", "Pn2RuntimeError"]
+           "synth", "stack", "shard", "plan", "pointnet2_sem_seg", "pointnet2_sem_seg_features", "train",
+           "AdamOptimizer", "SegMetrics", "get_learning_rate", "get_bn_decay", "train_step", "lib", "LIB_PATH", "InvalidArgumentError", "Pn2RuntimeError"]

@@ -80,6 +80,19 @@ class AttnLayer(ctypes.Structure):
 
 PN2_ATTN_MAX_LAYERS = 4
 
+
+class AdamSlot(ctypes.Structure):
+    """struct pn2_adam_slot (include/pn2hip.h)."""
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p),
+                ("v", ctypes.c_void_p), ("n", ctypes.c_longlong)]
+
+
+PN2_ADAM_SLOTS = 64
+PN2_ADAM_CHUNK = 2048
+PN2_ADAM_MAX_N = 1 << 35
+PN2_METRICS_MAX_C = 64
+PN2_CONFUSION_BLOCK_ROWS = 2048
+
 # name -> (restype, argtypes); mirrors include/pn2hip.h and include/pn2plan.h (tests/test_capi.py checks the header)
 SIGNATURES = {
     "pn2_version": (ctypes.c_char_p, []),
@@ -165,6 +178,12 @@ SIGNATURES = {
     "pn2_softmax_xent_workspace_size": (_S, [_LL]),
     "pn2_softmax_xent_fwd": (_I, [_P, _P, _P, _LL, _I, _P, _P, _P, _P, _P, _S, _P]),
     "pn2_softmax_xent_bwd": (_I, [_P, _P, _P, _P, _P, _P, _LL, _I, _P, _P]),
+    "pn2_adam_step": (_I, [_P, _I, _F, _F, _F, _F, _P]),
+    "pn2cpu_adam_step": (_I, [_P, _I, _F, _F, _F, _F]),
+    "pn2_seg_confusion": (_I, [_P, _P, _LL, _I, _P, _P, _P]),
+    "pn2_mean_iou": (_I, [_P, _I, _P, _P, _P]),
+    "pn2cpu_seg_confusion": (_I, [_P, _P, _LL, _I, _P, _P]),
+    "pn2cpu_mean_iou": (_I, [_P, _I, _P, _P]),
     "pn2_scene_workspace_size": (_S, [_I]),
     "pn2_scene_bbox": (_I, [_P, _I, _P, _P, _S, _P]),
     "pn2_crop_workspace_size": (_S, [_I, _I, _I]),

@@ -945,6 +945,111 @@ Tensor softmax_xent_grad_hip(const Tensor& grad_loss_, const Tensor& logits_, co
   return grad;
 }
 
+// ---- optimiser and metrics (csrc/optim.hip): tf.train.AdamOptimizer's ApplyAdam over every
+// variable in ceil(n / PN2_ADAM_SLOTS) launches, get_metrics' confusion matrix and counts, and
+// tf.metrics.mean_iou's value (attention_points/train.py:145-163, :337). None is differentiable.
+void chk_adam(at::TensorList params, at::TensorList grads, at::TensorList exp_avg,
+              at::TensorList exp_avg_sq) {
+  const size_t n = params.size();
+  TORCH_CHECK_VALUE(grads.size() == n && exp_avg.size() == n && exp_avg_sq.size() == n,
+                    "adam_step expects four lists of one length, got ", n, ", ", grads.size(), ", ",
+                    exp_avg.size(), ", ", exp_avg_sq.size());
+  for (size_t i = 0; i < n; ++i) {
+    const Tensor* t[4] = {&params[i], &grads[i], &exp_avg[i], &exp_avg_sq[i]};
+    const char* name[4] = {"params", "grads", "exp_avg", "exp_avg_sq"};
+    for (int k = 0; k < 4; ++k) {
+      TORCH_CHECK_VALUE(t[k]->scalar_type() == at::kFloat, "adam_step expects float32 tensors, got ",
+                        t[k]->scalar_type(), " in ", name[k], "[", i, "]");
+      TORCH_CHECK_VALUE(t[k]->is_contiguous(), "adam_step expects contiguous tensors: ", name[k],
+                        "[", i, "] is not");
+      TORCH_CHECK_VALUE(t[k]->numel() == params[i].numel(), "adam_step expects ", name[k], "[", i,
+                        "] with the ", params[i].numel(), " elements of params[", i, "], got ",
+                        t[k]->numel());
+      TORCH_CHECK_VALUE(t[k]->device() == params[0].device(),
+                        "adam_step expects every tensor on one device: ", name[k], "[", i,
+                        "] is on ", t[k]->device(), ", params[0] on ", params[0].device());
+    }
+  }
+}
+int64_t chk_confusion(const Tensor& confusion, const char* op) {
+  TORCH_CHECK_VALUE(confusion.scalar_type() == at::kLong && confusion.dim() == 2 &&
+                        confusion.size(0) == confusion.size(1) && confusion.size(0) > 0 &&
+                        confusion.size(0) <= PN2_METRICS_MAX_C && confusion.is_contiguous(),
+                    op, " expects a contiguous int64 (C, C) confusion with 0 < C <= ",
+                    PN2_METRICS_MAX_C, ", got ", confusion.scalar_type(), " ", confusion.sizes());
+  return confusion.size(0);
+}
+void chk_seg_confusion(const Tensor& labels, const Tensor& pred, const Tensor& confusion,
+                       const Tensor& counts) {
+  const char* op = "seg_confusion";
+  TORCH_CHECK_VALUE(labels.scalar_type() == at::kInt && pred.scalar_type() == at::kInt, op,
+                    " expects int32 labels and pred, got ", labels.scalar_type(), " and ",
+                    pred.scalar_type());
+  TORCH_CHECK_VALUE(labels.sizes() == pred.sizes(), op, " expects labels and pred of one shape: ",
+                    "labels ", labels.sizes(), ", pred ", pred.sizes());
+  chk_confusion(confusion, op);
+  TORCH_CHECK_VALUE(counts.scalar_type() == at::kLong && counts.dim() == 1 && counts.size(0) == 2 &&
+                        counts.is_contiguous(),
+                    op, " expects int64 (2,) counts, got ", counts.scalar_type(), " ",
+                    counts.sizes());
+  TORCH_CHECK_VALUE(pred.device() == labels.device() && confusion.device() == labels.device() &&
+                        counts.device() == labels.device(),
+                    op, " expects every tensor on one device");
+}
+
+// the mutated tensors' in-place version counters advance, as for torch's own in-place ops
+// (tf_util.ParamStore.stamp keys the packed inference layers on them)
+void bump(const Tensor& t) { t.unsafeGetTensorImpl()->bump_version(); }
+
+void adam_step_hip(at::TensorList params, at::TensorList grads, at::TensorList exp_avg,
+                   at::TensorList exp_avg_sq, double alpha, double beta1, double beta2,
+                   double epsilon) {
+  chk_adam(params, grads, exp_avg, exp_avg_sq);
+  if (params.empty()) return;
+  std::vector<pn2_adam_slot> slots(params.size());
+  for (size_t i = 0; i < params.size(); ++i) {
+    TORCH_CHECK(params[i].is_cuda(), "params[", i, "] is on ", params[i].device(),
+                ": pn2hip ops run on the MI355X only (no CPU fallback)");
+    slots[i] = {params[i].data_ptr<float>(), grads[i].data_ptr<float>(),
+                exp_avg[i].data_ptr<float>(), exp_avg_sq[i].data_ptr<float>(), params[i].numel()};
+  }
+  c10::hip::HIPGuard g(params[0].device().index());
+  check_rc(pn2_adam_step(slots.data(), I(static_cast<int64_t>(slots.size())),
+                         static_cast<float>(alpha), static_cast<float>(beta1),
+                         static_cast<float>(beta2), static_cast<float>(epsilon),
+                         stream_of(params[0])), "adam_step");
+  for (size_t i = 0; i < params.size(); ++i) {
+    bump(params[i]);
+    bump(exp_avg[i]);
+    bump(exp_avg_sq[i]);
+  }
+}
+
+void seg_confusion_hip(const Tensor& labels_, const Tensor& pred_, const Tensor& confusion,
+                       const Tensor& counts) {
+  chk_seg_confusion(labels_, pred_, confusion, counts);
+  Tensor labels = dev(labels_, "labels", at::kInt), pred = dev(pred_, "pred", at::kInt);
+  c10::hip::HIPGuard g(labels.device().index());
+  check_rc(pn2_seg_confusion(Ii(labels), Ii(pred), labels.numel(), I(confusion.size(0)),
+                             reinterpret_cast<long long*>(confusion.data_ptr<int64_t>()),
+                             reinterpret_cast<long long*>(counts.data_ptr<int64_t>()),
+                             stream_of(labels)), "seg_confusion");
+  bump(confusion);
+  bump(counts);
+}
+
+std::tuple<Tensor, Tensor> mean_iou_hip(const Tensor& confusion) {
+  const int64_t C = chk_confusion(confusion, "mean_iou");
+  TORCH_CHECK(confusion.is_cuda(), "confusion is on ", confusion.device(),
+              ": pn2hip ops run on the MI355X only (no CPU fallback)");
+  c10::hip::HIPGuard g(confusion.device().index());
+  Tensor iou = at::empty({}, f32(confusion)), per_class = at::empty({C}, f32(confusion));
+  check_rc(pn2_mean_iou(reinterpret_cast<const long long*>(confusion.data_ptr<int64_t>()), I(C),
+                        iou.data_ptr<float>(), per_class.data_ptr<float>(), stream_of(confusion)),
+           "mean_iou");
+  return {iou, per_class};
+}
+
 // ---- training-mode geometry (csrc/geom_train.hip): the fused forward kernels of the SA and FP
 // modules with their gradients as ordered gathers (no float atomics, no zero fill, no slices)
 void chk_group_concat_grad(const Tensor& grad, const Tensor& idx, int64_t N, int64_t C,
@@ -1283,6 +1388,18 @@ Tensor softmax_xent_grad_meta(const Tensor& grad_loss, const Tensor& logits, con
   chk_xent_grad(grad_loss, logits, labels, weights, lse, num_present, "softmax_xent_grad");
   return at::empty(logits.sizes(), mf(logits));
 }
+void adam_step_meta(at::TensorList params, at::TensorList grads, at::TensorList exp_avg,
+                    at::TensorList exp_avg_sq, double, double, double, double) {
+  chk_adam(params, grads, exp_avg, exp_avg_sq);
+}
+void seg_confusion_meta(const Tensor& labels, const Tensor& pred, const Tensor& confusion,
+                        const Tensor& counts) {
+  chk_seg_confusion(labels, pred, confusion, counts);
+}
+std::tuple<Tensor, Tensor> mean_iou_meta(const Tensor& confusion) {
+  const int64_t C = chk_confusion(confusion, "mean_iou");
+  return {at::empty({}, mf(confusion)), at::empty({C}, mf(confusion))};
+}
 Tensor group_concat_train_meta(const Tensor& xyz, const std::optional<Tensor>& points,
                                const Tensor& new_xyz, const Tensor& idx, bool use_xyz,
                                bool xyz_last) {
@@ -1511,6 +1628,10 @@ TORCH_LIBRARY(pn2, m) {
         "(Tensor loss, Tensor lse, Tensor pred, Tensor num_present)");
   m.def("softmax_xent_grad(Tensor grad_loss, Tensor logits, Tensor labels, Tensor? weights, "
         "Tensor lse, Tensor num_present) -> Tensor");
+  m.def("adam_step(Tensor(a!)[] params, Tensor[] grads, Tensor(b!)[] exp_avg, "
+        "Tensor(c!)[] exp_avg_sq, float alpha, float beta1, float beta2, float epsilon) -> ()");
+  m.def("seg_confusion(Tensor labels, Tensor pred, Tensor(a!) confusion, Tensor(b!) counts) -> ()");
+  m.def("mean_iou(Tensor confusion) -> (Tensor, Tensor)");
   m.def("group_concat_train(Tensor xyz, Tensor? points, Tensor new_xyz, Tensor idx, bool use_xyz, "
         "bool xyz_last) -> Tensor");
   m.def("group_concat_train_grad(Tensor grad_new_points, Tensor idx, int N, int C, int col0) -> "
@@ -1552,6 +1673,9 @@ TORCH_LIBRARY_IMPL(pn2, CUDA, m) {
   m.impl("dropout", &dropout_hip);
   m.impl("softmax_xent", &softmax_xent_hip);
   m.impl("softmax_xent_grad", &softmax_xent_grad_hip);
+  m.impl("adam_step", &adam_step_hip);
+  m.impl("seg_confusion", &seg_confusion_hip);
+  m.impl("mean_iou", &mean_iou_hip);
   m.impl("group_concat_train", &group_concat_train_hip);
   m.impl("group_concat_train_grad", &group_concat_train_grad_hip);
   m.impl("fp_apply_train", &fp_apply_train_hip);
@@ -1602,6 +1726,9 @@ TORCH_LIBRARY_IMPL(pn2, Meta, m) {
   m.impl("dropout", &dropout_meta);
   m.impl("softmax_xent", &softmax_xent_meta);
   m.impl("softmax_xent_grad", &softmax_xent_grad_meta);
+  m.impl("adam_step", &adam_step_meta);
+  m.impl("seg_confusion", &seg_confusion_meta);
+  m.impl("mean_iou", &mean_iou_meta);
   m.impl("group_concat_train", &group_concat_train_meta);
   m.impl("group_concat_train_grad", &group_concat_train_grad_meta);
   m.impl("fp_apply_train", &fp_apply_train_meta);

@@ -22,13 +22,15 @@ FP_LAYERS = (("fa_layer1", [256, 256]), ("fa_layer2", [256, 256]), ("fa_layer3",
              ("fa_layer4", [128, 128, 128]))
 
 
-def get_model(point_cloud, is_training, num_class, bn_decay=None, params=None):
-    """Semantic-segmentation PointNet++: point_cloud (B, N, 3) -> (logits (B, N, num_class),
-    end_points with 'l0_xyz' and 'feats', the fc1 output). Extra keyword `params`: the
-    ParamStore (default: tf_util.default_store())."""
+def model_body(point_cloud, l0_points, is_training, num_class, bn_decay=None, params=None,
+               seed=None):
+    """The layers of get_model, shared with pointnet2_sem_seg_features.get_model: l0_points is
+    None here and the per-point features (B, N, C) there (attention_points/models/
+    pointnet2_sem_seg_features.py:25). `seed`: the dropout seed (tf_util.dropout), None to draw
+    one from torch's CPU generator."""
     store = params if params is not None else tf_util.default_store()
     end_points = {"l0_xyz": point_cloud}
-    xyz, points = [point_cloud], [None]
+    xyz, points = [point_cloud], [l0_points]
     for scope, npoint, radius, nsample, mlp in SA_LAYERS:
         new_xyz, new_points, _ = pointnet_sa_module(
             xyz[-1], points[-1], npoint, radius, nsample, mlp, None, False, is_training, bn_decay,
@@ -42,12 +44,19 @@ def get_model(point_cloud, is_training, num_class, bn_decay=None, params=None):
     net = tf_util.conv1d(points[0], 128, 1, "fc1", padding="VALID", bn=True,
                          is_training=is_training, bn_decay=bn_decay, params=store)
     end_points["feats"] = net
-    net = tf_util.dropout(net, is_training, "dp1", keep_prob=0.5)
+    net = tf_util.dropout(net, is_training, "dp1", keep_prob=0.5, seed=seed)
     # the reference calls fc2 without is_training; here the flag selects the training layer, and
     # without it fc2's variables would never learn on a trainable store
     net = tf_util.conv1d(net, num_class, 1, "fc2", padding="VALID", activation_fn=None,
                          is_training=is_training, params=store)
     return net, end_points
+
+
+def get_model(point_cloud, is_training, num_class, bn_decay=None, params=None):
+    """Semantic-segmentation PointNet++: point_cloud (B, N, 3) -> (logits (B, N, num_class),
+    end_points with 'l0_xyz' and 'feats', the fc1 output). Extra keyword `params`: the
+    ParamStore (default: tf_util.default_store())."""
+    return model_body(point_cloud, None, is_training, num_class, bn_decay, params)
 
 
 def get_loss(pred, label, smpw):

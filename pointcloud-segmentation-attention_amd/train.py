@@ -1,0 +1,220 @@
+"""attention_points/train.py: what the reference's training loop (:288-387) runs around the
+model, on the gfx950 kernels of csrc/optim.hip.
+
+    get_learning_rate, get_bn_decay   the two staircase schedules (:27-58), Python floats
+    AdamOptimizer                     tf.train.AdamOptimizer (:337): TF 1.x ApplyAdam over every
+                                      variable in ceil(n / 64) launches (torch.ops.pn2.adam_step)
+    SegMetrics                        get_metrics (:145-163): the accuracy over the annotated
+                                      points and the streaming tf.metrics.mean_iou
+    train_step                        one step: forward, weighted loss, backward, Adam, metrics
+
+A loop written against this module never reads the device back inside a step:
+
+    store = tf_util.ParamStore(seed=0).trainable("cuda")
+    opt, metrics = AdamOptimizer(store), SegMetrics(21)
+    for batch, (xyz, feats, labels, smpw) in enumerate(loader):
+        loss, counts = train_step(store, opt, metrics, xyz, labels, smpw, 21,
+                                  bn_decay=get_bn_decay(batch),
+                                  learning_rate=get_learning_rate(batch), features=feats)
+    mean_iou, per_class = metrics.iou()
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _torch_ops
+from .pointnet2_sem_seg import model_body
+from .tf_util import ParamStore
+
+BATCH_SIZE = 16         # train.py:17
+N_TRAIN_SAMPLES = 1201  # train.py:15, the number of train scenes
+DECAY_EPOCHS = 80       # train.py:37, :54: decay_steps = N_TRAIN_SAMPLES * 80
+
+
+def _staircase(batch, batch_size, n_train_samples):
+    """tf.train.exponential_decay's exponent with staircase=True."""
+    return (int(batch) * int(batch_size)) // (int(n_train_samples) * DECAY_EPOCHS)
+
+
+def get_learning_rate(batch, batch_size=BATCH_SIZE, n_train_samples=N_TRAIN_SAMPLES):
+    """train.py:27-41: 1e-3 * 0.7 ** k with k = (batch * batch_size) // (n_train_samples * 80),
+    clipped from below at 1e-5."""
+    return max(1e-3 * 0.7 ** _staircase(batch, batch_size, n_train_samples), 1e-5)
+
+
+def get_bn_decay(batch, batch_size=BATCH_SIZE, n_train_samples=N_TRAIN_SAMPLES):
+    """train.py:44-58: min(0.99, 1 - 0.5 * 0.5 ** k) with get_learning_rate's k."""
+    return min(0.99, 1 - 0.5 * 0.5 ** _staircase(batch, batch_size, n_train_samples))
+
+
+class AdamOptimizer:
+    """tf.train.AdamOptimizer(learning_rate, beta1, beta2, epsilon) on torch.ops.pn2.adam_step
+    (csrc/optim.hip: TF 1.x ApplyAdam without Nesterov).
+
+    `params`: an iterable of leaves (store.parameters()) or a tf_util.ParamStore. Given a store,
+    the slot variables carry the reference's names (<var>/Adam, <var>/Adam_1) and a variable the
+    model creates after construction is picked up at the next step() with zero slots.
+
+    step() folds both bias corrections into the step size, alpha = lr * sqrt(1 - beta2^t) /
+    (1 - beta1^t), and adds epsilon to the uncorrected sqrt(v): TF's update, not torch.optim.Adam's,
+    which divides sqrt(v) by sqrt(1 - beta2^t) before it adds epsilon. The trajectory's bits are
+    this package's, not TensorFlow's, for two reasons: TF keeps beta1_power and beta2_power as
+    fp32 variables multiplied once per step and computes alpha from them in fp32, while here
+    alpha comes from t in double (beta1 and beta2 rounded to fp32 first, alpha rounded to fp32
+    last); and TF's kernels may contract the update's multiplies and adds, while every operation
+    here rounds on its own (the host twin pn2cpu_adam_step pins the bits)."""
+
+    def __init__(self, params, learning_rate=1e-3, beta1=0.9, beta2=0.999, epsilon=1e-8):
+        self.learning_rate = float(learning_rate)
+        self.beta1 = float(np.float32(beta1))
+        self.beta2 = float(np.float32(beta2))
+        self.epsilon = float(epsilon)
+        if not (0.0 <= self.beta1 < 1.0 and 0.0 <= self.beta2 < 1.0 and self.epsilon >= 0.0):
+            raise ValueError("AdamOptimizer expects beta1 and beta2 in [0, 1) and epsilon >= 0")
+        self.t = 0
+        self.store = params if isinstance(params, ParamStore) else None
+        self._leaves = None if self.store is not None else list(params)
+        self._slots = {}    # name -> (exp_avg, exp_avg_sq)
+        self._loaded = {}   # slots of load_state_dict whose variable does not exist yet
+
+    def named_parameters(self):
+        """(name, leaf) of every trainable variable: the store's TF names, or the position in
+        the list the optimiser was built from."""
+        if self.store is not None:
+            return [(k, v) for k, v in self.store.items() if v.requires_grad]
+        return [(str(i), p) for i, p in enumerate(self._leaves)]
+
+    def _slot(self, name, p):
+        """The slot variables of `name`: loaded ones, or zeros (TF's slot initialiser)."""
+        hit = self._slots.get(name)
+        if hit is None or hit[0].shape != p.shape or hit[0].device != p.device:
+            loaded = self._loaded.pop(name, None)
+            if loaded is not None:
+                hit = tuple(torch.as_tensor(a, dtype=torch.float32).reshape(p.shape).to(
+                    p.device, copy=True).contiguous() for a in loaded)
+            else:
+                hit = (torch.zeros_like(p, memory_format=torch.contiguous_format),
+                       torch.zeros_like(p, memory_format=torch.contiguous_format))
+            self._slots[name] = hit
+        return hit
+
+    def zero_grad(self):
+        """Gradients to None (torch's set_to_none)."""
+        for _, p in self.named_parameters():
+            p.grad = None
+
+    def alpha(self, learning_rate=None):
+        """The step size of step number self.t, rounded to fp32."""
+        lr = self.learning_rate if learning_rate is None else float(learning_rate)
+        return float(np.float32(lr * math.sqrt(1.0 - self.beta2 ** self.t)
+                                / (1.0 - self.beta1 ** self.t)))
+
+    @torch.no_grad()
+    def step(self, learning_rate=None):
+        """One ApplyAdam over every parameter whose .grad is not None, in one adam_step call;
+        the others and their slots stay untouched. `learning_rate` overrides the constructor's
+        for this step (the schedule's value). Nothing synchronises."""
+        self.t += 1
+        params, grads, ms, vs = [], [], [], []
+        for name, p in self.named_parameters():
+            if p.grad is None:
+                continue
+            m, v = self._slot(name, p)
+            params.append(p)
+            grads.append(p.grad.contiguous())
+            ms.append(m)
+            vs.append(v)
+        if params:
+            _torch_ops.call("adam_step", params, grads, ms, vs, self.alpha(learning_rate),
+                            self.beta1, self.beta2, self.epsilon)
+
+    def state_dict(self):
+        """CPU float32 arrays under the reference checkpoint's names: <var>/Adam and
+        <var>/Adam_1 for every variable, beta1_power, beta2_power (beta ** t) and global_step."""
+        d = {}
+        for name, p in self.named_parameters():
+            m, v = self._slot(name, p)
+            d[f"{name}/Adam"] = m.detach().cpu().numpy().copy()
+            d[f"{name}/Adam_1"] = v.detach().cpu().numpy().copy()
+        for name, (m, v) in self._loaded.items():
+            d[f"{name}/Adam"] = np.array(m, dtype=np.float32)
+            d[f"{name}/Adam_1"] = np.array(v, dtype=np.float32)
+        d["beta1_power"] = np.float32(self.beta1 ** self.t)
+        d["beta2_power"] = np.float32(self.beta2 ** self.t)
+        d["global_step"] = np.int64(self.t)
+        return d
+
+    def load_state_dict(self, d):
+        """Restore state_dict()'s arrays (or a reference checkpoint's Adam variables, exported to
+        a dict). t is global_step; the beta powers are not read (they follow from t). Slots of
+        variables that do not exist yet wait until the model creates them."""
+        self.t = int(np.asarray(d["global_step"]))
+        self._slots.clear()
+        self._loaded = {}
+        for key in d:
+            if key.endswith("/Adam"):
+                name = key[:-len("/Adam")]
+                if f"{name}/Adam_1" not in d:
+                    raise KeyError(f"{name}/Adam_1")
+                self._loaded[name] = (np.asarray(d[key], dtype=np.float32),
+                                      np.asarray(d[f"{name}/Adam_1"], dtype=np.float32))
+        for name, p in self.named_parameters():
+            if name in self._loaded:
+                self._slot(name, p)
+
+
+class SegMetrics:
+    """get_metrics' accuracy and mean IoU (train.py:145-163) on torch.ops.pn2.seg_confusion and
+    mean_iou: an int64 (C, C) confusion matrix on the device, accumulated over update() calls
+    like tf.metrics.mean_iou's total_cm. Points with label 0 (unannotated) are left out."""
+
+    def __init__(self, num_classes, device="cuda"):
+        self.num_classes = int(num_classes)
+        self.confusion = torch.zeros(self.num_classes, self.num_classes, dtype=torch.int64,
+                                     device=device)
+
+    def update(self, labels, pred):
+        """Add a batch: labels (...) integer, pred (...) int32 (softmax_xent's argmax). Returns
+        this batch's counts = (correct, assigned) as an int64 device tensor; no
+        synchronisation."""
+        if labels.dtype in (torch.int64, torch.int16, torch.uint8, torch.int8):
+            labels = labels.to(torch.int32)
+        counts = torch.zeros(2, dtype=torch.int64, device=self.confusion.device)
+        _torch_ops.call("seg_confusion", labels, pred, self.confusion, counts)
+        return counts
+
+    @staticmethod
+    def accuracy(counts):
+        """correct / assigned of update()'s counts as a float (reads the device); NaN when
+        nothing is assigned, TensorFlow's 0 / 0."""
+        correct, assigned = (int(c) for c in counts.tolist())
+        return correct / assigned if assigned else float("nan")
+
+    def iou(self):
+        """(mean IoU, per-class IoU (C,)) of everything added since reset(), float32 device
+        tensors: tf.metrics.mean_iou's value. Classes that occur neither as a label nor as a
+        prediction are left out of the mean and read 0 per class."""
+        return tuple(_torch_ops.call("mean_iou", self.confusion))
+
+    def reset(self):
+        self.confusion.zero_()
+
+
+def train_step(store, opt, metrics, point_cloud, labels, smpw, num_class, bn_decay=None,
+               learning_rate=None, features=None, seed=None):
+    """One training step of train.py's loop on a trainable store: zero_grad, the model with
+    is_training=True (pointnet2_sem_seg, or pointnet2_sem_seg_features when `features` (B, N, C)
+    is given), the weighted loss, backward, opt.step(learning_rate), metrics.update with the
+    loss kernel's own argmax (no second pass over the logits). `seed`: the dropout seed, so a
+    step is reproducible. Returns (loss, counts), device tensors: nothing here reads the device
+    back."""
+    opt.zero_grad()
+    logits, _ = model_body(point_cloud, features, True, num_class, bn_decay, store, seed=seed)
+    if labels.dtype in (torch.int64, torch.int16, torch.uint8, torch.int8):
+        labels = labels.to(torch.int32)
+    loss, _, pred, _ = _torch_ops.call("softmax_xent", logits, labels, smpw)
+    loss.backward()
+    opt.step(learning_rate)
+    counts = metrics.update(labels, pred)
+    return loss.detach(), counts
