@@ -60,6 +60,12 @@
  *                        :70-154 (training crop sampler)           pn2_crop_sample
  *   whole-scene chunker  scannet_dataset/complete_scene_loader.py → pn2_subvolume_select,
  *                        :4-117 (subvolume selection, gathers)     pn2_gather_rows
+ *   generate_predictions attention_points/benchmark/             → pn2_scene_vote,
+ *                        generate_predictions.py:139-186 (argmax,   pn2_scene_labels,
+ *                        map_back :19-37, map_to_nyu40 :40-53);     pn2_map_back_rows,
+ *                        benchmark/evaluate.py:58-108 and           pn2_label_lut,
+ *                        data_transformation.py:21-67 (label        pn2cpu_scene_vote, ...
+ *                        look-ups)                                  (host twins)
  *
  * (reference paths are under pointnet2_tensorflow/tf_ops/{sampling,grouping,interpolation_3d},
  *  pointnet2_tensorflow/utils and attention_points/attention_scannet.)
@@ -790,6 +796,72 @@ int pn2_subvolume_select(const float* points, int N, const double* bounds, int S
  * [0, nsrc) reads row 0. */
 int pn2_gather_rows(const void* src, long long nsrc, int row_bytes, const int32_t* idx,
                     long long n, void* dst, pn2_stream_t stream);
+
+/* ---------------------------------------------------------------- scene prediction ----- */
+
+/* What the reference does with a trained model (attention_points/benchmark/
+ * generate_predictions.py:139-186): the argmax of every chunk row's logits and map_back
+ * (:19-37), res = zeros(res_shape); res[orig[mask]] = values[mask], over a scene's
+ * concatenated chunks. numpy writes repeated indices in order, so of the masked rows that name
+ * one point the last row in concatenation order wins. csrc/predict.hip, with host twins in
+ * csrc/cpu_predict.cpp.
+ *
+ * Every scene point holds one 64-bit key, ((global_row + 1) << PN2_VOTE_LABEL_BITS) | label,
+ * 0 = never written, and a voting row applies an unsigned 64-bit atomic max to its point's
+ * key. The largest global row wins, numpy's order; an integer max commutes, so the keys are the
+ * same bits for any launch order, any stream and any split of the scene into batches. */
+#define PN2_VOTE_LABEL_BITS 8
+
+/* One batch of chunk rows votes. logits (rows, C) fp32 or NULL (the label is 0 and C is
+ * ignored: the vote then only records which row wins, for pn2_map_back_rows); mask (rows)
+ * uint8, orig (rows) int32: the chunker's `mask` and `points_orig_idxs`; row0: the global index
+ * of the batch's first row; keys (n_scene) as above, zeroed by the caller once per scene;
+ * pred_rows (rows) int32 or NULL: every row's argmax, voting or not. The argmax takes the lowest
+ * index of a tie (np.argmax); NaN logits are unsupported. Row r votes iff mask[r] != 0 and
+ * 0 <= orig[r] < n_scene; no other row indexes keys (the reference raises IndexError for an
+ * index past the scene and wraps a negative one).
+ * PN2_EINVAL, checked before any launch: C outside [1, 1 << PN2_VOTE_LABEL_BITS] when logits
+ * are given, rows < 0, row0 < 0, row0 + rows >= 2^55 (the key's 56 row bits), n_scene outside
+ * [0, 2^31), a NULL mask, orig or keys. rows = 0 returns 0 without a launch. */
+int pn2_scene_vote(const float* logits, long long rows, int C, const uint8_t* mask,
+                   const int32_t* orig, long long row0, long long n_scene, long long* keys,
+                   int32_t* pred_rows, pn2_stream_t stream);
+/* The keys resolved, each output (n_scene) and optional (NULL):
+ *   labels[p] = key ? key & 255 : 0             int32: the remapped prediction, 0 where unwritten
+ *   winner[p] = key ? (key >> 8) - 1 : -1       int64: the global row that wrote point p
+ *   mapped[p] = 0 <= labels[p] < nlut ? lut[labels[p]] : dflt   (needs lut: map_to_nyu40 in the
+ *               same pass) */
+int pn2_scene_labels(const long long* keys, long long n_scene, const int32_t* lut, int nlut,
+                     int32_t dflt, int32_t* labels, int32_t* mapped, long long* winner,
+                     pn2_stream_t stream);
+/* map_back of any per-row values: values (rows, row_bytes) are the rows [row0, row0 + rows) of
+ * the scene's concatenated chunks, out (n_scene, row_bytes). Per point p with winner w:
+ *   key 0                      out[p] = zero bytes
+ *   row0 <= w < row0 + rows    out[p] = values[w - row0]
+ *   otherwise                  out[p] stays as it is,
+ * so a caller that keeps one batch at a time resolves batch by batch into one `out`. row_bytes
+ * is a multiple of 4, as in pn2_gather_rows; the row0 / rows / n_scene bounds are
+ * pn2_scene_vote's. */
+int pn2_map_back_rows(const void* values, int row_bytes, long long row0, long long rows,
+                      const long long* keys, long long n_scene, void* out, pn2_stream_t stream);
+/* out[i] = 0 <= in[i] < nlut ? lut[in[i]] : dflt over n int32 labels; in == out is allowed. One
+ * kernel for generate_predictions.py's map_to_nyu40 (dict.get(label, 1): dflt = 1),
+ * data_transformation.py's label_map (a 41-entry table, dflt = 0: the reference's
+ * min(label, 40) look-up for every non-negative label) and evaluate.py's two tests against
+ * VALID_CLASS_IDS (ground truth not valid -> 0, prediction not valid -> 40). A negative label
+ * gives dflt, where the reference's gather wraps around or raises. */
+int pn2_label_lut(const int32_t* in, long long n, const int32_t* lut, int nlut, int32_t dflt,
+                  int32_t* out, pn2_stream_t stream);
+/* The same four functions on HOST pointers in plain C++, synchronous: equal bits. */
+int pn2cpu_scene_vote(const float* logits, long long rows, int C, const uint8_t* mask,
+                      const int32_t* orig, long long row0, long long n_scene, long long* keys,
+                      int32_t* pred_rows);
+int pn2cpu_scene_labels(const long long* keys, long long n_scene, const int32_t* lut, int nlut,
+                        int32_t dflt, int32_t* labels, int32_t* mapped, long long* winner);
+int pn2cpu_map_back_rows(const void* values, int row_bytes, long long row0, long long rows,
+                         const long long* keys, long long n_scene, void* out);
+int pn2cpu_label_lut(const int32_t* in, long long n, const int32_t* lut, int nlut, int32_t dflt,
+                     int32_t* out);
 
 #ifdef __cplusplus
 }

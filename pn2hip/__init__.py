@@ -29,7 +29,8 @@ _impl = importlib.import_module("pointcloud-segmentation-attention_amd")
 
 MODULES = ("tf_sampling", "tf_grouping", "tf_interpolate", "pointnet_util", "tf_util",
            "attention_layer", "data_transformation", "complete_scene_loader", "grid", "stack",
-           "shard", "synth", "pointnet2_sem_seg", "pointnet2_sem_seg_features", "train")
+           "shard", "synth", "pointnet2_sem_seg", "pointnet2_sem_seg_features", "train",
+           "generate_predictions", "evaluate")
 for _name in MODULES:
     _mod = getattr(_impl, _name)
     globals()[_name] = _mod
@@ -40,7 +41,8 @@ LIB_PATH = _impl.LIB_PATH
 InvalidArgumentError = _impl.InvalidArgumentError
 Pn2RuntimeError = _impl.Pn2RuntimeError
 # the training loop's names (train.py): pn2hip.AdamOptimizer, pn2hip.train_step, ...
-TRAIN_NAMES = ("AdamOptimizer", "SegMetrics", "get_learning_rate", "get_bn_decay", "train_step")
+TRAIN_NAMES = ("AdamOptimizer", "SegMetrics", "get_learning_rate", "get_bn_decay", "train_step",
+               "eval_step")
 for _name in TRAIN_NAMES:
     globals()[_name] = getattr(_impl.train, _name)
 

@@ -76,6 +76,18 @@ train.py:145-163, :337), none of it differentiable:
                          int64 (C, C) confusion matrix and to counts = (correct, assigned)
     mean_iou(confusion)                                 tf.metrics.mean_iou's value
                                                          -> (iou, per_class)
+
+and whole-scene prediction and the label look-ups of the benchmark score (csrc/predict.hip;
+attention_points/benchmark/generate_predictions.py:19-53, :139-186, evaluate.py:58-83). These
+four are listed in HOST_NAMES, not NAMES: next to the HIP and Meta kernels they have CPU kernels
+(host twins with equal bits), because everything in them is integers and copied bytes:
+
+    scene_vote(logits, mask, orig, row0, keys)          argmax per chunk row and a 64-bit atomic
+                         max of ((row0 + r + 1) << 8) | label into keys[orig[r]] for the masked
+                         rows: numpy's last-write-wins in any launch order   -> pred_rows
+    scene_labels(keys, lut, dflt)                       -> (labels, mapped, winner)
+    map_back_rows(values, row0, keys, out)              out[p] = values[winner(p) - row0]
+    label_lut(inp, lut, dflt)                           0 <= inp < len(lut) ? lut[inp] : dflt
 """
 import importlib
 
@@ -90,7 +102,10 @@ NAMES = ("farthest_point_sample", "farthest_point_sample_and_gather", "gather_po
          "bn_train_grad", "dropout", "softmax_xent", "softmax_xent_grad", "group_concat_train",
          "group_concat_train_grad", "fp_apply_train", "fp_apply_train_grad", "adam_step",
          "seg_confusion", "mean_iou")
-for _n in NAMES:
+# the ops that also run on CPU tensors (every op in NAMES is device-only, three_nn and the two
+# three_interpolate ops excepted)
+HOST_NAMES = ("scene_vote", "scene_labels", "map_back_rows", "label_lut")
+for _n in NAMES + HOST_NAMES:
     globals()[_n] = getattr(_ops, _n)
 
-__all__ = list(NAMES)
+__all__ = list(NAMES + HOST_NAMES)

@@ -92,6 +92,7 @@ PN2_ADAM_CHUNK = 2048
 PN2_ADAM_MAX_N = 1 << 35
 PN2_METRICS_MAX_C = 64
 PN2_CONFUSION_BLOCK_ROWS = 2048
+PN2_VOTE_LABEL_BITS = 8  # include/pn2hip.h
 
 # name -> (restype, argtypes); mirrors include/pn2hip.h and include/pn2plan.h (tests/test_capi.py checks the header)
 SIGNATURES = {
@@ -192,6 +193,14 @@ SIGNATURES = {
     "pn2_subvolume_slices": (_I, [_I]),
     "pn2_subvolume_select": (_I, [_P, _I, _P, _I, ctypes.c_double, _P, _P, _P, _P]),
     "pn2_gather_rows": (_I, [_P, _LL, _I, _P, _LL, _P, _P]),
+    "pn2_scene_vote": (_I, [_P, _LL, _I, _P, _P, _LL, _LL, _P, _P, _P]),
+    "pn2_scene_labels": (_I, [_P, _LL, _P, _I, ctypes.c_int32, _P, _P, _P, _P]),
+    "pn2_map_back_rows": (_I, [_P, _I, _LL, _LL, _P, _LL, _P, _P]),
+    "pn2_label_lut": (_I, [_P, _LL, _P, _I, ctypes.c_int32, _P, _P]),
+    "pn2cpu_scene_vote": (_I, [_P, _LL, _I, _P, _P, _LL, _LL, _P, _P]),
+    "pn2cpu_scene_labels": (_I, [_P, _LL, _P, _I, ctypes.c_int32, _P, _P, _P]),
+    "pn2cpu_map_back_rows": (_I, [_P, _I, _LL, _LL, _P, _LL, _P]),
+    "pn2cpu_label_lut": (_I, [_P, _LL, _P, _I, ctypes.c_int32, _P]),
     # include/pn2plan.h: the native step executor
     "pn2_plan_create": (_P, []),
     "pn2_plan_destroy": (None, [_P]),

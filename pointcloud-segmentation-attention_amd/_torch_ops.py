@@ -13,7 +13,9 @@ stand-alone batch-statistics batch norm (bn_train: x, gamma, beta). The training
 the logits only) and the training-mode geometry ops (csrc/geom_train.hip: group_concat_train,
 the points only; fp_apply_train, points1 and points2) carry their autograd in libpn2torch.so
 itself (csrc/torch_ops.cpp). The optimiser and metrics ops (csrc/optim.hip: adam_step,
-seg_confusion, mean_iou) mutate their arguments in place and are not differentiable.
+seg_confusion, mean_iou) mutate their arguments in place and are not differentiable. The
+prediction ops (csrc/predict.hip: scene_vote, scene_labels, map_back_rows, label_lut) are
+integers and copied bytes; they alone also have CPU kernels (the host twins, equal bits).
 
 The mirror modules (tf_sampling, tf_grouping, tf_interpolate, attention_layer) call these ops
 for every reference-signature call; the pn2hip alias package re-exports them as pn2hip.ops.

@@ -20,7 +20,9 @@
 // CPU kernels exist only for the three ops the reference itself runs on the CPU (ThreeNN,
 // ThreeInterpolate, ThreeInterpolateGrad: registered for DEVICE_CPU only,
 // tf_interpolate.cpp:187,222,262), through the host twins pn2cpu_* (csrc/cpu_interp.cpp);
-// every other op has no CPU kernel, so a CPU tensor fails in the dispatcher (no CPU fallback).
+// and for the four prediction ops (scene_vote, scene_labels, map_back_rows, label_lut: integers
+// and copied bytes, host twins in csrc/cpu_predict.cpp with equal bits); every other op has no
+// CPU kernel, so a CPU tensor fails in the dispatcher (no CPU fallback).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -1050,6 +1052,172 @@ std::tuple<Tensor, Tensor> mean_iou_hip(const Tensor& confusion) {
   return {iou, per_class};
 }
 
+// ---- whole-scene prediction (csrc/predict.hip): the argmax + map_back of
+// attention_points/benchmark/generate_predictions.py as a 64-bit atomic max per scene point, and
+// the label look-ups of map_to_nyu40, label_map and benchmark/evaluate.py. These four ops have
+// CPU kernels too (the host twins of csrc/cpu_predict.cpp: equal bits), so the path from chunk
+// rows to a score runs and is tested without a GPU. `keys` is int64; the kernels read its bits
+// as unsigned (they stay below 2^63).
+const long long* KeysC(const Tensor& t) { return reinterpret_cast<const long long*>(t.data_ptr<int64_t>()); }
+long long* Keys(const Tensor& t) { return reinterpret_cast<long long*>(t.data_ptr<int64_t>()); }
+
+void chk_keys(const Tensor& keys, const char* op) {
+  TORCH_CHECK_VALUE(keys.scalar_type() == at::kLong && keys.dim() == 1 && keys.is_contiguous(), op,
+                    " expects contiguous int64 (n_scene,) keys, got ", keys.scalar_type(), " ",
+                    keys.sizes());
+}
+bool is_byte(const Tensor& t) { return t.scalar_type() == at::kByte || t.scalar_type() == at::kBool; }
+void chk_scene_vote(const std::optional<Tensor>& logits, const Tensor& mask, const Tensor& orig,
+                    int64_t row0, const Tensor& keys) {
+  const char* op = "scene_vote";
+  TORCH_CHECK_VALUE(is_byte(mask) && orig.scalar_type() == at::kInt, op,
+                    " expects uint8 or bool mask and int32 orig, got ", mask.scalar_type(), " and ",
+                    orig.scalar_type());
+  TORCH_CHECK_VALUE(mask.sizes() == orig.sizes(), op, " expects mask and orig of one shape: mask ",
+                    mask.sizes(), ", orig ", orig.sizes());
+  chk_keys(keys, op);
+  TORCH_CHECK_VALUE(row0 >= 0, op, " expects row0 >= 0, got ", row0);
+  TORCH_CHECK_VALUE(orig.device() == mask.device() && keys.device() == mask.device(), op,
+                    " expects every tensor on one device");
+  if (logits.has_value()) {
+    const Tensor& l = *logits;
+    TORCH_CHECK_VALUE(l.scalar_type() == at::kFloat && l.dim() >= 1 && l.size(-1) >= 1 &&
+                          l.size(-1) <= (1 << PN2_VOTE_LABEL_BITS) &&
+                          l.numel() == mask.numel() * l.size(-1),
+                      op, " expects float32 logits (rows, C) with 1 <= C <= ",
+                      (1 << PN2_VOTE_LABEL_BITS), " and mask's ", mask.numel(), " rows, got ",
+                      l.scalar_type(), " ", l.sizes());
+    TORCH_CHECK_VALUE(l.device() == mask.device(), op, " expects every tensor on one device");
+  }
+}
+void chk_lut(const Tensor& lut, const Tensor& like, const char* op) {
+  TORCH_CHECK_VALUE(lut.scalar_type() == at::kInt && lut.dim() == 1, op,
+                    " expects an int32 (nlut,) lut, got ", lut.scalar_type(), " ", lut.sizes());
+  TORCH_CHECK_VALUE(lut.device() == like.device(), op, " expects every tensor on one device");
+}
+void chk_i32_dflt(int64_t dflt, const char* op) {
+  TORCH_CHECK_VALUE(dflt >= INT32_MIN && dflt <= INT32_MAX, op, " expects an int32 dflt, got ", dflt);
+}
+// bytes of one row of values (rows, ...) / out (n_scene, ...)
+int64_t chk_map_back(const Tensor& values, int64_t row0, const Tensor& keys, const Tensor& out) {
+  const char* op = "map_back_rows";
+  chk_keys(keys, op);
+  TORCH_CHECK_VALUE(row0 >= 0, op, " expects row0 >= 0, got ", row0);
+  TORCH_CHECK_VALUE(values.dim() >= 1 && out.dim() == values.dim() &&
+                        out.scalar_type() == values.scalar_type() &&
+                        out.sizes().slice(1) == values.sizes().slice(1) &&
+                        out.size(0) == keys.size(0) && out.is_contiguous(),
+                    op, " expects values (rows, ...) and a contiguous out (n_scene, ...) of one ",
+                    "dtype and row shape, got ", values.scalar_type(), " ", values.sizes(), " and ",
+                    out.scalar_type(), " ", out.sizes(), " for ", keys.size(0), " keys");
+  int64_t row = static_cast<int64_t>(values.element_size());
+  for (int64_t d = 1; d < values.dim(); ++d) row *= values.size(d);
+  TORCH_CHECK_VALUE(row > 0 && row % 4 == 0 && row <= INT32_MAX, op,
+                    " expects rows of a multiple of 4 bytes, got ", row);
+  TORCH_CHECK_VALUE(keys.device() == values.device() && out.device() == values.device(), op,
+                    " expects every tensor on one device");
+  return row;
+}
+const uint8_t* Bytes(const Tensor& t) { return static_cast<const uint8_t*>(t.data_ptr()); }
+
+template <bool HIP>
+Tensor scene_vote_impl(const std::optional<Tensor>& logits_, const Tensor& mask_,
+                       const Tensor& orig_, int64_t row0, const Tensor& keys) {
+  chk_scene_vote(logits_, mask_, orig_, row0, keys);
+  TORCH_CHECK(HIP ? mask_.is_cuda() : mask_.device().is_cpu(), "scene_vote: mask is on ",
+              mask_.device());
+  Tensor mask = mask_.contiguous(), orig = orig_.contiguous(), logits;
+  int C = 0;
+  if (logits_.has_value()) {
+    logits = logits_->contiguous();
+    C = I(logits.size(-1));
+  }
+  Tensor pred = at::empty(mask.sizes(), i32(mask));
+  const long long rows = mask.numel(), n = keys.size(0);
+  if (HIP) {
+    c10::hip::HIPGuard g(mask.device().index());
+    check_rc(pn2_scene_vote(F(logits), rows, C, Bytes(mask), Ii(orig), row0, n, Keys(keys),
+                            pred.data_ptr<int32_t>(), stream_of(mask)), "scene_vote");
+  } else {
+    check_rc(pn2cpu_scene_vote(F(logits), rows, C, Bytes(mask), Ii(orig), row0, n, Keys(keys),
+                               pred.data_ptr<int32_t>()), "scene_vote");
+  }
+  bump(keys);
+  return pred;
+}
+
+template <bool HIP>
+std::tuple<Tensor, Tensor, Tensor> scene_labels_impl(const Tensor& keys,
+                                                     const std::optional<Tensor>& lut_,
+                                                     int64_t dflt) {
+  const char* op = "scene_labels";
+  chk_keys(keys, op);
+  chk_i32_dflt(dflt, op);
+  TORCH_CHECK(HIP ? keys.is_cuda() : keys.device().is_cpu(), "scene_labels: keys is on ",
+              keys.device());
+  Tensor lut;
+  if (lut_.has_value()) {
+    chk_lut(*lut_, keys, op);
+    lut = lut_->contiguous();
+  }
+  const long long n = keys.size(0);
+  Tensor labels = at::empty({n}, i32(keys)), winner = at::empty({n}, keys.options());
+  Tensor mapped = at::empty({lut.defined() ? n : 0}, i32(keys));
+  const int32_t* lp = lut.defined() ? Ii(lut) : nullptr;
+  const int nlut = lut.defined() ? I(lut.numel()) : 0;
+  int32_t* mp = lut.defined() ? mapped.data_ptr<int32_t>() : nullptr;
+  if (HIP) {
+    c10::hip::HIPGuard g(keys.device().index());
+    check_rc(pn2_scene_labels(KeysC(keys), n, lp, nlut, static_cast<int32_t>(dflt),
+                              labels.data_ptr<int32_t>(), mp, Keys(winner), stream_of(keys)), op);
+  } else {
+    check_rc(pn2cpu_scene_labels(KeysC(keys), n, lp, nlut, static_cast<int32_t>(dflt),
+                                 labels.data_ptr<int32_t>(), mp, Keys(winner)), op);
+  }
+  return {labels, mapped, winner};
+}
+
+template <bool HIP>
+void map_back_rows_impl(const Tensor& values_, int64_t row0, const Tensor& keys,
+                        const Tensor& out) {
+  const int64_t row = chk_map_back(values_, row0, keys, out);
+  TORCH_CHECK(HIP ? keys.is_cuda() : keys.device().is_cpu(), "map_back_rows: keys is on ",
+              keys.device());
+  Tensor values = values_.contiguous();
+  const long long rows = values.size(0), n = keys.size(0);
+  if (HIP) {
+    c10::hip::HIPGuard g(keys.device().index());
+    check_rc(pn2_map_back_rows(values.data_ptr(), I(row), row0, rows, KeysC(keys), n,
+                               out.data_ptr(), stream_of(keys)), "map_back_rows");
+  } else {
+    check_rc(pn2cpu_map_back_rows(values.data_ptr(), I(row), row0, rows, KeysC(keys), n,
+                                  out.data_ptr()), "map_back_rows");
+  }
+  bump(out);
+}
+
+template <bool HIP>
+Tensor label_lut_impl(const Tensor& inp_, const Tensor& lut_, int64_t dflt) {
+  const char* op = "label_lut";
+  TORCH_CHECK_VALUE(inp_.scalar_type() == at::kInt, op, " expects int32 inp, got ",
+                    inp_.scalar_type());
+  chk_lut(lut_, inp_, op);
+  chk_i32_dflt(dflt, op);
+  TORCH_CHECK(HIP ? inp_.is_cuda() : inp_.device().is_cpu(), "label_lut: inp is on ",
+              inp_.device());
+  Tensor inp = inp_.contiguous(), lut = lut_.contiguous();
+  Tensor out = at::empty(inp.sizes(), i32(inp));
+  if (HIP) {
+    c10::hip::HIPGuard g(inp.device().index());
+    check_rc(pn2_label_lut(Ii(inp), inp.numel(), Ii(lut), I(lut.numel()),
+                           static_cast<int32_t>(dflt), out.data_ptr<int32_t>(), stream_of(inp)), op);
+  } else {
+    check_rc(pn2cpu_label_lut(Ii(inp), inp.numel(), Ii(lut), I(lut.numel()),
+                              static_cast<int32_t>(dflt), out.data_ptr<int32_t>()), op);
+  }
+  return out;
+}
+
 // ---- training-mode geometry (csrc/geom_train.hip): the fused forward kernels of the SA and FP
 // modules with their gradients as ordered gathers (no float atomics, no zero fill, no slices)
 void chk_group_concat_grad(const Tensor& grad, const Tensor& idx, int64_t N, int64_t C,
@@ -1400,6 +1568,31 @@ std::tuple<Tensor, Tensor> mean_iou_meta(const Tensor& confusion) {
   const int64_t C = chk_confusion(confusion, "mean_iou");
   return {at::empty({}, mf(confusion)), at::empty({C}, mf(confusion))};
 }
+Tensor scene_vote_meta(const std::optional<Tensor>& logits, const Tensor& mask, const Tensor& orig,
+                       int64_t row0, const Tensor& keys) {
+  chk_scene_vote(logits, mask, orig, row0, keys);
+  return at::empty(mask.sizes(), mi(mask));
+}
+std::tuple<Tensor, Tensor, Tensor> scene_labels_meta(const Tensor& keys,
+                                                     const std::optional<Tensor>& lut,
+                                                     int64_t dflt) {
+  chk_keys(keys, "scene_labels");
+  chk_i32_dflt(dflt, "scene_labels");
+  if (lut.has_value()) chk_lut(*lut, keys, "scene_labels");
+  const int64_t n = keys.size(0);
+  return {at::empty({n}, mi(keys)), at::empty({lut.has_value() ? n : 0}, mi(keys)),
+          at::empty({n}, keys.options())};
+}
+void map_back_rows_meta(const Tensor& values, int64_t row0, const Tensor& keys, const Tensor& out) {
+  chk_map_back(values, row0, keys, out);
+}
+Tensor label_lut_meta(const Tensor& inp, const Tensor& lut, int64_t dflt) {
+  TORCH_CHECK_VALUE(inp.scalar_type() == at::kInt, "label_lut expects int32 inp, got ",
+                    inp.scalar_type());
+  chk_lut(lut, inp, "label_lut");
+  chk_i32_dflt(dflt, "label_lut");
+  return at::empty(inp.sizes(), mi(inp));
+}
 Tensor group_concat_train_meta(const Tensor& xyz, const std::optional<Tensor>& points,
                                const Tensor& new_xyz, const Tensor& idx, bool use_xyz,
                                bool xyz_last) {
@@ -1639,6 +1832,11 @@ TORCH_LIBRARY(pn2, m) {
   m.def("fp_apply_train(Tensor dist, Tensor idx, Tensor? points1, Tensor points2) -> Tensor");
   m.def("fp_apply_train_grad(Tensor grad_out, Tensor dist, Tensor idx, int m, int C2, int C1) -> "
         "(Tensor, Tensor)");
+  m.def("scene_vote(Tensor? logits, Tensor mask, Tensor orig, int row0, Tensor(a!) keys) -> Tensor");
+  m.def("scene_labels(Tensor keys, Tensor? lut, int dflt) -> "
+        "(Tensor labels, Tensor mapped, Tensor winner)");
+  m.def("map_back_rows(Tensor values, int row0, Tensor keys, Tensor(a!) out) -> ()");
+  m.def("label_lut(Tensor inp, Tensor lut, int dflt) -> Tensor");
 }
 
 // ROCm builds of PyTorch dispatch HIP tensors under the CUDA key.
@@ -1680,6 +1878,10 @@ TORCH_LIBRARY_IMPL(pn2, CUDA, m) {
   m.impl("group_concat_train_grad", &group_concat_train_grad_hip);
   m.impl("fp_apply_train", &fp_apply_train_hip);
   m.impl("fp_apply_train_grad", &fp_apply_train_grad_hip);
+  m.impl("scene_vote", &scene_vote_impl<true>);
+  m.impl("scene_labels", &scene_labels_impl<true>);
+  m.impl("map_back_rows", &map_back_rows_impl<true>);
+  m.impl("label_lut", &label_lut_impl<true>);
 }
 
 TORCH_LIBRARY_IMPL(pn2, Autograd, m) {
@@ -1693,6 +1895,11 @@ TORCH_LIBRARY_IMPL(pn2, CPU, m) {
   m.impl("three_nn", &three_nn_cpu);
   m.impl("three_interpolate", &three_interpolate_cpu);
   m.impl("three_interpolate_grad", &three_interpolate_grad_cpu);
+  // the prediction ops' host twins (csrc/cpu_predict.cpp)
+  m.impl("scene_vote", &scene_vote_impl<false>);
+  m.impl("scene_labels", &scene_labels_impl<false>);
+  m.impl("map_back_rows", &map_back_rows_impl<false>);
+  m.impl("label_lut", &label_lut_impl<false>);
 }
 
 TORCH_LIBRARY_IMPL(pn2, Meta, m) {
@@ -1733,4 +1940,8 @@ TORCH_LIBRARY_IMPL(pn2, Meta, m) {
   m.impl("group_concat_train_grad", &group_concat_train_grad_meta);
   m.impl("fp_apply_train", &fp_apply_train_meta);
   m.impl("fp_apply_train_grad", &fp_apply_train_grad_meta);
+  m.impl("scene_vote", &scene_vote_meta);
+  m.impl("scene_labels", &scene_labels_meta);
+  m.impl("map_back_rows", &map_back_rows_meta);
+  m.impl("label_lut", &label_lut_meta);
 }

@@ -10,9 +10,15 @@ torch.Generator, and for the same draws the result is the reference's.
 Reference quirk kept: the validity test divides the labelled-point count by
 reduce_sum(ones_like(cur_points)) = 3 n (the (n, 3) tensor, :113), so no try is ever valid and
 every crop is the LAST try's column.
+
+label_map, label_map_numpy and label_map_more_parameters (:25-67) map a scene's NYU-40 label ids
+to 0..20 through torch.ops.pn2.label_lut (csrc/predict.hip), the look-up kernel that
+generate_predictions.map_to_nyu40 and evaluate.evaluate_scan share.
 """
+import numpy as np
 import torch
 
+from . import _torch_ops
 from ._lib import InvalidArgumentError, check, device_tensor, lib, ptr, stream_of
 
 LABEL_WEIGHTS = [0, 2.743064592944318, 3.0830506790927132, 4.785754459526457, 4.9963745147506184,
@@ -22,6 +28,39 @@ LABEL_WEIGHTS = [0, 2.743064592944318, 3.0830506790927132, 4.785754459526457, 4.
                  5.422955391988761, 5.433705358072363, 5.417426773812747,
                  4.870172044153657]  # data_transformation.py:82-86
 TRIES = 10  # :138-141
+# :21-22, the NYU-40 ids of the 20 ScanNet classes -> 1..20; every other id -> 0
+LABEL_MAP = {1: 1, 2: 2, 3: 3, 4: 4, 5: 5, 6: 6, 7: 7, 8: 8, 9: 9, 10: 10, 11: 11, 12: 12, 14: 13,
+             16: 14, 24: 15, 28: 16, 33: 17, 34: 18, 36: 19, 39: 20}
+LABEL_LUT = [LABEL_MAP.get(i, 0) for i in range(41)]  # :36, :53
+
+
+def _label_lut(labels):
+    """LABEL_LUT over int32 labels on their device (torch.ops.pn2.label_lut; CPU tensors run the
+    host twin). A label past 40 gives 0, which is the reference's map[min(label, 40)]; a negative
+    label gives 0 too, where the reference's gather wraps around (numpy) or raises (TF)."""
+    lut = torch.tensor(LABEL_LUT, dtype=torch.int32, device=labels.device)
+    return _torch_ops.call("label_lut", labels.to(torch.int32), lut, 0)
+
+
+def label_map(points, labels, colors, normals):
+    """:25-39: the labels of a scene from NYU-40 ids to 0..20, tensors (the TF function);
+    points, colors and normals pass through. Returns (points, mapped labels int32, colors,
+    normals)."""
+    return points, _label_lut(labels), colors, normals
+
+
+def label_map_numpy(points, labels, colors, normals):
+    """:42-56: label_map on numpy arrays; the mapped labels are int64 as the reference's
+    np.array of Python ints."""
+    mapped = label_map_more_parameters(labels)
+    return points, mapped, colors, normals
+
+
+def label_map_more_parameters(labels):
+    """:59-67: LABEL_MAP.get(label, 0) over an array of labels, int64."""
+    a = np.asarray(labels)
+    t = torch.from_numpy(np.ascontiguousarray(np.clip(a, -1, 2 ** 31 - 1).astype(np.int32)))
+    return _label_lut(t).numpy().astype(np.int64).reshape(a.shape)
 
 
 def scene_bbox(points):

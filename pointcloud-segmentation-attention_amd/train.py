@@ -7,6 +7,8 @@ model, on the gfx950 kernels of csrc/optim.hip.
     SegMetrics                        get_metrics (:145-163): the accuracy over the annotated
                                       points and the streaming tf.metrics.mean_iou
     train_step                        one step: forward, weighted loss, backward, Adam, metrics
+    eval_step                         one validation batch (eval_model, :221-285): the inference
+                                      path, the same loss and metrics, nothing updated
 
 A loop written against this module never reads the device back inside a step:
 
@@ -218,3 +220,18 @@ def train_step(store, opt, metrics, point_cloud, labels, smpw, num_class, bn_dec
     opt.step(learning_rate)
     counts = metrics.update(labels, pred)
     return loss.detach(), counts
+
+
+@torch.no_grad()
+def eval_step(store, metrics, point_cloud, labels, smpw, num_class, features=None):
+    """One batch of train.py's validation pass (eval_model, :221-285): train_step without
+    zero_grad, backward and the optimiser, with is_training=False, so the model runs its inference
+    path on the moving statistics and no variable of the store changes. The weighted loss and the
+    metrics are train_step's: softmax_xent's loss and argmax, metrics.update. Returns (loss,
+    counts), device tensors: nothing here reads the device back."""
+    logits, _ = model_body(point_cloud, features, False, num_class, None, store)
+    if labels.dtype in (torch.int64, torch.int16, torch.uint8, torch.int8):
+        labels = labels.to(torch.int32)
+    loss, _, pred, _ = _torch_ops.call("softmax_xent", logits, labels, smpw)
+    counts = metrics.update(labels, pred)
+    return loss, counts
