@@ -1,0 +1,849 @@
+"""GPU: the gradient of the whole training-mode model against float64.
+
+The training-mode model (pointnet2_sem_seg.model_body, the body of both get_models, called
+directly because it takes the dropout seed, as train_step calls it) + get_loss + backward() on a
+fresh trainable store, for
+
+  (a) pointnet2_sem_seg, 21 classes, no input features (layer 1 groups coordinates only and FP4
+      has no points1),
+  (b) pointnet2_sem_seg_features, 6 feature channels as a leaf, 4 classes (the features' gradient
+      is the sum of SA1's grouping gradient and FP4's concat gradient),
+  (c) an attention stack assembled from the package's modules: pointnet_sa_module_attention,
+      pointnet_sa_module_attention_and_pooling, two pointnet_fp_modules, fc1, dropout, fc2
+      (model_train_ref.attention_spec): the gradient that enters attn_kv_train_grad comes from an
+      FP module and a skip connection together,
+
+each at B = 2, N = 2048, bn_decay 0.8, an explicit dropout seed, labels with a fifth of zeros and
+weights that are 0 there and on a further 10 % of the rows.
+
+The reference is tests/model_train_ref.py (checked without a GPU by
+tests/test_model_train_ref_cpu.py): plain torch on the CPU in float64, and in float32 as the
+yardstick, on the discrete choices a recording spy around _torch_ops.call took from the GPU's
+own forward. Compared: logits, end_points["feats"], the loss, the gradient of every variable, the
+gradient of the input features, every moving mean and variance (0.8 * initial + 0.2 * batch
+statistic), with the project's rule, that of tests/test_gpu_mlp_train.py::assert_close, stated
+once in Comparisons.close with the factor as a parameter
+
+    max |gpu - f64|  <=  max(4 * max |fp32 - f64|,  1e-6 * (1 + max |f64|))
+
+(case (c): 8 in place of 4, for the reason and under the condition written down below).
+Every comparison prints err, err32 and tol; all of a case's comparisons run before the test fails
+on any of them, and the activations of every layer are printed next to the reference's (not
+asserted: the place to look first when a bound is exceeded).
+
+What the record must show: every SA grouping whose points carry a gradient runs
+group_concat_train (4 in (b); 3 in (a), whose layer 1 has no points, so nothing there asks for a
+gradient and the no-grad kernel runs), every FP module fp_apply_train, every SSG SA module
+mlp_layer_train_pool, and neither atomic gradient (group_point_grad, three_interpolate_grad)
+runs; (c) runs attn_kv_train and bn_train twice each.
+
+train_step: on a second store with the same initial values, forward + loss + backward by hand
+and optim_cases.numpy_adam (alpha of step 1, zero slots, float32) give every variable that
+train_step left in the first store bit for bit, and the same moving statistics.
+
+The factor of case (c). Case (c) ran four times on the MI355X. Its largest ratio was each time
+that of the gradient of layer1's query kernel, layer1/ScannetAttentionLayer/dense/kernel:
+
+    run   err = max |gpu - f64|   err32 = max |fp32 - f64|   err / err32
+    1     2.21e-06                5.44e-07                   4.07   (over the project's 4)
+    2     2.21e-06                6.18e-07                   3.58
+    3     2.21e-06                6.04e-07                   3.67
+    4     2.21e-06                5.57e-07                   3.98   (with the factor 8 in place)
+
+The GPU's error is the same in all of them; the float32 yardstick is torch's threaded CPU
+arithmetic and moves with the host. Run 1 is the one that justifies the factor. Of it, the
+eight largest ratios were kept: 4.07 (that kernel), 2.61 (layer1/ScannetAttentionLayer/dense/
+bias), 2.59 (layer1/conv0/bn/gamma), 2.01 (the input features), 1.84 (layer1/
+ScannetAttentionLayer/dense_1/kernel), 1.71 and 1.66 (layer1/conv2/bn/beta and gamma), 1.62
+(layer2/conv2/weights). The table of all 92 tensors further down is run 2's. The
+op is not at fault: attention_ops_alone compares every attn_kv_train_grad call of the backward
+with the reference fed the GPU's own recorded inputs to that call, under the project's factor 4
+(measured: at most 0.16 of the tolerance, which there is the 1e-6 floor), and the layer
+activations printed for the case stay at the float32 reference's own error from the first layer
+to the last. What the whole model shows is float32 rounding that reaches the op through the FP
+chain and the skip connection. So case (c), and only it, uses the factor 8 (at most twice the
+largest measured ratio, 4.07); cases (a) and (b) keep 4 (largest measured ratios 2.62 and 1.35),
+and so does every comparison of the op alone. The per-tensor ratios of case (c) follow the
+yardstick table.
+
+The float32 yardstick: max |fp32 - f64| of the reference with the decisions of its own float64
+forward, and the largest float64 magnitude, per compared tensor (the moving statistics are 0.2 of
+the batch statistics listed). Printed by tests/test_model_train_ref_cpu.py -s; measured at commit
+ee545c1 plus these tests.
+
+case (a): tensor, max |fp32 - f64|, max |f64|
+    logits                                                0.000147      11.7
+    feats                                                 0.000113      6.05
+    loss                                                  1.36e-07      10.7
+    layer1/conv0/bn batch mean                            1.44e-10  0.000856
+    layer1/conv0/bn batch variance                        3.92e-11  0.000421
+    layer1/conv1/bn batch mean                            3.16e-08     0.329
+    layer1/conv1/bn batch variance                        1.76e-08     0.151
+    layer1/conv2/bn batch mean                            9.92e-08     0.747
+    layer1/conv2/bn batch variance                        7.33e-08     0.632
+    layer2/conv0/bn batch mean                            1.87e-07      2.12
+    layer2/conv0/bn batch variance                        5.63e-07      2.35
+    layer2/conv1/bn batch mean                            9.66e-08     0.777
+    layer2/conv1/bn batch variance                        2.21e-07     0.899
+    layer2/conv2/bn batch mean                            1.62e-07     0.947
+    layer2/conv2/bn batch variance                        9.03e-08     0.534
+    layer3/conv0/bn batch mean                            4.35e-07      2.78
+    layer3/conv0/bn batch variance                        4.64e-07      1.86
+    layer3/conv1/bn batch mean                            1.86e-07      1.12
+    layer3/conv1/bn batch variance                        1.83e-07     0.746
+    layer3/conv2/bn batch mean                            1.49e-07     0.911
+    layer3/conv2/bn batch variance                         1.5e-07     0.511
+    layer4/conv0/bn batch mean                            9.58e-07      2.92
+    layer4/conv0/bn batch variance                        1.05e-06      1.18
+    layer4/conv1/bn batch mean                            3.33e-07      1.52
+    layer4/conv1/bn batch variance                        1.08e-06     0.908
+    layer4/conv2/bn batch mean                            3.33e-07     0.916
+    layer4/conv2/bn batch variance                        7.34e-07     0.561
+    fa_layer1/conv_0/bn batch mean                        3.48e-06      4.84
+    fa_layer1/conv_0/bn batch variance                    3.95e-06      2.06
+    fa_layer1/conv_1/bn batch mean                         3.7e-07      1.17
+    fa_layer1/conv_1/bn batch variance                    1.39e-06     0.654
+    fa_layer2/conv_0/bn batch mean                        7.85e-07      2.84
+    fa_layer2/conv_0/bn batch variance                    2.05e-06      1.18
+    fa_layer2/conv_1/bn batch mean                        2.61e-07      1.25
+    fa_layer2/conv_1/bn batch variance                    1.53e-06     0.807
+    fa_layer3/conv_0/bn batch mean                        4.58e-07      2.42
+    fa_layer3/conv_0/bn batch variance                    1.39e-06     0.999
+    fa_layer3/conv_1/bn batch mean                        2.39e-07       1.4
+    fa_layer3/conv_1/bn batch variance                    8.88e-07      1.11
+    fa_layer4/conv_0/bn batch mean                        3.45e-07      1.06
+    fa_layer4/conv_0/bn batch variance                    7.96e-07     0.524
+    fa_layer4/conv_1/bn batch mean                        1.96e-07      1.07
+    fa_layer4/conv_1/bn batch variance                    1.23e-06     0.524
+    fa_layer4/conv_2/bn batch mean                        1.81e-07       1.1
+    fa_layer4/conv_2/bn batch variance                    8.26e-07     0.517
+    fc1/bn batch mean                                     2.53e-07       1.1
+    fc1/bn batch variance                                  1.1e-06     0.663
+    grad layer1/conv0/weights                             5.47e-05      4.78
+    grad layer1/conv0/biases                              0.000187  7.07e-13
+    grad layer1/conv0/bn/gamma                            1.62e-05      1.93
+    grad layer1/conv0/bn/beta                             2.93e-05      2.75
+    grad layer1/conv1/weights                             3.95e-05      4.68
+    grad layer1/conv1/biases                              8.34e-06  1.48e-14
+    grad layer1/conv1/bn/gamma                            6.54e-06      1.35
+    grad layer1/conv1/bn/beta                             8.45e-06       1.1
+    grad layer1/conv2/weights                             3.27e-05      2.22
+    grad layer1/conv2/biases                              4.11e-06   5.4e-15
+    grad layer1/conv2/bn/gamma                            7.52e-06     0.594
+    grad layer1/conv2/bn/beta                             2.17e-06     0.403
+    grad layer2/conv0/weights                              1.2e-05      1.69
+    grad layer2/conv0/biases                               3.2e-07  8.05e-16
+    grad layer2/conv0/bn/gamma                            5.55e-06      0.47
+    grad layer2/conv0/bn/beta                             4.16e-06     0.395
+    grad layer2/conv1/weights                             8.87e-06      0.91
+    grad layer2/conv1/biases                              5.07e-07  7.08e-16
+    grad layer2/conv1/bn/gamma                            3.28e-06     0.444
+    grad layer2/conv1/bn/beta                             3.52e-06     0.382
+    grad layer2/conv2/weights                             7.12e-06      1.12
+    grad layer2/conv2/biases                              2.42e-07  3.82e-16
+    grad layer2/conv2/bn/gamma                            2.48e-06     0.346
+    grad layer2/conv2/bn/beta                             4.55e-07    0.0697
+    grad layer3/conv0/weights                             5.05e-06     0.583
+    grad layer3/conv0/biases                              9.31e-08  1.84e-16
+    grad layer3/conv0/bn/gamma                            1.57e-06     0.241
+    grad layer3/conv0/bn/beta                             1.22e-06      0.14
+    grad layer3/conv1/weights                              2.7e-06     0.391
+    grad layer3/conv1/biases                               8.2e-08  1.94e-16
+    grad layer3/conv1/bn/gamma                            1.11e-06     0.159
+    grad layer3/conv1/bn/beta                             1.23e-06     0.115
+    grad layer3/conv2/weights                             2.02e-06     0.306
+    grad layer3/conv2/biases                               6.8e-08  1.11e-16
+    grad layer3/conv2/bn/gamma                            7.44e-07    0.0909
+    grad layer3/conv2/bn/beta                             1.55e-07    0.0251
+    grad layer4/conv0/weights                             1.51e-06     0.156
+    grad layer4/conv0/biases                              3.45e-08  6.25e-17
+    grad layer4/conv0/bn/gamma                            4.61e-07    0.0667
+    grad layer4/conv0/bn/beta                             3.19e-07    0.0402
+    grad layer4/conv1/weights                             1.37e-06     0.133
+    grad layer4/conv1/biases                              2.79e-08  8.13e-17
+    grad layer4/conv1/bn/gamma                            4.54e-07    0.0568
+    grad layer4/conv1/bn/beta                             2.62e-07    0.0308
+    grad layer4/conv2/weights                             1.55e-06     0.112
+    grad layer4/conv2/biases                              2.24e-08  3.82e-17
+    grad layer4/conv2/bn/gamma                            3.38e-07    0.0287
+    grad layer4/conv2/bn/beta                             8.24e-08   0.00896
+    grad fa_layer1/conv_0/weights                         9.45e-07     0.112
+    grad fa_layer1/conv_0/biases                          5.59e-09  1.21e-17
+    grad fa_layer1/conv_0/bn/gamma                        4.43e-07    0.0338
+    grad fa_layer1/conv_0/bn/beta                         2.16e-07    0.0258
+    grad fa_layer1/conv_1/weights                         8.49e-07    0.0781
+    grad fa_layer1/conv_1/biases                          5.82e-09  1.91e-17
+    grad fa_layer1/conv_1/bn/gamma                        3.51e-07     0.031
+    grad fa_layer1/conv_1/bn/beta                         1.98e-07     0.029
+    grad fa_layer2/conv_0/weights                         9.59e-07     0.116
+    grad fa_layer2/conv_0/biases                          9.31e-09  2.08e-17
+    grad fa_layer2/conv_0/bn/gamma                         3.7e-07    0.0379
+    grad fa_layer2/conv_0/bn/beta                         1.75e-07    0.0282
+    grad fa_layer2/conv_1/weights                         6.82e-07    0.0691
+    grad fa_layer2/conv_1/biases                          7.45e-09  1.73e-17
+    grad fa_layer2/conv_1/bn/gamma                        2.63e-07    0.0278
+    grad fa_layer2/conv_1/bn/beta                            2e-07    0.0237
+    grad fa_layer3/conv_0/weights                          6.9e-07     0.089
+    grad fa_layer3/conv_0/biases                          8.38e-09  1.73e-17
+    grad fa_layer3/conv_0/bn/gamma                        2.92e-07    0.0307
+    grad fa_layer3/conv_0/bn/beta                         1.93e-07     0.024
+    grad fa_layer3/conv_1/weights                         5.74e-07    0.0578
+    grad fa_layer3/conv_1/biases                          1.02e-08  1.65e-17
+    grad fa_layer3/conv_1/bn/gamma                        3.05e-07      0.04
+    grad fa_layer3/conv_1/bn/beta                         2.18e-07    0.0388
+    grad fa_layer4/conv_0/weights                         5.31e-07    0.0564
+    grad fa_layer4/conv_0/biases                          1.02e-08  2.26e-17
+    grad fa_layer4/conv_0/bn/gamma                        2.81e-07    0.0266
+    grad fa_layer4/conv_0/bn/beta                         1.85e-07    0.0209
+    grad fa_layer4/conv_1/weights                         4.95e-07    0.0558
+    grad fa_layer4/conv_1/biases                          9.31e-09  1.47e-17
+    grad fa_layer4/conv_1/bn/gamma                        2.77e-07    0.0241
+    grad fa_layer4/conv_1/bn/beta                         1.22e-07    0.0188
+    grad fa_layer4/conv_2/weights                          5.4e-07    0.0544
+    grad fa_layer4/conv_2/biases                          1.02e-08  1.47e-17
+    grad fa_layer4/conv_2/bn/gamma                        3.36e-07    0.0208
+    grad fa_layer4/conv_2/bn/beta                          8.2e-08     0.022
+    grad fc1/weights                                      4.71e-07    0.0298
+    grad fc1/biases                                       1.75e-08   2.3e-17
+    grad fc1/bn/gamma                                     3.52e-07    0.0739
+    grad fc1/bn/beta                                      1.33e-07    0.0725
+    grad fc2/weights                                      7.42e-07      0.15
+    grad fc2/biases                                       1.34e-07     0.202
+
+case (b): tensor, max |fp32 - f64|, max |f64|
+    logits                                                0.000116       8.6
+    feats                                                 7.87e-05      8.64
+    loss                                                  8.01e-07      4.93
+    grad input features                                   4.26e-06     0.381
+    layer1/conv0/bn batch mean                            4.75e-08     0.501
+    layer1/conv0/bn batch variance                        1.46e-08     0.141
+    layer1/conv1/bn batch mean                            1.19e-07      1.29
+    layer1/conv1/bn batch variance                        8.74e-08     0.958
+    layer1/conv2/bn batch mean                            1.19e-07     0.821
+    layer1/conv2/bn batch variance                        4.74e-08     0.392
+    layer2/conv0/bn batch mean                            3.07e-07      1.94
+    layer2/conv0/bn batch variance                        3.03e-07      1.48
+    layer2/conv1/bn batch mean                            9.81e-08     0.774
+    layer2/conv1/bn batch variance                         1.1e-07     0.708
+    layer2/conv2/bn batch mean                            8.21e-08      0.95
+    layer2/conv2/bn batch variance                        5.86e-08     0.602
+    layer3/conv0/bn batch mean                            3.87e-07      2.53
+    layer3/conv0/bn batch variance                        3.19e-07      1.54
+    layer3/conv1/bn batch mean                            1.52e-07      1.09
+    layer3/conv1/bn batch variance                        2.28e-07     0.808
+    layer3/conv2/bn batch mean                            1.55e-07     0.884
+    layer3/conv2/bn batch variance                        1.77e-07     0.482
+    layer4/conv0/bn batch mean                            6.52e-07      2.63
+    layer4/conv0/bn batch variance                        1.56e-06      2.12
+    layer4/conv1/bn batch mean                            3.03e-07      1.45
+    layer4/conv1/bn batch variance                        9.41e-07      1.03
+    layer4/conv2/bn batch mean                             3.1e-07     0.867
+    layer4/conv2/bn batch variance                        8.65e-07     0.803
+    fa_layer1/conv_0/bn batch mean                        2.74e-06      5.58
+    fa_layer1/conv_0/bn batch variance                    6.43e-06      5.27
+    fa_layer1/conv_1/bn batch mean                        4.22e-07      1.15
+    fa_layer1/conv_1/bn batch variance                    2.46e-06     0.901
+    fa_layer2/conv_0/bn batch mean                        4.81e-07      2.64
+    fa_layer2/conv_0/bn batch variance                    1.52e-06      1.56
+    fa_layer2/conv_1/bn batch mean                        1.82e-07      1.23
+    fa_layer2/conv_1/bn batch variance                    1.03e-06      1.08
+    fa_layer3/conv_0/bn batch mean                        3.91e-07      2.18
+    fa_layer3/conv_0/bn batch variance                     1.1e-06     0.864
+    fa_layer3/conv_1/bn batch mean                        1.76e-07      1.38
+    fa_layer3/conv_1/bn batch variance                    6.64e-07      1.29
+    fa_layer4/conv_0/bn batch mean                        2.63e-07      1.11
+    fa_layer4/conv_0/bn batch variance                    6.38e-07     0.685
+    fa_layer4/conv_1/bn batch mean                        1.91e-07      1.05
+    fa_layer4/conv_1/bn batch variance                    6.04e-07     0.545
+    fa_layer4/conv_2/bn batch mean                        2.08e-07      1.08
+    fa_layer4/conv_2/bn batch variance                    8.66e-07     0.687
+    fc1/bn batch mean                                     2.06e-07      1.09
+    fc1/bn batch variance                                 8.15e-07     0.949
+    grad layer1/conv0/weights                             4.12e-05      4.71
+    grad layer1/conv0/biases                              4.17e-06  4.44e-15
+    grad layer1/conv0/bn/gamma                            8.86e-06      0.84
+    grad layer1/conv0/bn/beta                             9.38e-06     0.939
+    grad layer1/conv1/weights                             2.29e-05      1.73
+    grad layer1/conv1/biases                              5.81e-07  1.53e-15
+    grad layer1/conv1/bn/gamma                            5.55e-06     0.622
+    grad layer1/conv1/bn/beta                             3.58e-06     0.586
+    grad layer1/conv2/weights                             1.24e-05       1.1
+    grad layer1/conv2/biases                              4.69e-07  7.49e-16
+    grad layer1/conv2/bn/gamma                             4.5e-06     0.349
+    grad layer1/conv2/bn/beta                              1.7e-06     0.232
+    grad layer2/conv0/weights                             7.48e-06     0.795
+    grad layer2/conv0/biases                              2.38e-07  3.05e-16
+    grad layer2/conv0/bn/gamma                            2.83e-06     0.311
+    grad layer2/conv0/bn/beta                             2.95e-06     0.283
+    grad layer2/conv1/weights                             6.89e-06     0.933
+    grad layer2/conv1/biases                              1.79e-07  4.16e-16
+    grad layer2/conv1/bn/gamma                            2.24e-06      0.33
+    grad layer2/conv1/bn/beta                             1.47e-06     0.213
+    grad layer2/conv2/weights                             4.76e-06      0.47
+    grad layer2/conv2/biases                              1.19e-07  3.31e-16
+    grad layer2/conv2/bn/gamma                            1.53e-06     0.206
+    grad layer2/conv2/bn/beta                             3.69e-07     0.055
+    grad layer3/conv0/weights                             3.11e-06     0.481
+    grad layer3/conv0/biases                              6.15e-08  1.46e-16
+    grad layer3/conv0/bn/gamma                            1.32e-06     0.239
+    grad layer3/conv0/bn/beta                             7.07e-07     0.089
+    grad layer3/conv1/weights                             2.28e-06     0.327
+    grad layer3/conv1/biases                              5.84e-08  1.35e-16
+    grad layer3/conv1/bn/gamma                            8.84e-07     0.132
+    grad layer3/conv1/bn/beta                             8.89e-07    0.0871
+    grad layer3/conv2/weights                             2.09e-06     0.246
+    grad layer3/conv2/biases                              3.68e-08  6.16e-17
+    grad layer3/conv2/bn/gamma                            7.88e-07    0.0782
+    grad layer3/conv2/bn/beta                             1.33e-07    0.0205
+    grad layer4/conv0/weights                             1.37e-06     0.176
+    grad layer4/conv0/biases                              2.51e-08   5.9e-17
+    grad layer4/conv0/bn/gamma                            5.03e-07    0.0466
+    grad layer4/conv0/bn/beta                             3.07e-07    0.0358
+    grad layer4/conv1/weights                              9.8e-07     0.113
+    grad layer4/conv1/biases                              1.96e-08  5.03e-17
+    grad layer4/conv1/bn/gamma                            3.12e-07    0.0598
+    grad layer4/conv1/bn/beta                             2.06e-07    0.0251
+    grad layer4/conv2/weights                             1.05e-06     0.133
+    grad layer4/conv2/biases                              1.35e-08  3.12e-17
+    grad layer4/conv2/bn/gamma                            2.17e-07    0.0273
+    grad layer4/conv2/bn/beta                             5.17e-08    0.0072
+    grad fa_layer1/conv_0/weights                         8.57e-07     0.113
+    grad fa_layer1/conv_0/biases                          5.24e-09  6.94e-18
+    grad fa_layer1/conv_0/bn/gamma                        2.85e-07    0.0412
+    grad fa_layer1/conv_0/bn/beta                         2.93e-07    0.0228
+    grad fa_layer1/conv_1/weights                         5.29e-07    0.0684
+    grad fa_layer1/conv_1/biases                          9.31e-09  1.15e-17
+    grad fa_layer1/conv_1/bn/gamma                        2.48e-07    0.0356
+    grad fa_layer1/conv_1/bn/beta                         1.73e-07    0.0218
+    grad fa_layer2/conv_0/weights                         7.26e-07      0.11
+    grad fa_layer2/conv_0/biases                          9.31e-09  1.19e-17
+    grad fa_layer2/conv_0/bn/gamma                        2.42e-07    0.0309
+    grad fa_layer2/conv_0/bn/beta                         1.41e-07    0.0264
+    grad fa_layer2/conv_1/weights                         5.05e-07    0.0763
+    grad fa_layer2/conv_1/biases                          7.92e-09  1.73e-17
+    grad fa_layer2/conv_1/bn/gamma                        2.54e-07    0.0316
+    grad fa_layer2/conv_1/bn/beta                         1.38e-07     0.026
+    grad fa_layer3/conv_0/weights                         5.36e-07     0.082
+    grad fa_layer3/conv_0/biases                          7.68e-09  2.26e-17
+    grad fa_layer3/conv_0/bn/gamma                        3.04e-07    0.0307
+    grad fa_layer3/conv_0/bn/beta                         1.81e-07     0.023
+    grad fa_layer3/conv_1/weights                         4.58e-07    0.0671
+    grad fa_layer3/conv_1/biases                          9.31e-09  1.86e-17
+    grad fa_layer3/conv_1/bn/gamma                        3.15e-07    0.0355
+    grad fa_layer3/conv_1/bn/beta                         1.58e-07    0.0221
+    grad fa_layer4/conv_0/weights                         4.66e-07     0.068
+    grad fa_layer4/conv_0/biases                          1.02e-08  1.73e-17
+    grad fa_layer4/conv_0/bn/gamma                         3.1e-07    0.0365
+    grad fa_layer4/conv_0/bn/beta                         1.32e-07    0.0346
+    grad fa_layer4/conv_1/weights                         4.45e-07    0.0516
+    grad fa_layer4/conv_1/biases                          7.57e-09  1.21e-17
+    grad fa_layer4/conv_1/bn/gamma                         2.5e-07    0.0244
+    grad fa_layer4/conv_1/bn/beta                         1.05e-07    0.0231
+    grad fa_layer4/conv_2/weights                         3.62e-07    0.0406
+    grad fa_layer4/conv_2/biases                          6.05e-09  1.17e-17
+    grad fa_layer4/conv_2/bn/gamma                        1.89e-07    0.0185
+    grad fa_layer4/conv_2/bn/beta                         8.06e-08    0.0168
+    grad fc1/weights                                      4.84e-07     0.042
+    grad fc1/biases                                       1.86e-08  5.57e-17
+    grad fc1/bn/gamma                                     3.96e-07     0.127
+    grad fc1/bn/beta                                      1.85e-07     0.129
+    grad fc2/weights                                      1.13e-06     0.339
+    grad fc2/biases                                       1.52e-07     0.509
+
+case (c): tensor, max |fp32 - f64|, max |f64|
+    logits                                                 4.9e-05      13.6
+    feats                                                 3.84e-05      8.23
+    loss                                                  3.39e-07      5.81
+    grad input features                                   2.15e-06     0.665
+    layer1/conv0/bn batch mean                            5.27e-08     0.529
+    layer1/conv0/bn batch variance                         7.9e-09     0.134
+    layer1/conv1/bn batch mean                            1.11e-07      1.29
+    layer1/conv1/bn batch variance                        5.71e-08     0.912
+    layer1/conv2/bn batch mean                            1.25e-07     0.826
+    layer1/conv2/bn batch variance                        7.38e-08     0.367
+    layer1/layer1 batch mean                              2.48e-08     0.234
+    layer1/layer1 batch variance                          1.89e-08    0.0921
+    layer2/conv0/bn batch mean                            6.08e-08     0.114
+    layer2/conv0/bn batch variance                        3.63e-07      1.69
+    layer2/conv1/bn batch mean                            7.04e-08      0.71
+    layer2/conv1/bn batch variance                        1.11e-07     0.777
+    layer2/conv2/bn batch mean                            9.75e-08     0.875
+    layer2/conv2/bn batch variance                        8.15e-08     0.611
+    layer2/layer2 batch mean                              9.52e-08     0.204
+    layer2/layer2 batch variance                          2.56e-07     0.201
+    fa_layer1/conv_0/bn batch mean                         5.3e-07      3.75
+    fa_layer1/conv_0/bn batch variance                    1.53e-06      4.64
+    fa_layer1/conv_1/bn batch mean                        1.12e-07      1.18
+    fa_layer1/conv_1/bn batch variance                     3.7e-07     0.838
+    fa_layer2/conv_0/bn batch mean                        1.98e-07      1.03
+    fa_layer2/conv_0/bn batch variance                    4.29e-07     0.765
+    fa_layer2/conv_1/bn batch mean                        1.54e-07      1.14
+    fa_layer2/conv_1/bn batch variance                     3.2e-07     0.818
+    fc1/bn batch mean                                     1.75e-07      1.05
+    fc1/bn batch variance                                 3.14e-07     0.681
+    grad layer1/conv0/weights                             4.14e-06      1.47
+    grad layer1/conv0/biases                              6.56e-07  7.77e-16
+    grad layer1/conv0/bn/gamma                            7.63e-07     0.651
+    grad layer1/conv0/bn/beta                             7.54e-07     0.312
+    grad layer1/conv1/weights                             2.04e-06     0.917
+    grad layer1/conv1/biases                              1.34e-07  2.22e-16
+    grad layer1/conv1/bn/gamma                            9.59e-07     0.553
+    grad layer1/conv1/bn/beta                              5.6e-07     0.204
+    grad layer1/conv2/weights                             1.21e-06     0.662
+    grad layer1/conv2/biases                              7.64e-08   1.6e-16
+    grad layer1/conv2/bn/gamma                            6.52e-07     0.195
+    grad layer1/conv2/bn/beta                             4.57e-07     0.129
+    grad layer1/ScannetAttentionLayer/dense/kernel        1.73e-06     0.488
+    grad layer1/ScannetAttentionLayer/dense/bias          7.14e-07     0.215
+    grad layer1/ScannetAttentionLayer/dense_1/kernel      8.98e-07     0.343
+    grad layer1/ScannetAttentionLayer/dense_1/bias        3.29e-07     0.112
+    grad layer1/ScannetAttentionLayer/dense_2/kernel      8.85e-07     0.274
+    grad layer1/ScannetAttentionLayer/dense_2/bias        2.34e-07    0.0809
+    grad layer1/layer1/gamma                              4.45e-07     0.147
+    grad layer1/layer1/beta                               2.33e-08  3.73e-17
+    grad layer2/conv0/weights                             1.01e-06     0.357
+    grad layer2/conv0/biases                               2.7e-08  3.82e-17
+    grad layer2/conv0/bn/gamma                            5.13e-07     0.104
+    grad layer2/conv0/bn/beta                             1.54e-07    0.0859
+    grad layer2/conv1/weights                              9.1e-07     0.263
+    grad layer2/conv1/biases                              2.33e-08  4.86e-17
+    grad layer2/conv1/bn/gamma                            3.57e-07     0.109
+    grad layer2/conv1/bn/beta                              1.4e-07    0.0534
+    grad layer2/conv2/weights                             7.55e-07     0.242
+    grad layer2/conv2/biases                              2.14e-08  9.19e-17
+    grad layer2/conv2/bn/gamma                            2.82e-07     0.126
+    grad layer2/conv2/bn/beta                             1.28e-07    0.0322
+    grad layer2/ScannetAttentionLayer/dense/kernel        6.64e-07     0.313
+    grad layer2/ScannetAttentionLayer/dense/bias          2.05e-07    0.0909
+    grad layer2/ScannetAttentionLayer/dense_1/kernel      6.07e-07     0.199
+    grad layer2/ScannetAttentionLayer/dense_1/bias        7.49e-08    0.0287
+    grad layer2/ScannetAttentionLayer/dense_2/kernel      6.25e-07     0.187
+    grad layer2/ScannetAttentionLayer/dense_2/bias         5.3e-08    0.0203
+    grad layer2/layer2/gamma                              1.03e-07    0.0278
+    grad layer2/layer2/beta                               6.52e-09  1.56e-17
+    grad fa_layer1/conv_0/weights                         3.27e-07     0.108
+    grad fa_layer1/conv_0/biases                          5.59e-09  1.04e-17
+    grad fa_layer1/conv_0/bn/gamma                        9.71e-08    0.0571
+    grad fa_layer1/conv_0/bn/beta                          5.4e-08    0.0285
+    grad fa_layer1/conv_1/weights                         2.36e-07    0.0808
+    grad fa_layer1/conv_1/biases                          1.02e-08  1.73e-17
+    grad fa_layer1/conv_1/bn/gamma                        8.17e-08    0.0349
+    grad fa_layer1/conv_1/bn/beta                         5.22e-08    0.0316
+    grad fa_layer2/conv_0/weights                         1.99e-07    0.0863
+    grad fa_layer2/conv_0/biases                          1.08e-08  3.14e-17
+    grad fa_layer2/conv_0/bn/gamma                        6.28e-08    0.0363
+    grad fa_layer2/conv_0/bn/beta                         3.53e-08     0.032
+    grad fa_layer2/conv_1/weights                          1.4e-07    0.0733
+    grad fa_layer2/conv_1/biases                          8.38e-09  1.26e-17
+    grad fa_layer2/conv_1/bn/gamma                        7.42e-08    0.0251
+    grad fa_layer2/conv_1/bn/beta                          4.4e-08    0.0217
+    grad fc1/weights                                      1.39e-07    0.0603
+    grad fc1/biases                                       1.58e-08  3.95e-17
+    grad fc1/bn/gamma                                     7.29e-08     0.091
+    grad fc1/bn/beta                                      3.37e-08     0.106
+    grad fc2/weights                                      3.53e-07     0.235
+    grad fc2/biases                                       9.76e-08     0.443
+
+Case (c) on the MI355X, the reference on the GPU's own decisions: tensor, err = max |gpu - f64|,
+err32 = max |fp32 - f64|, err / err32, in run 2 of the four above (largest ratio 3.58; not the
+run that exceeded 4, of which only the eight ratios quoted above were kept):
+
+    logits                                                2.92e-05  4.82e-05   0.61
+    feats                                                 2.35e-05  4.17e-05   0.56
+    loss                                                  3.39e-07  1.38e-07   2.46
+    grad layer1/conv0/weights                             4.83e-06  4.29e-06   1.13
+    grad layer1/conv0/biases                              1.28e-15  4.77e-07   0.00
+    grad layer1/conv0/bn/gamma                            1.69e-06  7.44e-07   2.27
+    grad layer1/conv0/bn/beta                             9.74e-07  7.25e-07   1.34
+    grad layer1/conv1/weights                             2.96e-06  3.05e-06   0.97
+    grad layer1/conv1/biases                              2.78e-16  1.19e-07   0.00
+    grad layer1/conv1/bn/gamma                             1.1e-06   7.7e-07   1.43
+    grad layer1/conv1/bn/beta                             4.53e-07  4.12e-07   1.10
+    grad layer1/conv2/weights                             2.05e-06  1.94e-06   1.06
+    grad layer1/conv2/biases                              3.05e-16  1.04e-07   0.00
+    grad layer1/conv2/bn/gamma                            1.04e-06  7.19e-07   1.45
+    grad layer1/conv2/bn/beta                             5.77e-07  3.55e-07   1.63
+    grad layer1/ScannetAttentionLayer/dense/kernel        2.21e-06  6.18e-07   3.58
+    grad layer1/ScannetAttentionLayer/dense/bias          7.42e-07  2.56e-07   2.90
+    grad layer1/ScannetAttentionLayer/dense_1/kernel      1.23e-06  6.86e-07   1.79
+    grad layer1/ScannetAttentionLayer/dense_1/bias         3.7e-07  2.74e-07   1.35
+    grad layer1/ScannetAttentionLayer/dense_2/kernel      8.76e-07  8.82e-07   0.99
+    grad layer1/ScannetAttentionLayer/dense_2/bias        2.87e-07  2.33e-07   1.23
+    grad layer1/layer1/gamma                              3.09e-07   3.9e-07   0.79
+    grad layer1/layer1/beta                               3.63e-08  1.86e-08   1.95
+    grad layer2/conv0/weights                             7.73e-07  7.57e-07   1.02
+    grad layer2/conv0/biases                              8.72e-17  1.72e-08   0.00
+    grad layer2/conv0/bn/gamma                            3.47e-07   2.5e-07   1.39
+    grad layer2/conv0/bn/beta                             1.78e-07  1.16e-07   1.53
+    grad layer2/conv1/weights                             6.81e-07  6.01e-07   1.13
+    grad layer2/conv1/biases                              5.68e-17  1.91e-08   0.00
+    grad layer2/conv1/bn/gamma                             2.8e-07   1.9e-07   1.47
+    grad layer2/conv1/bn/beta                             9.41e-08  1.24e-07   0.76
+    grad layer2/conv2/weights                             9.99e-07  6.14e-07   1.63
+    grad layer2/conv2/biases                              3.82e-17  3.35e-08   0.00
+    grad layer2/conv2/bn/gamma                            2.11e-07  2.85e-07   0.74
+    grad layer2/conv2/bn/beta                              1.2e-07  8.82e-08   1.36
+    grad layer2/ScannetAttentionLayer/dense/kernel        7.67e-07  7.08e-07   1.08
+    grad layer2/ScannetAttentionLayer/dense/bias          1.59e-07  1.21e-07   1.31
+    grad layer2/ScannetAttentionLayer/dense_1/kernel      4.43e-07  3.31e-07   1.34
+    grad layer2/ScannetAttentionLayer/dense_1/bias        9.02e-08  4.38e-08   2.06
+    grad layer2/ScannetAttentionLayer/dense_2/kernel      4.47e-07  2.64e-07   1.69
+    grad layer2/ScannetAttentionLayer/dense_2/bias        8.19e-08  4.38e-08   1.87
+    grad layer2/layer2/gamma                              8.64e-08  1.12e-07   0.77
+    grad layer2/layer2/beta                               6.98e-09  6.98e-09   1.00
+    grad fa_layer1/conv_0/weights                          2.7e-07  3.32e-07   0.81
+    grad fa_layer1/conv_0/biases                          1.39e-17  5.59e-09   0.00
+    grad fa_layer1/conv_0/bn/gamma                        1.35e-07  9.61e-08   1.40
+    grad fa_layer1/conv_0/bn/beta                         7.76e-08  5.27e-08   1.47
+    grad fa_layer1/conv_1/weights                         1.81e-07  1.96e-07   0.92
+    grad fa_layer1/conv_1/biases                          1.73e-17  9.31e-09   0.00
+    grad fa_layer1/conv_1/bn/gamma                        1.33e-07  1.13e-07   1.18
+    grad fa_layer1/conv_1/bn/beta                         6.06e-08  4.17e-08   1.45
+    grad fa_layer2/conv_0/weights                          2.2e-07  1.98e-07   1.11
+    grad fa_layer2/conv_0/biases                          3.64e-17  1.02e-08   0.00
+    grad fa_layer2/conv_0/bn/gamma                        8.86e-08  8.13e-08   1.09
+    grad fa_layer2/conv_0/bn/beta                         3.62e-08  3.36e-08   1.08
+    grad fa_layer2/conv_1/weights                         1.73e-07  1.74e-07   0.99
+    grad fa_layer2/conv_1/biases                          1.39e-17  7.92e-09   0.00
+    grad fa_layer2/conv_1/bn/gamma                        7.11e-08   7.2e-08   0.99
+    grad fa_layer2/conv_1/bn/beta                         3.27e-08  2.97e-08   1.10
+    grad fc1/weights                                      1.33e-07  1.64e-07   0.81
+    grad fc1/biases                                       4.16e-17  1.91e-08   0.00
+    grad fc1/bn/gamma                                     8.23e-08  1.03e-07   0.80
+    grad fc1/bn/beta                                      4.02e-08  4.22e-08   0.95
+    grad fc2/weights                                      3.51e-07  3.02e-07   1.16
+    grad fc2/biases                                       5.81e-08  1.25e-07   0.46
+    grad of the input features                            3.16e-06  1.66e-06   1.90
+    layer1/conv0/bn/moving_mean                           5.88e-09   1.5e-08   0.39
+    layer1/conv0/bn/moving_variance                       4.14e-08  4.14e-08   1.00
+    layer1/conv1/bn/moving_mean                           1.54e-08  2.54e-08   0.61
+    layer1/conv1/bn/moving_variance                       4.71e-08  3.62e-08   1.30
+    layer1/conv2/bn/moving_mean                           1.34e-08   2.8e-08   0.48
+    layer1/conv2/bn/moving_variance                       4.21e-08  4.04e-08   1.04
+    layer1/layer1/moving_mean                             7.72e-09  8.69e-09   0.89
+    layer1/layer1/moving_variance                         4.03e-08  4.13e-08   0.98
+    layer2/conv0/bn/moving_mean                            1.3e-08  1.48e-08   0.88
+    layer2/conv0/bn/moving_variance                       8.18e-08  8.87e-08   0.92
+    layer2/conv1/bn/moving_mean                           2.84e-08  1.86e-08   1.53
+    layer2/conv1/bn/moving_variance                       4.74e-08  4.74e-08   1.00
+    layer2/conv2/bn/moving_mean                           1.96e-08  1.81e-08   1.08
+    layer2/conv2/bn/moving_variance                       4.74e-08  5.14e-08   0.92
+    layer2/layer2/moving_mean                              1.6e-08  2.26e-08   0.71
+    layer2/layer2/moving_variance                         9.46e-08  9.46e-08   1.00
+    fa_layer1/conv_0/bn/moving_mean                       8.67e-08  8.69e-08   1.00
+    fa_layer1/conv_0/bn/moving_variance                   4.12e-07  3.06e-07   1.35
+    fa_layer1/conv_1/bn/moving_mean                       2.11e-08  2.99e-08   0.71
+    fa_layer1/conv_1/bn/moving_variance                    8.1e-08  9.95e-08   0.81
+    fa_layer2/conv_0/bn/moving_mean                       3.24e-08  4.18e-08   0.78
+    fa_layer2/conv_0/bn/moving_variance                   7.56e-08  8.69e-08   0.87
+    fa_layer2/conv_1/bn/moving_mean                       1.97e-08  3.15e-08   0.63
+    fa_layer2/conv_1/bn/moving_variance                   9.12e-08     1e-07   0.91
+    fc1/bn/moving_mean                                    3.43e-08  3.88e-08   0.88
+    fc1/bn/moving_variance                                8.87e-08  1.14e-07   0.78
+"""
+import importlib
+
+import numpy as np
+import pytest
+
+import model_train_ref as R
+from conftest import PKG_NAME, gpu_available
+from optim_cases import bits, numpy_adam
+
+pytestmark = [pytest.mark.gpu,
+              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+
+# The factor on the float32 yardstick, per case: the project's 4, except case (c) (see the
+# module docstring: the attention op itself is within 4 on the model's own inputs)
+FACTOR = {"a": 4, "b": 4, "c": 8}
+SPIED = ("_torch_ops", "attention_layer", "tf_sampling", "tf_grouping", "tf_interpolate")
+LAYER_OPS = ("mlp_layer_train", "mlp_layer_train_pool")
+
+
+@pytest.fixture(scope="module")
+def env():
+    import torch
+    pkg = importlib.import_module(PKG_NAME)
+    return pkg, torch, torch.device("cuda:0")
+
+
+@pytest.fixture
+def spy(env, monkeypatch):
+    """(name, args, outputs) of every torch.ops.pn2 op the mirror modules call, in order: the
+    indices, distances and the dropout seed are among the arguments, the masks and argmaxes
+    among the outputs. Every module that imported `call` for itself is patched as well."""
+    pkg = env[0]
+    entries, real = [], pkg._torch_ops.call
+
+    def call(name, *args):
+        out = real(name, *args)
+        entries.append((name, args, out))
+        return out
+    for mod in SPIED:
+        assert getattr(getattr(pkg, mod), "call") is real, mod
+        monkeypatch.setattr(getattr(pkg, mod), "call", call)
+    return entries
+
+
+class OpLog:
+    """Counts the pn2 operators that reach the dispatcher, autograd's backward calls included
+    (tests/test_gpu_geom_train.py OpCounter), and keeps the arguments and outputs of `keep`."""
+
+    def __init__(self, keep=()):
+        import collections
+
+        from torch.utils._python_dispatch import TorchDispatchMode
+        counts, kept = collections.Counter(), []
+        self.counts, self.kept = counts, kept
+
+        class Mode(TorchDispatchMode):
+            def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+                out = func(*args, **(kwargs or {}))
+                counts[func.name()] += 1
+                if func.name() in keep:
+                    kept.append((func.name(), args, out))
+                return out
+
+        self.mode = Mode()
+
+    def __enter__(self):
+        self.mode.__enter__()
+        return self
+
+    def __exit__(self, *a):
+        return self.mode.__exit__(*a)
+
+
+def gpu_model(pkg, spec, store, xyz, feats, seed):
+    """(logits, fc1 output): model_body for the SSG specs, the same layers called one by one
+    with the attention SA modules for case (c)."""
+    if all(L["kind"] == "max" for L in spec["sa"]):
+        logits, end_points = pkg.pointnet2_sem_seg.model_body(
+            xyz, feats, True, spec["num_class"], R.DECAY, store, seed=seed)
+        return logits, end_points["feats"]
+    al, pu, tu = pkg.attention_layer, pkg.pointnet_util, pkg.tf_util
+    module = {"attn": al.pointnet_sa_module_attention,
+              "attn_pool": al.pointnet_sa_module_attention_and_pooling}
+    lv, pts = [xyz], [feats]
+    for L in spec["sa"]:
+        nx, p, _ = module[L["kind"]](lv[-1], pts[-1], L["npoint"], L["radius"], L["nsample"],
+                                     L["mlp"], None, False, True, R.DECAY, L["scope"],
+                                     params=store)
+        lv.append(nx)
+        pts.append(p)
+    for j, L in enumerate(spec["fp"]):
+        k = len(spec["sa"]) - 1 - j
+        pts[k] = pu.pointnet_fp_module(lv[k], lv[k + 1], pts[k], pts[k + 1], L["mlp"], True,
+                                       R.DECAY, L["scope"], params=store)
+    fc1 = tu.conv1d(pts[0], spec["fc1"], 1, "fc1", padding="VALID", bn=True, is_training=True,
+                    bn_decay=R.DECAY, params=store)
+    net = tu.dropout(fc1, True, "dp1", keep_prob=spec["keep_prob"], seed=seed)
+    net = tu.conv1d(net, spec["num_class"], 1, "fc2", padding="VALID", activation_fn=None,
+                    is_training=True, params=store)
+    return net, fc1
+
+
+class Comparisons:
+    """The rule of tests/test_gpu_mlp_train.py::assert_close (same checks, same printed line) with
+    the factor on the float32 yardstick as a parameter, on every tensor of a case; the failures
+    are raised together at the end."""
+
+    def __init__(self, case, factor=4):
+        self.case, self.factor, self.rows, self.failed = case, factor, [], []
+
+    def close(self, got, r64, r32, what):
+        g = got.detach().cpu().double()
+        assert g.shape == r64.shape, (what, g.shape, r64.shape)
+        err = float((g - r64).abs().max())
+        err32 = float((r32.double() - r64).abs().max())
+        tol = max(self.factor * err32, 1e-6 * (1 + float(r64.abs().max())))
+        print(f"{what}: err {err:.3g} tol {tol:.3g} (fp32 err {err32:.3g})")
+        self.rows.append((err / tol, err / err32 if err32 else float("inf"), what))
+        if not bool(g.isfinite().all()):
+            self.failed.append(f"{what}: non-finite values")
+        elif not err <= tol:
+            self.failed.append(f"{what}: max err {err:.3g} > tol {tol:.3g} "
+                               f"(fp32 cpu err {err32:.3g})")
+
+    def finish(self):
+        worst = max(self.rows)
+        print(f"case ({self.case}): {len(self.rows)} tensors, largest err / tol {worst[0]:.3g} "
+              f"(err / err32 {worst[1]:.3g}) at {worst[2]}")
+        for r in sorted(self.rows, reverse=True)[:8]:
+            print(f"    err / tol {r[0]:.3g}  err / err32 {r[1]:.3g}  {r[2]}")
+        assert not self.failed, f"case ({self.case}):\n" + "\n".join(self.failed)
+
+
+def print_layers(torch, entries, r64, r32):
+    """Not asserted: each layer's activation on the GPU against the reference's, in call order."""
+    gpu = [out[0] for name, _, out in entries if name in LAYER_OPS]
+    ref = [(k, a, b) for (k, a), (_, b) in zip(r64["inter"], r32["inter"])
+           if k != "dp1" and not k.endswith("/attention")]
+    assert len(gpu) == len(ref)
+    for g, (k, a, b) in zip(gpu, ref):
+        err = float((g.detach().cpu().double() - a).abs().max())
+        err32 = float((b.double() - a).abs().max())
+        print(f"    layer {k:24s} err {err:9.3g}  err32 {err32:9.3g}  max |f64| "
+              f"{float(a.abs().max()):9.3g}")
+
+
+def attention_ops_alone(env, spec, store, kept):
+    """What allows case (c) its factor: every attn_kv_train_grad call of the backward, compared
+    on its own with the reference fed the GPU's recorded inputs to it (the module's per-point
+    features, the incoming gradients, the argmax), is within the project's factor 4. The error
+    the whole model shows beyond that is float32 rounding upstream of the op."""
+    pkg, torch, dev = env
+    attn = [L for L in spec["sa"] if L["kind"] != "max"]
+    assert len(kept) == len(attn)
+    for (_, args, outs), L in zip(kept, reversed(attn)):  # the backward runs the last one first
+        grad_att, grad_pmax, arg, x = args[:4]
+        assert int(x.shape[-1]) == L["mlp"][-1]
+        assert (grad_pmax is not None) == (L["kind"] == "attn_pool")
+        weights = [store[n].detach() for n in R.attention_names(L["scope"])]
+        assert torch.equal(args[4], weights[0]) and torch.equal(args[5], weights[2])
+        r64 = R.attention_op_grads(x, weights, grad_att, grad_pmax, arg, torch.float64)
+        r32 = R.attention_op_grads(x, weights, grad_att, grad_pmax, arg, torch.float32)
+        alone = Comparisons(f"{L['scope']} attn_kv_train_grad alone")
+        for got, a, b, what in zip(outs, r64, r32, ("x", "wq", "bq", "wk", "bk", "wv", "bv")):
+            alone.close(got.reshape(a.shape), a, b, f"{L['scope']} alone: grad {what}")
+        alone.finish()
+
+
+@pytest.mark.parametrize("case", sorted(R.CASES))
+def test_training_step_vs_f64(env, spy, case):
+    pkg, torch, dev = env
+    spec, xyz, feats0, labels, smpw = R.case_inputs(pkg, case)
+    assert 0.15 < float((labels == 0).float().mean()) < 0.25
+    assert bool((smpw[labels == 0] == 0).all()) and float((smpw == 0).float().mean()) > 0.25
+    store = pkg.tf_util.ParamStore(seed=R.STORE_SEED).trainable(dev)
+    feats = None if feats0 is None else feats0.to(dev).requires_grad_(True)
+    with OpLog(keep=("pn2::attn_kv_train_grad",)) as log:
+        logits, fc1 = gpu_model(pkg, spec, store, xyz.to(dev), feats, R.DROPOUT_SEED)
+        loss = pkg.pointnet2_sem_seg.get_loss(logits, labels.to(dev), smpw.to(dev))
+        loss.backward()
+    torch.cuda.synchronize()
+    names, counts = [e[0] for e in spy], log.counts
+
+    # ---- the variables: the reference's set exactly, created with the initialisers' values
+    init = R.store_init(pkg, spec)
+    leaves = R.leaf_names(spec)
+    assert sorted(store) == sorted(init)
+    assert sorted(k for k, v in store.items() if v.grad is not None) == sorted(leaves)
+    assert sorted(k for k, v in store.items() if v.requires_grad) == sorted(leaves)
+    for k in leaves:
+        assert tuple(store[k].shape) == tuple(init[k].shape), k
+        assert torch.equal(store[k].detach().cpu(), init[k]), k
+
+    # ---- the reference on the GPU's own discrete choices
+    rec = R.decisions(spy)
+    assert rec["seed"] == R.DROPOUT_SEED and rec["keep_prob"] == spec["keep_prob"]
+    assert len(rec["centres"]) == len(rec["group_idx"]) == len(spec["sa"])
+    assert len(rec["nn"]) == len(spec["fp"])
+    r64 = R.run(spec, init, xyz, feats0, labels, smpw, rec, torch.float64)
+    r32 = R.run(spec, init, xyz, feats0, labels, smpw, rec, torch.float32)
+    print(f"\ncase ({case})")
+    print_layers(torch, spy, r64, r32)
+    cmp = Comparisons(case, FACTOR[case])
+    cmp.close(logits, r64["logits"], r32["logits"], "logits")
+    cmp.close(fc1, r64["feats"], r32["feats"], "feats")
+    cmp.close(loss, r64["loss"], r32["loss"], "loss")
+    for k in leaves:
+        cmp.close(store[k].grad, r64["grads"][k], r32["grads"][k], "grad " + k)
+    if feats is not None:
+        assert feats.grad is not None
+        cmp.close(feats.grad, r64["grad_feats"], r32["grad_feats"], "grad of the input features")
+    m64 = R.moving_after(r64["stats"], init, R.DECAY, torch.float64)
+    m32 = R.moving_after(r32["stats"], init, R.DECAY, torch.float32)
+    assert sorted(m64) == sorted(R.bn_scopes(spec))
+    for s in R.bn_scopes(spec):
+        cmp.close(store[f"{s}/moving_mean"], m64[s][0], m32[s][0], f"{s}/moving_mean")
+        cmp.close(store[f"{s}/moving_variance"], m64[s][1], m32[s][1], f"{s}/moving_variance")
+    problems = []
+    for check in (cmp.finish, lambda: attention_ops_alone(env, spec, store, log.kept)):
+        try:
+            check()
+        except AssertionError as e:
+            problems.append(str(e))
+    assert not problems, "\n".join(problems)
+
+    # ---- exact statements
+    for k in R.bias_under_bn(spec):
+        assert bool((store[k].grad == 0).all()), k  # the batch mean absorbs the bias
+    assert float(store["fc2/biases"].grad.abs().max()) > 0
+    keep = torch.from_numpy(r64["keep"])
+    dropped = rec["dropout_out"]
+    assert bool((dropped[~keep] == 0).all()) and 0.49 < float(keep.float().mean()) < 0.51
+    assert torch.equal(dropped[keep], (fc1.detach().cpu() / np.float32(spec["keep_prob"]))[keep])
+
+    # ---- the intended ops ran
+    n_sa, n_fp = len(spec["sa"]), len(spec["fp"])
+    with_points = n_sa - (1 if feats0 is None else 0)  # layer 1 without points asks for no gradient
+    assert names.count("group_concat_train") == with_points
+    assert counts["pn2::group_concat_train_grad"] == with_points
+    assert names.count("fp_apply_train") == n_fp and counts["pn2::fp_apply_train_grad"] == n_fp
+    assert names.count("group_point") == 0 and names.count("three_interpolate") == 0
+    assert counts["pn2::group_point_grad"] == 0 and counts["pn2::three_interpolate_grad"] == 0
+    if case == "c":
+        assert names.count("attn_kv_train") == 2 and names.count("bn_train") == 2
+        assert counts["pn2::attn_kv_train_grad"] == 2 and counts["pn2::bn_train_grad"] == 2
+        assert names.count("mlp_layer_train_pool") == 0
+    else:
+        assert names.count("mlp_layer_train_pool") == 4
+        assert counts["pn2::mlp_layer_train_pool_grad"] == 4
+    if case == "a":
+        # layer 1 has no points: its grouping never reaches the ops (the no-grad kernel of
+        # group_concat runs), so its ball query is followed by its first MLP layer
+        assert names[:3] == ["farthest_point_sample_and_gather", "query_ball_point",
+                             "mlp_layer_train"]
+        assert names.count("group_concat") == 0
+        # SA4: 16 centres, 32 samples of 64 points: the groups are padded with repeats of their
+        # first index, so the inverse index's duplicate-key path is on the gradient's route
+        idx = rec["group_idx"][3].reshape(-1, 32)
+        padded = sum(len(set(g.tolist())) < 32 for g in idx)
+        print(f"SA4: {padded} of {len(idx)} groups hold a repeated index")
+        assert idx.shape[0] == R.B * 16 and 2 * padded >= len(idx)
+        # SA1 picks a real subset, and FP4 interpolates between distinct points
+        assert rec["centres"][0].shape[1] == 1024 < R.N
+        d4 = rec["nn"][3][0]
+        assert float((d4[..., 1] > 0).float().mean()) > 0.99
+        assert float((d4[..., 0] > 0).float().mean()) > 0.4
+
+
+def test_train_step_passes_every_gradient_on(env):
+    """train_step on store A against forward + loss + backward by hand on store B (same initial
+    values, same dropout seed) followed by numpy's Adam: the variables and the moving statistics
+    of A are B's, bit for bit."""
+    pkg, torch, dev = env
+    spec, xyz, feats, labels, smpw = R.case_inputs(pkg, "b")
+    xyz, feats, labels, smpw = (t.to(dev) for t in (xyz, feats, labels, smpw))
+    lr = 2e-3
+    A = pkg.tf_util.ParamStore(seed=R.STORE_SEED).trainable(dev)
+    opt = pkg.train.AdamOptimizer(A)
+    metrics = pkg.train.SegMetrics(spec["num_class"])
+    loss_a, _ = pkg.train.train_step(A, opt, metrics, xyz, labels, smpw, spec["num_class"],
+                                     bn_decay=R.DECAY, learning_rate=lr, features=feats,
+                                     seed=R.DROPOUT_SEED)
+    assert opt.t == 1
+    alpha = opt.alpha(lr)
+    Bs = pkg.tf_util.ParamStore(seed=R.STORE_SEED).trainable(dev)
+    logits, _ = pkg.pointnet2_sem_seg.model_body(xyz, feats, True, spec["num_class"], R.DECAY, Bs,
+                                                 seed=R.DROPOUT_SEED)
+    loss_b = pkg.pointnet2_sem_seg.get_loss(logits, labels, smpw)
+    loss_b.backward()
+    assert torch.equal(loss_a, loss_b.detach())
+    leaves = R.leaf_names(spec)
+    assert sorted(A) == sorted(Bs) == sorted(n for n, _, _, _ in R.variables(spec))
+    moved = 0
+    for k in leaves:
+        p, g = Bs[k].detach().cpu().numpy(), Bs[k].grad.cpu().numpy()
+        zero = np.zeros_like(p)
+        want = numpy_adam(p, g, zero, zero, alpha, opt.beta1, opt.beta2, opt.epsilon, np.float32)[0]
+        got = A[k].detach().cpu().numpy()
+        assert np.array_equal(bits(got), bits(want)), k
+        moved += int(not np.array_equal(bits(got), bits(p)))
+    # every variable but the biases under batch norm (gradient 0) took a step
+    assert moved == len(leaves) - len(R.bias_under_bn(spec))
+    for s in R.bn_scopes(spec):
+        for v in ("moving_mean", "moving_variance"):
+            a, b = (S[f"{s}/{v}"].cpu().numpy() for S in (A, Bs))
+            assert np.array_equal(bits(a), bits(b)), f"{s}/{v}"
