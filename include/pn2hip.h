@@ -79,7 +79,21 @@
  *  - return 0 on success, PN2_EINVAL (-22) for a shape/attribute error (where the reference
  *    raises InvalidArgument through OP_REQUIRES), PN2_EFAULT (-14) when an earlier sampler
  *    launch reported a device fault (pn2_fault_status), or a positive hipError_t from the
- *    launch.
+ *    launch;
+ *  - alignment: every pointer needs its element's natural alignment (4 bytes for float and
+ *    int32_t, 8 for the 64-bit keys and counters) and nothing more, unless the entry point
+ *    says otherwise. Rows, clouds and batches are dense (no strides) unless the entry point takes a
+ *    leading dimension (ld / col0). The kernels that use
+ *    16-byte loads and stores choose them per launch from the pointers they are given and
+ *    take a per-element path for any other pointer, with the same arithmetic in the same
+ *    order: the bits of the result do not depend on the alignment. The exceptions, which
+ *    return PN2_EINVAL for a pointer that is not 16-byte aligned before any launch:
+ *    pn2_copy_f4, pn2_attn_reduce, pn2_attn_reduce_layers, pn2_attn_reduce_grad,
+ *    pn2_attn_kv_reduce, pn2_attn_kv_reduce_grad (all buffers), pn2_group_mlp_attention (out, bn_scale and
+ *    bn_shift; its other buffers follow the general rule), the `packed` weights of
+ *    pn2_mlp_layer / pn2_mlp_pack, every grid (pn2_grid_size bytes) and the inverse index
+ *    `inv`. The torch and Python front ends copy a misaligned tensor argument of those
+ *    functions to a fresh allocation first.
  */
 #ifndef PN2HIP_H
 #define PN2HIP_H
@@ -448,13 +462,15 @@ int pn2_three_interpolate_grad_ordered(const float* grad_out, int ld, int col0, 
  * heads H = C/4. Q (B,M,C), K,V (B,M,ns,C) → out (B,M,C). Head h reads the CONTIGUOUS
  * block [4*ns*h, 4*ns*(h+1)) of each group's flattened ns*C K/V values as ns rows of 4
  * (the reference's tf.reshape reinterpretation), s = (K_h·q_h)/2, a = softmax(s),
- * out[4h:4h+4] = aᵀ V_h. C must be a multiple of 4. */
+ * out[4h:4h+4] = aᵀ V_h. C must be a multiple of 4; Q, K, V and out 16-byte aligned
+ * (PN2_EINVAL otherwise, before any launch). */
 int pn2_attn_reduce(const float* Q, const float* K, const float* V, int B, int M, int ns,
                     int C, float* out, pn2_stream_t stream);
 /* Several attention reductions of one nsample in ONE launch (the SSG stack's four SA layers,
  * attention_layer.py:35-42 per layer): per layer exactly pn2_attn_reduce(Q, K, V, B, M, ns,
  * C, out); one nsample for every layer, else PN2_EINVAL (an nsample outside {8, 16, 32, 64, 128},
- * or a layer too large for the one-launch task arithmetic, runs as pn2_attn_reduce does). */
+ * or a layer too large for the one-launch task arithmetic, runs as pn2_attn_reduce does).
+ * Every layer's Q, K, V and out 16-byte aligned, as for pn2_attn_reduce. */
 #define PN2_ATTN_MAX_LAYERS 4
 typedef struct pn2_attn_layer {
   const float* Q;
@@ -499,7 +515,9 @@ int pn2_mlp_pack(const float* weight, const float* bias, const float* bn_scale,
  *   (B,M,2*cout) = [avg, max]; PN2_POOL_NONE → out (B,M,nsample,cout) (the per-point
  *   features the attention SA modules feed to AttentionLayer, attention_layer.py:229-263).
  * Products and sums in fp32 on the matrix cores; the grouped input and the per-layer
- * activations stay on chip. Host array `layers`. */
+ * activations stay on chip. Host array `layers`. `points` rows are gathered with 16-byte
+ * loads when C % 4 == 0 and `points` is 16-byte aligned, float by float otherwise (slower,
+ * the same bits); xyz, new_xyz, idx and out need 4-byte alignment only. */
 int pn2_group_mlp(const float* xyz, const float* points, const float* new_xyz,
                   const int32_t* idx, int B, int N, int C, int M, int nsample, int flags,
                   int nlayers, const pn2_mlp_layer* layers, int pool, float* out,
@@ -513,7 +531,10 @@ int pn2_group_mlp(const float* xyz, const float* points, const float* new_xyz,
  * tf.reshape of :35-36), softmax((K_h q_h)/2) V_h; then the inference batch norm
  * out = att * bn_scale + bn_shift (:261; NULL = none) and, with add_max, + the max over nsample
  * of the MLP output (pointnet_sa_module_attention_and_pooling, :296-303). out (B,M,C).
- * nsample <= 128; C = layers[nlayers-1].cout, a multiple of 32. */
+ * nsample <= 128; C = layers[nlayers-1].cout, a multiple of 32. out, bn_scale and
+ * bn_shift are accessed in 16-byte units and must be 16-byte aligned (PN2_EINVAL otherwise,
+ * before any launch); xyz, points, new_xyz and idx as for pn2_group_mlp (a misaligned `points`
+ * takes the per-float gather). */
 int pn2_group_mlp_attention(const float* xyz, const float* points, const float* new_xyz,
                             const int32_t* idx, int B, int N, int C, int M, int nsample,
                             int flags, int nlayers, const pn2_mlp_layer* layers,
@@ -523,12 +544,18 @@ int pn2_group_mlp_attention(const float* xyz, const float* points, const float* 
 /* pointnet_fp_module (pointnet_util.py:218-238): IDW weights of dist (B,n,3) + interpolation
  * of points2 (B,m,C2) at nn_idx (B,n,3) + concat [interp, points1 (B,n,C1)] (bit-identical to
  * pn2_fp_apply's output) fed to the packed layers → out (B,n,cout). points1 may be NULL
- * (C1 = 0). dist / nn_idx come from pn2_three_nn or pn2_three_nn_grid. */
+ * (C1 = 0). dist / nn_idx come from pn2_three_nn or pn2_three_nn_grid. points2 rows are read
+ * with 16-byte loads when C2 % 4 == 0 and points2 is 16-byte aligned, points1 rows when
+ * C1 % 4 == 0, C2 % 4 == 0 and points1 is 16-byte aligned; any other pointer takes the
+ * per-float gather (slower, the same bits). out is stored in 16-byte units when cout % 4 == 0
+ * and it is 16-byte aligned, per float otherwise. */
 int pn2_fp_mlp(const float* dist, const int32_t* nn_idx, const float* points1, int C1,
                const float* points2, int C2, int B, int n, int m, int nlayers,
                const pn2_mlp_layer* layers, float* out, pn2_stream_t stream);
 /* Per-point MLP over rows: x (rows,cin) → out (rows,cout) (tf_util.conv1d with kernel 1,
- * e.g. the fc1/fc2 head of pointnet2_sem_seg.py:57-60). */
+ * e.g. the fc1/fc2 head of pointnet2_sem_seg.py:57-60). x is read with 16-byte loads when
+ * cin % 4 == 0 and x is 16-byte aligned, out stored in 16-byte units when cout % 4 == 0 and
+ * out is 16-byte aligned; any other pointer takes the per-float path (slower, the same bits). */
 int pn2_shared_mlp(const float* x, long long rows, int cin, int nlayers,
                    const pn2_mlp_layer* layers, float* out, pn2_stream_t stream);
 /* R (row tiles per workgroup) and tpw (tiles per workgroup) that pn2_shared_mlp would launch

@@ -278,3 +278,12 @@ def device_tensor(t, name, dtype):
     if t.dtype != dtype:
         raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
     return t.contiguous()
+
+
+def aligned_device_tensor(t, name, dtype):
+    """device_tensor for an argument whose C function demands 16-byte alignment (the attention
+    reductions, include/pn2hip.h): a contiguous view at an odd offset into a larger buffer is
+    copied to a fresh allocation. Arguments whose kernels have a scalar path use device_tensor
+    and stay where they are."""
+    t = device_tensor(t, name, dtype)
+    return t.clone() if t.data_ptr() % 16 else t

@@ -11,8 +11,8 @@ import ctypes
 import torch
 
 from . import pointnet_util, tf_grouping, tf_sampling, tf_util
-from ._lib import (PN2_ATTN_MAX_LAYERS, AttnLayer, InvalidArgumentError, check, device_tensor,
-                   lib, ptr, stream_of)
+from ._lib import (PN2_ATTN_MAX_LAYERS, AttnLayer, InvalidArgumentError, aligned_device_tensor,
+                   check, device_tensor, lib, ptr, stream_of)
 from ._torch_ops import call
 
 
@@ -49,9 +49,9 @@ def attention_reduce_layers(qkvs):
     for i, (Q, K, V) in enumerate(qkvs):
         if Q.dim() == 4 and Q.shape[2] == 1:
             Q = Q.squeeze(2)
-        Q = device_tensor(Q, "Q", torch.float32)
-        K = device_tensor(K, "K", torch.float32)
-        V = device_tensor(V, "V", torch.float32)
+        Q = aligned_device_tensor(Q, "Q", torch.float32)
+        K = aligned_device_tensor(K, "K", torch.float32)
+        V = aligned_device_tensor(V, "V", torch.float32)
         if Q.dim() != 3 or K.dim() != 4 or tuple(V.shape) != tuple(K.shape):
             raise InvalidArgumentError("attention_reduce_layers expects Q (B,M,C), K and V "
                                        "(B,M,ns,C)")

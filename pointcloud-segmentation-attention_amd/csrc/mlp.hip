@@ -1114,6 +1114,10 @@ void set_segments(Params& prm, int nA, bool vecA, int offA, int nB, bool vecB, i
   prm.div_pad = make_fastdiv((uint32_t)(npad > 0 ? npad : 1));
 }
 
+// A source is read as float4 only from a 16-byte aligned base (its row width, a multiple of 4,
+// then keeps every row aligned); any other pointer takes the per-float gather.
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 int check_layers(int nl, const pn2_mlp_layer* layers, int cin0) {
   if (nl < 1 || nl > PN2_MLP_MAX_LAYERS || !layers) return PN2_EINVAL;
   int cin = cin0;
@@ -1325,6 +1329,8 @@ static int group_mlp_impl(const float* xyz, const float* points, const float* ne
   const long long ngroups = (long long)B * M;
   if (ngroups == 0) return PN2_OK;
   if (!xyz || !new_xyz || !idx || !out || ngroups > 0x7fffffffLL) return PN2_EINVAL;
+  // the attention tail loads bn_scale / bn_shift and stores out in float4 units (attn_scores)
+  if (qkv && !(aligned16(out) && aligned16(bn_scale) && aligned16(bn_shift))) return PN2_EINVAL;
   if ((long long)B * N > 0x7fffffffLL || ngroups * nsample > 0x7fffffffLL) return PN2_EINVAL;
   const bool pooled = pool >= 0;
   size_t lds = 0;
@@ -1356,10 +1362,11 @@ static int group_mlp_impl(const float* xyz, const float* points, const float* ne
   prm.M = M;
   prm.ns = nsample;
   prm.layout = layout;
+  const bool vec = C % 4 == 0 && aligned16(points);
   if (layout == kXyzOnly) set_segments(prm, 0, false, 0, 3, false, 0, 3);
-  else if (layout == kPointsOnly) set_segments(prm, C, C % 4 == 0, 0, 0, false, 0, C);
-  else if (layout == kXyzFirst) set_segments(prm, C, C % 4 == 0, 3, 3, false, 0, C + 3);
-  else set_segments(prm, C, C % 4 == 0, 0, 3, false, C, C + 3);
+  else if (layout == kPointsOnly) set_segments(prm, C, vec, 0, 0, false, 0, C);
+  else if (layout == kXyzFirst) set_segments(prm, C, vec, 3, 3, false, 0, C + 3);
+  else set_segments(prm, C, vec, 0, 3, false, C, C + 3);
   prm.ngroups = (int)ngroups;
   prm.pool = pool;
   prm.out = out;
@@ -1432,7 +1439,8 @@ int pn2_fp_mlp(const float* dist, const int32_t* nn_idx, const float* points1, i
   prm.n = n;
   prm.m = m;
   prm.rows = rows;
-  set_segments(prm, C2, C2 % 4 == 0, 0, C1, C1 % 4 == 0 && C2 % 4 == 0, C2, C1 + C2);
+  set_segments(prm, C2, C2 % 4 == 0 && aligned16(points2), 0, C1,
+               C1 % 4 == 0 && C2 % 4 == 0 && aligned16(points1), C2, C1 + C2);
   prm.passes = 1;
   prm.pool = PN2_POOL_NONE;
   prm.out = out;
@@ -1485,7 +1493,7 @@ int pn2_shared_mlp(const float* x, long long rows, int cin, int nlayers,
   prm.x = x;
   prm.cin = cin;
   prm.rows = rows;
-  set_segments(prm, cin, cin % 4 == 0, 0, 0, false, 0, cin);
+  set_segments(prm, cin, cin % 4 == 0 && aligned16(x), 0, 0, false, 0, cin);
   prm.passes = 1;
   prm.pool = PN2_POOL_NONE;
   prm.out = out;

@@ -59,6 +59,15 @@ Tensor dev(const Tensor& t, const char* name, at::ScalarType dt) {
   return t.contiguous();
 }
 
+// dev() for an argument whose C function demands 16-byte alignment (the attention reductions,
+// include/pn2hip.h): a contiguous view at an odd offset into a larger buffer is copied to a
+// fresh allocation. Arguments whose kernels have a scalar path go through dev() and stay put.
+Tensor dev16(const Tensor& t, const char* name, at::ScalarType dt) {
+  Tensor c = dev(t, name, dt);
+  if (reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 != 0) c = c.clone();
+  return c;
+}
+
 int I(int64_t v) { return static_cast<int>(v); }
 at::TensorOptions f32(const Tensor& like) { return like.options().dtype(at::kFloat); }
 at::TensorOptions i32(const Tensor& like) { return like.options().dtype(at::kInt); }
@@ -415,7 +424,8 @@ Tensor fp_fused_hip(const Tensor& xyz1_, const Tensor& xyz2_, const std::optiona
 
 Tensor attn_reduce_hip(const Tensor& Q_, const Tensor& K_, const Tensor& V_) {
   chk_attn(Q_, K_, V_);
-  Tensor Q = dev(Q_, "Q", at::kFloat), K = dev(K_, "K", at::kFloat), V = dev(V_, "V", at::kFloat);
+  Tensor Q = dev16(Q_, "Q", at::kFloat), K = dev16(K_, "K", at::kFloat);
+  Tensor V = dev16(V_, "V", at::kFloat);
   c10::hip::HIPGuard g(Q.device().index());
   const int B = I(K.size(0)), M = I(K.size(1)), ns = I(K.size(2)), C = I(K.size(3));
   Tensor out = at::empty({B, M, C}, f32(Q));
@@ -428,8 +438,8 @@ std::tuple<Tensor, Tensor, Tensor> attn_reduce_grad_hip(const Tensor& Q_, const 
                                                         const Tensor& V_, const Tensor& go_) {
   chk_attn(Q_, K_, V_);
   TORCH_CHECK_VALUE(go_.sizes() == Q_.sizes(), "attn_reduce_grad expects grad_out shaped like Q");
-  Tensor Q = dev(Q_, "Q", at::kFloat), K = dev(K_, "K", at::kFloat), V = dev(V_, "V", at::kFloat);
-  Tensor go = dev(go_, "grad_out", at::kFloat);
+  Tensor Q = dev16(Q_, "Q", at::kFloat), K = dev16(K_, "K", at::kFloat);
+  Tensor V = dev16(V_, "V", at::kFloat), go = dev16(go_, "grad_out", at::kFloat);
   c10::hip::HIPGuard g(Q.device().index());
   const int B = I(K.size(0)), M = I(K.size(1)), ns = I(K.size(2)), C = I(K.size(3));
   Tensor gQ = at::empty_like(Q), gK = at::empty_like(K), gV = at::empty_like(V);
@@ -759,10 +769,10 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> attn_kv_train
     const Tensor& kv_, bool need_grad_x) {
   const char* op = "attn_kv_train_grad";
   chk_attn_kv_grad(grad_att_, grad_pmax_, arg_, x_, wq_, wk_, wv_, q_, kv_, op);
-  Tensor go = dev(grad_att_, "grad_att", at::kFloat), x = dev(x_, "x", at::kFloat);
+  Tensor go = dev16(grad_att_, "grad_att", at::kFloat), x = dev(x_, "x", at::kFloat);
   Tensor wq = dev(wq_, "wq", at::kFloat), wk = dev(wk_, "wk", at::kFloat);
-  Tensor wv = dev(wv_, "wv", at::kFloat), q = dev(q_, "q", at::kFloat);
-  Tensor kv = dev(kv_, "kv", at::kFloat);
+  Tensor wv = dev(wv_, "wv", at::kFloat), q = dev16(q_, "q", at::kFloat);
+  Tensor kv = dev16(kv_, "kv", at::kFloat);
   Tensor gp, arg;
   if (has(grad_pmax_)) {
     gp = dev(*grad_pmax_, "grad_pmax", at::kFloat);

@@ -55,6 +55,10 @@ def group_concat(xyz, points, new_xyz, idx, use_xyz=True, xyz_last=False, want_g
     csrc/geom_train.hip: the same forward bits, and gradients that two runs reproduce bit for
     bit. A gradient for xyz or new_xyz (or ordered_grad=False) keeps the composition of the
     reference's ops, whose grouping gradient is a float-atomic scatter."""
+    # (contiguous: the kernel reads dense rows; xyz is often a channel slice of the input)
+    xyz = device_tensor(xyz, "xyz", torch.float32)
+    new_xyz = device_tensor(new_xyz, "new_xyz", torch.float32)
+    idx = device_tensor(idx, "idx", torch.int32)
     B, N = int(xyz.shape[0]), int(xyz.shape[1])
     M, ns = int(idx.shape[1]), int(idx.shape[2])
     if _is_empty_points(points):
@@ -400,7 +404,8 @@ def fp_apply(nn, points1, points2, unknown_grid=None):
     three_nn distances, three_interpolate and concat [interpolated, points1] -- nn = (dist, idx)
     of tf_interpolate.three_nn over the same points (unknown_grid: the grid that search took
     its unknowns' order from; rows are written in that order). Returns (B, n, C2 + C1)."""
-    dist, idx = nn
+    dist = device_tensor(nn[0], "dist", torch.float32)
+    idx = device_tensor(nn[1], "idx", torch.int32)
     points2 = device_tensor(points2, "points2", torch.float32)
     B, n, m, C2 = int(dist.shape[0]), int(dist.shape[1]), int(points2.shape[1]), int(points2.shape[2])
     if tuple(idx.shape) != (B, n, 3) or tuple(dist.shape) != (B, n, 3) or int(points2.shape[0]) != B:

@@ -86,6 +86,42 @@ def test_argument_checks_return_einval_without_launching(pn2):
     assert lib.pn2_three_nn(None, None, 0, 10, 10, None, None, None) == 0
 
 
+def test_alignment_demanding_entry_points_return_einval(pn2):
+    """The entry points that need 16-byte aligned buffers (include/pn2hip.h, Conventions) say
+    so with PN2_EINVAL before any launch: fake device addresses, one of them 4, 8 or 12 bytes
+    off in turn. (The front ends copy such a tensor first; tests/test_gpu_layouts.py.)"""
+    import ctypes
+    lib = pn2.lib()
+    E, ok = -22, 1 << 20
+    for off in (4, 8, 12):
+        for i in range(4):   # Q, K, V, out
+            p = [ok] * 4
+            p[i] += off
+            assert lib.pn2_attn_reduce(p[0], p[1], p[2], 1, 1, 8, 8, p[3], None) == E
+            arr = (pn2._lib.AttnLayer * 2)(pn2._lib.AttnLayer(ok, ok, ok, 0, 8, 8, ok),
+                                           pn2._lib.AttnLayer(p[0], p[1], p[2], 1, 8, 8, p[3]))
+            assert lib.pn2_attn_reduce_layers(ctypes.addressof(arr), 2, 1, None) == E
+        for i in range(7):   # Q, K, V, grad_out, grad_Q, grad_K, grad_V
+            p = [ok] * 7
+            p[i] += off
+            assert lib.pn2_attn_reduce_grad(p[0], p[1], p[2], p[3], 1, 1, 8, 8, p[4], p[5], p[6],
+                                            None) == E
+        # pn2_group_mlp_attention: out, bn_scale and bn_shift (float4 units in its tail)
+        ML = pn2._lib.MlpLayer
+        layers = (ML * 1)(ML(ok, 3, 32, 1))
+        qkv = (ML * 3)(*[ML(ok, 32, 32, 0) for _ in range(3)])
+        for i in range(3):   # out, bn_scale, bn_shift
+            p = [ok] * 3
+            p[i] += off
+            assert lib.pn2_group_mlp_attention(ok, None, ok, ok, 1, 16, 0, 2, 8, 1, 1, layers, qkv,
+                                               p[1], p[2], 0, p[0], None) == E
+        assert lib.pn2_copy_f4(ok + off, ok, 64, 1, None) == E
+        assert lib.pn2_copy_f4(ok, ok + off, 64, 1, None) == E
+        assert lib.pn2_copy_f4(ok, ok, 64 + off, 1, None) == E
+    assert lib.pn2_copy_f4(ok, ok, 0, 1, None) == 0          # nothing to copy
+    assert lib.pn2_copy_f4(ok + 4, ok, 0, 1, None) == 0
+
+
 def test_grid_contract(pn2):
     lib = pn2.lib()
     E = -22
