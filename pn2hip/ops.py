@@ -1,7 +1,7 @@
 """torch.ops.pn2.* under the reference's op names and argument order.
 
-Each name is the registered PyTorch operator itself (csrc/torch_ops.cpp: HIP + Meta kernels,
-autograd for gather_point / group_point / three_interpolate / attn_reduce and the training
+Each name is the registered PyTorch operator itself (csrc/torch_ops.cpp: one body under the CUDA
+and Meta keys, so a fake tensor meets the device call's checks; autograd for gather_point / group_point / three_interpolate / attn_reduce and the training
 layers mlp_layer_train, mlp_layer_train_pool, attn_kv_train, bn_train), so calls are
 visible to torch.compile and TorchScript:
 
@@ -79,7 +79,7 @@ train.py:145-163, :337), none of it differentiable:
 
 and whole-scene prediction and the label look-ups of the benchmark score (csrc/predict.hip;
 attention_points/benchmark/generate_predictions.py:19-53, :139-186, evaluate.py:58-83). These
-four are listed in HOST_NAMES, not NAMES: next to the HIP and Meta kernels they have CPU kernels
+four are listed in HOST_NAMES, not NAMES: next to the CUDA and Meta keys they have CPU kernels
 (host twins with equal bits), because everything in them is integers and copied bytes:
 
     scene_vote(logits, mask, orig, row0, keys)          argmax per chunk row and a 64-bit atomic

@@ -1,7 +1,7 @@
 """torch.ops.pn2.* — the C ABI registered as PyTorch operators (csrc/torch_ops.cpp, built into
 libpn2torch.so next to libpn2hip.so): TORCH_LIBRARY schemas with the reference's op names and
-argument order, HIP kernels that launch on the current HIP stream, Meta kernels for fake
-tensors / torch.compile. This module loads the library and registers autograd for the ops the
+argument order, one body per op that launches on the current HIP stream and, registered under
+Meta as well, gives fake tensors / torch.compile the same checks and output shapes. This module loads the library and registers autograd for the ops the
 reference registers gradients for, w.r.t. the points only (tf_sampling.py:44-48 GatherPoint,
 tf_grouping.py:42-46 GroupPoint, tf_interpolate.py:29-34 ThreeInterpolate), plus the attention
 reduction (TF autodiff through attention_layer.py:35-42, all of Q, K, V) and the training-mode

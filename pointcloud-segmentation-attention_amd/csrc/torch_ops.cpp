@@ -7,8 +7,10 @@
 // ValueError (TORCH_CHECK_VALUE) with the reference's message, outputs come from the caching
 // allocator, and every launch goes on the current HIP stream of the input's device
 // (c10::hip::getCurrentHIPStream), so the ops compose with torch streams and hipGraph capture.
-// Each op has a CUDA (= HIP on ROCm) kernel and a Meta kernel (shapes only, for fake tensors
-// and torch.compile). Autograd for gather_point / group_point / three_interpolate (w.r.t.
+// Each op has one body, registered under the CUDA (= HIP on ROCm) and the Meta dispatch keys:
+// fake tensors and torch.compile get the device call's checks, dtypes and output shapes, and the
+// body returns before its first launch.
+// Autograd for gather_point / group_point / three_interpolate (w.r.t.
 // the points only, tf_sampling.py:44-48, tf_grouping.py:42-46, tf_interpolate.py:29-34) and
 // attn_reduce is registered from Python (torch.library.register_autograd, _torch_ops.py), and
 // so is the training-mode shared-MLP layer's (mlp_layer_train -> mlp_layer_train_grad, and
@@ -21,8 +23,9 @@
 // ThreeInterpolate, ThreeInterpolateGrad: registered for DEVICE_CPU only,
 // tf_interpolate.cpp:187,222,262), through the host twins pn2cpu_* (csrc/cpu_interp.cpp);
 // and for the four prediction ops (scene_vote, scene_labels, map_back_rows, label_lut: integers
-// and copied bytes, host twins in csrc/cpu_predict.cpp with equal bits); every other op has no
-// CPU kernel, so a CPU tensor fails in the dispatcher (no CPU fallback).
+// and copied bytes, host twins in csrc/cpu_predict.cpp with equal bits). Those seven bodies are
+// templates over HIP / CPU; every other op has no CPU kernel, so a CPU tensor fails in the
+// dispatcher (no CPU fallback).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -51,9 +54,12 @@ void check_rc(int rc, const char* op) {
   TORCH_CHECK(rc == 0, op, ": HIP error ", rc, ": ", pn2_strerror(rc));
 }
 
-// A GPU input of the reference dtype, made contiguous.
+// a fake tensor (the Meta key): the body runs up to its allocations and returns them
+bool fake(const Tensor& t) { return t.device().type() == at::kMeta; }
+
+// A GPU (or Meta) input of the reference dtype, made contiguous.
 Tensor dev(const Tensor& t, const char* name, at::ScalarType dt) {
-  TORCH_CHECK(t.is_cuda(), name, " is on ", t.device(),
+  TORCH_CHECK(t.is_cuda() || fake(t), name, " is on ", t.device(),
               ": pn2hip ops run on the MI355X only (no CPU fallback)");
   TORCH_CHECK_TYPE(t.scalar_type() == dt, name, " must be ", dt, ", got ", t.scalar_type());
   return t.contiguous();
@@ -64,7 +70,7 @@ Tensor dev(const Tensor& t, const char* name, at::ScalarType dt) {
 // fresh allocation. Arguments whose kernels have a scalar path go through dev() and stay put.
 Tensor dev16(const Tensor& t, const char* name, at::ScalarType dt) {
   Tensor c = dev(t, name, dt);
-  if (reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 != 0) c = c.clone();
+  if (!fake(c) && reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 != 0) c = c.clone();
   return c;
 }
 
@@ -76,7 +82,7 @@ const float* F(const Tensor& t) { return t.defined() ? t.data_ptr<float>() : nul
 const int32_t* Ii(const Tensor& t) { return t.data_ptr<int32_t>(); }
 
 // ------------------------------------------------------------------------- shape checks
-// Shared by the HIP and Meta kernels (the messages are the reference's OP_REQUIRES texts).
+// (the messages are the reference's OP_REQUIRES texts)
 void chk_fps(int64_t npoint, const Tensor& inp) {
   TORCH_CHECK_VALUE(npoint > 0, "FarthestPointSample expects positive npoint");  // tf_sampling.cpp:99
   TORCH_CHECK_VALUE(inp.dim() == 3 && inp.size(2) == 3,                          // :105
@@ -169,15 +175,17 @@ Tensor grid_over(const Tensor& xyz, double cell_edge, const char* op) {
   return g;
 }
 
-// ------------------------------------------------------------------------- HIP kernels
+// ------------------------------------------------------------------------- the ops' bodies
+// Each: the shape checks; the inputs (dev / dev16 / dev_opt) and every output; the return for Meta;
+// then the device guard, workspaces and launches.
 std::tuple<Tensor, Tensor> fps_and_gather_hip(int64_t npoint, const Tensor& inp_) {
   chk_fps(npoint, inp_);
   Tensor inp = dev(inp_, "inp", at::kFloat);
-  c10::hip::HIPGuard g(inp.device().index());
   const int B = I(inp.size(0)), N = I(inp.size(1)), M = I(npoint);
   Tensor idx = at::empty({B, M}, i32(inp));
   Tensor nx = at::empty({B, M, 3}, f32(inp));
-  if (B == 0) return {idx, nx};
+  if (fake(inp) || B == 0) return {idx, nx};
+  c10::hip::HIPGuard g(inp.device().index());
   const size_t ws = pn2_fps_workspace_size(B, N);
   if (ws) {
     Tensor w = at::empty({static_cast<int64_t>((ws + 3) / 4)}, f32(inp));
@@ -194,9 +202,10 @@ Tensor fps_hip(int64_t npoint, const Tensor& inp) { return std::get<0>(fps_and_g
 Tensor gather_point_hip(const Tensor& inp_, const Tensor& idx_) {
   chk_gather(inp_, idx_, "GatherPoint");
   Tensor inp = dev(inp_, "inp", at::kFloat), idx = dev(idx_, "idx", at::kInt);
-  c10::hip::HIPGuard g(inp.device().index());
   const int B = I(inp.size(0)), N = I(inp.size(1)), M = I(idx.size(1));
   Tensor out = at::empty({B, M, 3}, f32(inp));
+  if (fake(inp)) return out;
+  c10::hip::HIPGuard g(inp.device().index());
   check_rc(pn2_gather_point(F(inp), Ii(idx), B, N, M, out.data_ptr<float>(), stream_of(inp)),
            "GatherPoint");
   return out;
@@ -209,8 +218,9 @@ Tensor gather_point_grad_hip(const Tensor& inp, const Tensor& idx_, const Tensor
                         out_g_.size(2) == 3,
                     "GatherPointGradGpuOp expects (batch_size,num_result,3) out_g shape");
   Tensor idx = dev(idx_, "idx", at::kInt), out_g = dev(out_g_, "out_g", at::kFloat);
-  c10::hip::HIPGuard g(out_g.device().index());
   Tensor inp_g = at::empty({B, N, 3}, f32(out_g));
+  if (fake(out_g)) return inp_g;
+  c10::hip::HIPGuard g(out_g.device().index());
   check_rc(pn2_gather_point_grad(F(out_g), Ii(idx), B, N, M, inp_g.data_ptr<float>(),
                                  stream_of(out_g)), "GatherPointGrad");
   return inp_g;
@@ -219,10 +229,10 @@ Tensor gather_point_grad_hip(const Tensor& inp, const Tensor& idx_, const Tensor
 Tensor prob_sample_hip(const Tensor& inp_, const Tensor& inpr_) {
   chk_prob(inp_, inpr_);
   Tensor inp = dev(inp_, "inp", at::kFloat), inpr = dev(inpr_, "inpr", at::kFloat);
-  c10::hip::HIPGuard g(inp.device().index());
   const int B = I(inp.size(0)), N = I(inp.size(1)), M = I(inpr.size(1));
   Tensor out = at::empty({B, M}, i32(inp));
-  if (B == 0 || M == 0) return out;
+  if (fake(inp) || B == 0 || M == 0) return out;
+  c10::hip::HIPGuard g(inp.device().index());
   const size_t ws = pn2_prob_sample_workspace_size(B, N);
   Tensor w = at::empty({static_cast<int64_t>(ws / 4 > 1 ? ws / 4 : 1)}, f32(inp));
   check_rc(pn2_prob_sample(F(inp), F(inpr), B, N, M, w.data_ptr<float>(), ws,
@@ -234,10 +244,11 @@ std::tuple<Tensor, Tensor> query_ball_point_hip(double radius, int64_t nsample, 
                                                 const Tensor& xyz2_) {
   chk_ball(radius, nsample, xyz1_, xyz2_);
   Tensor xyz1 = dev(xyz1_, "xyz1", at::kFloat), xyz2 = dev(xyz2_, "xyz2", at::kFloat);
-  c10::hip::HIPGuard g(xyz1.device().index());
   const int B = I(xyz1.size(0)), N = I(xyz1.size(1)), M = I(xyz2.size(1)), ns = I(nsample);
   Tensor idx = at::empty({B, M, ns}, i32(xyz1));
   Tensor cnt = at::empty({B, M}, i32(xyz1));
+  if (fake(xyz1)) return {idx, cnt};
+  c10::hip::HIPGuard g(xyz1.device().index());
   const float r = static_cast<float>(radius);
   if (N >= kBallGridMinPoints && int64_t(B) * M >= kBallGridMinQueries) {
     Tensor grid = grid_over(xyz1, r, "QueryBallPoint");
@@ -255,10 +266,11 @@ std::tuple<Tensor, Tensor> select_top_k_hip(int64_t k, const Tensor& dist_) {
   TORCH_CHECK_VALUE(dist_.dim() == 3, "SelectionSort expects (b,m,n) dist shape.");  // :118
   TORCH_CHECK_VALUE(k <= dist_.size(2), "SelectionSort expects k <= n");
   Tensor dist = dev(dist_, "dist", at::kFloat);
-  c10::hip::HIPGuard g(dist.device().index());
   const int B = I(dist.size(0)), m = I(dist.size(1)), n = I(dist.size(2));
   Tensor outi = at::empty({B, m, n}, i32(dist));
   Tensor out = at::empty({B, m, n}, f32(dist));
+  if (fake(dist)) return {outi, out};
+  c10::hip::HIPGuard g(dist.device().index());
   size_t ws = pn2_select_top_k_workspace_size(B, m, I(k));
   Tensor w = at::empty({static_cast<int64_t>(ws > 16 ? ws : 16)}, dist.options().dtype(at::kByte));
   check_rc(pn2_select_top_k(F(dist), B, m, n, I(k), outi.data_ptr<int32_t>(), out.data_ptr<float>(),
@@ -276,10 +288,11 @@ void chk_knn(int64_t k, const Tensor& xyz1, const Tensor& xyz2) {
 std::tuple<Tensor, Tensor> knn_point_hip(int64_t k, const Tensor& xyz1_, const Tensor& xyz2_) {
   chk_knn(k, xyz1_, xyz2_);
   Tensor xyz1 = dev(xyz1_, "xyz1", at::kFloat), xyz2 = dev(xyz2_, "xyz2", at::kFloat);
-  c10::hip::HIPGuard g(xyz1.device().index());
   const int B = I(xyz1.size(0)), n = I(xyz1.size(1)), c = I(xyz1.size(2)), m = I(xyz2.size(1));
   Tensor val = at::empty({B, m, k}, f32(xyz1));
   Tensor idx = at::empty({B, m, k}, i32(xyz1));
+  if (fake(xyz1)) return {val, idx};
+  c10::hip::HIPGuard g(xyz1.device().index());
   check_rc(pn2_knn_point(F(xyz1), F(xyz2), B, n, m, c, I(k), val.data_ptr<float>(),
                          idx.data_ptr<int32_t>(), stream_of(xyz1)), "knn_point");
   return {val, idx};
@@ -288,10 +301,11 @@ std::tuple<Tensor, Tensor> knn_point_hip(int64_t k, const Tensor& xyz1_, const T
 Tensor group_point_hip(const Tensor& points_, const Tensor& idx_) {
   chk_group(points_, idx_, "GroupPoint");
   Tensor points = dev(points_, "points", at::kFloat), idx = dev(idx_, "idx", at::kInt);
-  c10::hip::HIPGuard g(points.device().index());
   const int B = I(points.size(0)), N = I(points.size(1)), C = I(points.size(2));
   const int M = I(idx.size(1)), ns = I(idx.size(2));
   Tensor out = at::empty({B, M, ns, C}, f32(points));
+  if (fake(points)) return out;
+  c10::hip::HIPGuard g(points.device().index());
   check_rc(pn2_group_point(F(points), Ii(idx), B, N, C, M, ns, out.data_ptr<float>(),
                            stream_of(points)), "GroupPoint");
   return out;
@@ -305,8 +319,9 @@ Tensor group_point_grad_hip(const Tensor& points, const Tensor& idx_, const Tens
                         grad_out_.size(2) == ns && grad_out_.size(3) == C,  // tf_grouping.cpp:191
                     "GroupPointGrad expects (batch_size, npoints, nsample, channel) grad_out shape");
   Tensor idx = dev(idx_, "idx", at::kInt), grad_out = dev(grad_out_, "grad_out", at::kFloat);
-  c10::hip::HIPGuard g(grad_out.device().index());
   Tensor gp = at::empty({B, N, C}, f32(grad_out));
+  if (fake(grad_out)) return gp;
+  c10::hip::HIPGuard g(grad_out.device().index());
   check_rc(pn2_group_point_grad(F(grad_out), Ii(idx), B, N, C, M, ns, gp.data_ptr<float>(),
                                 stream_of(grad_out)), "GroupPointGrad");
   return gp;
@@ -321,13 +336,14 @@ std::tuple<Tensor, Tensor> group_concat_impl(const Tensor& xyz_, const std::opti
   Tensor idx = dev(idx_, "idx", at::kInt);
   Tensor points;
   if (points_.has_value() && points_->numel() > 0) points = dev(*points_, "points", at::kFloat);
-  c10::hip::HIPGuard g(xyz.device().index());
   const int B = I(xyz.size(0)), N = I(xyz.size(1)), M = I(idx.size(1)), ns = I(idx.size(2));
   const int C = points.defined() ? I(points.size(2)) : 0;
   const int cout = !points.defined() ? 3 : (use_xyz ? C + 3 : C);
   Tensor gx;
   if (want_gx) gx = at::empty({B, M, ns, 3}, f32(xyz));
   Tensor np = at::empty({B, M, ns, cout}, f32(xyz));
+  if (fake(xyz)) return {gx, np};
+  c10::hip::HIPGuard g(xyz.device().index());
   const int flags = (use_xyz ? PN2_USE_XYZ : 0) | (xyz_last ? PN2_XYZ_LAST : 0);
   check_rc(pn2_group_concat(F(xyz), F(points), F(new_xyz), Ii(idx), B, N, C, M, ns, flags,
                             want_gx ? gx.data_ptr<float>() : nullptr, np.data_ptr<float>(),
@@ -341,13 +357,29 @@ std::tuple<Tensor, Tensor> group_concat_hip(const Tensor& xyz, const std::option
   return group_concat_impl(xyz, points, new_xyz, idx, use_xyz, xyz_last, true);
 }
 
-std::tuple<Tensor, Tensor> three_nn_hip(const Tensor& xyz1_, const Tensor& xyz2_) {
+// The three ops the reference itself runs on the CPU have host twins (csrc/cpu_interp.cpp):
+// HIP false is the CPU kernel, which takes its inputs through host() and calls pn2cpu_*.
+Tensor host(const Tensor& t, const char* name, at::ScalarType dt) {
+  TORCH_CHECK(t.device().is_cpu(), name, " must be a CPU tensor here");
+  TORCH_CHECK_TYPE(t.scalar_type() == dt, name, " must be ", dt, ", got ", t.scalar_type());
+  return t.contiguous();
+}
+
+template <bool HIP>
+std::tuple<Tensor, Tensor> three_nn_impl(const Tensor& xyz1_, const Tensor& xyz2_) {
   chk_nn(xyz1_, xyz2_);
-  Tensor xyz1 = dev(xyz1_, "xyz1", at::kFloat), xyz2 = dev(xyz2_, "xyz2", at::kFloat);
-  c10::hip::HIPGuard g(xyz1.device().index());
+  const auto in = HIP ? dev : host;
+  Tensor xyz1 = in(xyz1_, "xyz1", at::kFloat), xyz2 = in(xyz2_, "xyz2", at::kFloat);
   const int B = I(xyz1.size(0)), n = I(xyz1.size(1)), m = I(xyz2.size(1));
   Tensor dist = at::empty({B, n, 3}, f32(xyz1));
   Tensor idx = at::empty({B, n, 3}, i32(xyz1));
+  if (fake(xyz1)) return {dist, idx};
+  if (!HIP) {
+    check_rc(pn2cpu_three_nn(F(xyz1), F(xyz2), B, n, m, dist.data_ptr<float>(),
+                             idx.data_ptr<int32_t>()), "ThreeNN");
+    return {dist, idx};
+  }
+  c10::hip::HIPGuard g(xyz1.device().index());
   if (int64_t(n) * m >= kNnGridMinPairs && m >= kNnGridMinKnown) {
     Tensor grid = grid_over(xyz2, 0.0, "ThreeNN");
     check_rc(pn2_three_nn_grid(P(grid), nullptr, F(xyz1), B, n, m, dist.data_ptr<float>(),
@@ -359,40 +391,57 @@ std::tuple<Tensor, Tensor> three_nn_hip(const Tensor& xyz1_, const Tensor& xyz2_
   return {dist, idx};
 }
 
-Tensor three_interpolate_hip(const Tensor& points_, const Tensor& idx_, const Tensor& weight_) {
+template <bool HIP>
+Tensor three_interpolate_impl(const Tensor& points_, const Tensor& idx_, const Tensor& weight_) {
   chk_interp(points_, idx_, weight_, "ThreeInterpolate");
-  Tensor points = dev(points_, "points", at::kFloat), idx = dev(idx_, "idx", at::kInt);
-  Tensor weight = dev(weight_, "weight", at::kFloat);
-  c10::hip::HIPGuard g(points.device().index());
+  const auto in = HIP ? dev : host;
+  Tensor points = in(points_, "points", at::kFloat), idx = in(idx_, "idx", at::kInt);
+  Tensor weight = in(weight_, "weight", at::kFloat);
   const int B = I(points.size(0)), m = I(points.size(1)), C = I(points.size(2)), n = I(idx.size(1));
   Tensor out = at::empty({B, n, C}, f32(points));
-  check_rc(pn2_three_interpolate(F(points), Ii(idx), F(weight), B, m, C, n, out.data_ptr<float>(),
-                                 stream_of(points)), "ThreeInterpolate");
+  if (fake(points)) return out;
+  if (HIP) {
+    c10::hip::HIPGuard g(points.device().index());
+    check_rc(pn2_three_interpolate(F(points), Ii(idx), F(weight), B, m, C, n,
+                                   out.data_ptr<float>(), stream_of(points)), "ThreeInterpolate");
+  } else {
+    check_rc(pn2cpu_three_interpolate(F(points), Ii(idx), F(weight), B, m, C, n,
+                                      out.data_ptr<float>()), "ThreeInterpolate");
+  }
   return out;
 }
 
-Tensor three_interpolate_grad_hip(const Tensor& points, const Tensor& idx_, const Tensor& weight_,
-                                  const Tensor& grad_out_) {
+template <bool HIP>
+Tensor three_interpolate_grad_impl(const Tensor& points, const Tensor& idx_, const Tensor& weight_,
+                                   const Tensor& grad_out_) {
   chk_interp(points, idx_, weight_, "ThreeInterpolateGrad");
   const int B = I(points.size(0)), m = I(points.size(1)), C = I(points.size(2)), n = I(idx_.size(1));
   TORCH_CHECK_VALUE(grad_out_.dim() == 3 && grad_out_.size(0) == B && grad_out_.size(1) == n &&
                         grad_out_.size(2) == C,  // tf_interpolate.cpp:243
                     "ThreeInterpolateGrad expects (b,n,c) grad_out shape");
-  Tensor idx = dev(idx_, "idx", at::kInt), weight = dev(weight_, "weight", at::kFloat);
-  Tensor grad_out = dev(grad_out_, "grad_out", at::kFloat);
-  c10::hip::HIPGuard g(grad_out.device().index());
+  const auto in = HIP ? dev : host;
+  Tensor idx = in(idx_, "idx", at::kInt), weight = in(weight_, "weight", at::kFloat);
+  Tensor grad_out = in(grad_out_, "grad_out", at::kFloat);
   Tensor gp = at::empty({B, m, C}, f32(grad_out));
-  check_rc(pn2_three_interpolate_grad(F(grad_out), Ii(idx), F(weight), B, n, C, m,
-                                      gp.data_ptr<float>(), stream_of(grad_out)),
-           "ThreeInterpolateGrad");
+  if (fake(grad_out)) return gp;
+  if (HIP) {
+    c10::hip::HIPGuard g(grad_out.device().index());
+    check_rc(pn2_three_interpolate_grad(F(grad_out), Ii(idx), F(weight), B, n, C, m,
+                                        gp.data_ptr<float>(), stream_of(grad_out)),
+             "ThreeInterpolateGrad");
+  } else {
+    check_rc(pn2cpu_three_interpolate_grad(F(grad_out), Ii(idx), F(weight), B, n, C, m,
+                                           gp.data_ptr<float>()), "ThreeInterpolateGrad");
+  }
   return gp;
 }
 
 Tensor idw_weights_hip(const Tensor& dist_) {
   TORCH_CHECK_VALUE(dist_.dim() == 3 && dist_.size(2) == 3, "idw_weights expects (b,n,3) dist shape");
   Tensor dist = dev(dist_, "dist", at::kFloat);
-  c10::hip::HIPGuard g(dist.device().index());
   Tensor w = at::empty_like(dist);
+  if (fake(dist)) return w;
+  c10::hip::HIPGuard g(dist.device().index());
   check_rc(pn2_idw_weights(F(dist), I(dist.size(0)), I(dist.size(1)), w.data_ptr<float>(),
                            stream_of(dist)), "idw_weights");
   return w;
@@ -413,10 +462,11 @@ Tensor fp_fused_hip(const Tensor& xyz1_, const Tensor& xyz2_, const std::optiona
                       "fp_fused expects (b,n,c1) points1");
     points1 = dev(*points1_, "points1", at::kFloat);
   }
-  c10::hip::HIPGuard g(xyz1.device().index());
   const int B = I(xyz1.size(0)), n = I(xyz1.size(1)), m = I(xyz2.size(1)), C2 = I(points2.size(2));
   const int C1 = points1.defined() ? I(points1.size(2)) : 0;
   Tensor out = at::empty({B, n, C2 + C1}, f32(xyz1));
+  if (fake(xyz1)) return out;
+  c10::hip::HIPGuard g(xyz1.device().index());
   check_rc(pn2_fp_fused(F(xyz1), F(xyz2), F(points1), C1, F(points2), C2, B, n, m,
                         out.data_ptr<float>(), stream_of(xyz1)), "fp_fused");
   return out;
@@ -426,9 +476,10 @@ Tensor attn_reduce_hip(const Tensor& Q_, const Tensor& K_, const Tensor& V_) {
   chk_attn(Q_, K_, V_);
   Tensor Q = dev16(Q_, "Q", at::kFloat), K = dev16(K_, "K", at::kFloat);
   Tensor V = dev16(V_, "V", at::kFloat);
-  c10::hip::HIPGuard g(Q.device().index());
   const int B = I(K.size(0)), M = I(K.size(1)), ns = I(K.size(2)), C = I(K.size(3));
   Tensor out = at::empty({B, M, C}, f32(Q));
+  if (fake(Q)) return out;
+  c10::hip::HIPGuard g(Q.device().index());
   check_rc(pn2_attn_reduce(F(Q), F(K), F(V), B, M, ns, C, out.data_ptr<float>(), stream_of(Q)),
            "attn_reduce");
   return out;
@@ -440,9 +491,10 @@ std::tuple<Tensor, Tensor, Tensor> attn_reduce_grad_hip(const Tensor& Q_, const 
   TORCH_CHECK_VALUE(go_.sizes() == Q_.sizes(), "attn_reduce_grad expects grad_out shaped like Q");
   Tensor Q = dev16(Q_, "Q", at::kFloat), K = dev16(K_, "K", at::kFloat);
   Tensor V = dev16(V_, "V", at::kFloat), go = dev16(go_, "grad_out", at::kFloat);
-  c10::hip::HIPGuard g(Q.device().index());
   const int B = I(K.size(0)), M = I(K.size(1)), ns = I(K.size(2)), C = I(K.size(3));
   Tensor gQ = at::empty_like(Q), gK = at::empty_like(K), gV = at::empty_like(V);
+  if (fake(Q)) return {gQ, gK, gV};
+  c10::hip::HIPGuard g(Q.device().index());
   check_rc(pn2_attn_reduce_grad(F(Q), F(K), F(V), F(go), B, M, ns, C, gQ.data_ptr<float>(),
                                 gK.data_ptr<float>(), gV.data_ptr<float>(), stream_of(Q)),
            "attn_reduce_grad");
@@ -454,9 +506,10 @@ Tensor group_pool_hip(const Tensor& x_, const std::optional<Tensor>& gxyz_, int6
   Tensor x = dev(x_, "x", at::kFloat);
   Tensor gxyz;
   if (mode == PN2_POOL_WEIGHTED_AVG) gxyz = dev(*gxyz_, "grouped_xyz", at::kFloat);
-  c10::hip::HIPGuard g(x.device().index());
   const int B = I(x.size(0)), M = I(x.size(1)), ns = I(x.size(2)), C = I(x.size(3));
   Tensor out = at::empty({B, M, mode == PN2_POOL_MAX_AND_AVG ? 2 * C : C}, f32(x));
+  if (fake(x)) return out;
+  c10::hip::HIPGuard g(x.device().index());
   check_rc(pn2_group_pool(F(x), F(gxyz), B, M, ns, C, I(mode), out.data_ptr<float>(), stream_of(x)),
            "group_pool");
   return out;
@@ -602,7 +655,6 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_train_fwd(
   Tensor bias = dev_opt(bias_, "bias"), gamma = dev_opt(gamma_, "gamma");
   Tensor beta = dev_opt(beta_, "beta");
   const bool bn = gamma.defined();
-  c10::hip::HIPGuard g(x.device().index());
   const int cin = I(weight.size(0)), cout = I(weight.size(1));
   const int64_t rows = x.numel() / cin;
   const std::vector<int64_t> out_sizes = pooled ? pooled_sizes(x, cout) : with_last(x, cout);
@@ -610,6 +662,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_train_fwd(
   if (pooled) arg = at::empty(out_sizes, i32(x));
   Tensor y = at::empty(with_last(x, cout), f32(x));
   Tensor mean = at::empty({bn ? cout : 0}, f32(x)), var = at::empty({bn ? cout : 0}, f32(x));
+  if (fake(x)) return {out, y, mean, var, arg};
+  c10::hip::HIPGuard g(x.device().index());
   if (no_rows(rows, {&mean, &var})) return {out, y, mean, var, arg};
   linear_rows(x, weight, bias, rows, y, op);
   if (bn) bn_stats(y, rows, cout, mean, var, op);
@@ -643,7 +697,6 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_train_bwd(
   Tensor y = dev(y_, "y", at::kFloat);
   Tensor mean = dev_opt(mean_, "mean", bn), var = dev_opt(var_, "var", bn);
   Tensor gamma = dev_opt(gamma_, "gamma"), beta = dev_opt(beta_, "beta");
-  c10::hip::HIPGuard g(x.device().index());
   const int cin = I(weight.size(0)), cout = I(weight.size(1));
   const int64_t rows = x.numel() / cin;
   Tensor grad_x = need_grad_x ? at::empty(x.sizes(), f32(x)) : at::empty({0}, f32(x));
@@ -652,6 +705,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_train_bwd(
   Tensor grad_b = bn ? at::zeros({cout}, f32(x)) : at::empty({cout}, f32(x));
   Tensor grad_gamma = at::empty({bn ? cout : 0}, f32(x));
   Tensor grad_beta = at::empty({bn ? cout : 0}, f32(x));
+  if (fake(x)) return {grad_x, grad_w, grad_b, grad_gamma, grad_beta};
+  c10::hip::HIPGuard g(x.device().index());
   if (no_rows(rows, {&grad_w, &grad_b, &grad_gamma, &grad_beta}))
     return {grad_x, grad_w, grad_b, grad_gamma, grad_beta};
   Tensor grad_y = at::empty(y.sizes(), f32(x));
@@ -742,7 +797,6 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> attn_kv_train_hip(
   Tensor wq = dev(wq_, "wq", at::kFloat), bq = dev(bq_, "bq", at::kFloat);
   Tensor wk = dev(wk_, "wk", at::kFloat), bk = dev(bk_, "bk", at::kFloat);
   Tensor wv = dev(wv_, "wv", at::kFloat), bv = dev(bv_, "bv", at::kFloat);
-  c10::hip::HIPGuard g(x.device().index());
   const int C = I(x.size(-1)), ns = I(x.size(-2));
   const int64_t rows = x.numel() / C, G = rows / ns;
   const std::vector<int64_t> pooled = pooled_sizes(x, C);
@@ -750,7 +804,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> attn_kv_train_hip(
   Tensor kv = at::empty(with_last(x, 2 * C), f32(x));
   Tensor pmax = add_max ? at::empty(pooled, f32(x)) : at::empty({0}, f32(x));
   Tensor arg = add_max ? at::empty(pooled, i32(x)) : at::empty({0}, i32(x));
-  if (G == 0) return {att, pmax, arg, q, kv};
+  if (fake(x) || G == 0) return {att, pmax, arg, q, kv};
+  c10::hip::HIPGuard g(x.device().index());
   // the query is the group's first row (attention_layer.py:259): G rows
   linear_rows(x.select(-2, 0).contiguous(), wq, bq, G, q, op);
   // [K | V] = x [wk | wv] + [bk | bv]: one GEMM, x read once
@@ -778,11 +833,14 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> attn_kv_train
     gp = dev(*grad_pmax_, "grad_pmax", at::kFloat);
     arg = dev(arg_, "arg", at::kInt);
   }
-  c10::hip::HIPGuard g(x.device().index());
   const int C = I(x.size(-1)), ns = I(x.size(-2));
   const int64_t rows = x.numel() / C, G = rows / ns;
   Tensor grad_x = need_grad_x ? at::empty(x.sizes(), f32(x)) : at::empty({0}, f32(x));
   Tensor grad_wq = at::empty({C, C}, f32(x)), grad_bq = at::empty({C}, f32(x));
+  if (fake(x))  // the k and v gradients are slices of joint ones below: (C, C) and (C) again
+    return {grad_x, grad_wq, grad_bq, at::empty_like(grad_wq), at::empty_like(grad_bq),
+            at::empty_like(grad_wq), at::empty_like(grad_bq)};
+  c10::hip::HIPGuard g(x.device().index());
   if (G == 0) {
     grad_wq.zero_();
     grad_bq.zero_();
@@ -826,11 +884,12 @@ std::tuple<Tensor, Tensor, Tensor> bn_train_hip(const Tensor& x_, const Tensor& 
   chk_bn(x_, gamma_, beta_, op);
   Tensor x = dev(x_, "x", at::kFloat), gamma = dev(gamma_, "gamma", at::kFloat);
   Tensor beta = dev(beta_, "beta", at::kFloat);
-  c10::hip::HIPGuard g(x.device().index());
   const int C = I(x.size(-1));
   const int64_t rows = x.numel() / C;
   Tensor out = at::empty(x.sizes(), f32(x));
   Tensor mean = at::empty({C}, f32(x)), var = at::empty({C}, f32(x));
+  if (fake(x)) return {out, mean, var};
+  c10::hip::HIPGuard g(x.device().index());
   if (no_rows(rows, {&mean, &var})) return {out, mean, var};
   bn_stats(x, rows, C, mean, var, op);
   check_rc(pn2_bn_act_fwd(F(x), rows, C, F(mean), F(var), F(gamma), F(beta),
@@ -851,11 +910,12 @@ std::tuple<Tensor, Tensor, Tensor> bn_train_grad_hip(const Tensor& grad_out_, co
   Tensor go = dev(grad_out_, "grad_out", at::kFloat), x = dev(x_, "x", at::kFloat);
   Tensor mean = dev(mean_, "mean", at::kFloat), var = dev(var_, "var", at::kFloat);
   Tensor gamma = dev(gamma_, "gamma", at::kFloat), beta = dev(beta_, "beta", at::kFloat);
-  c10::hip::HIPGuard g(x.device().index());
   const int C = I(x.size(-1));
   const int64_t rows = x.numel() / C;
   Tensor grad_x = at::empty(x.sizes(), f32(x));
   Tensor grad_gamma = at::empty({C}, f32(x)), grad_beta = at::empty({C}, f32(x));
+  if (fake(x)) return {grad_x, grad_gamma, grad_beta};
+  c10::hip::HIPGuard g(x.device().index());
   if (no_rows(rows, {&grad_gamma, &grad_beta})) return {grad_x, grad_gamma, grad_beta};
   bn_act_bwd(go, nullptr, x, rows, 1, C, mean, var, gamma, beta, eps, relu, grad_x, grad_gamma,
              grad_beta, op);
@@ -905,9 +965,9 @@ void chk_xent_grad(const Tensor& grad_loss, const Tensor& logits, const Tensor& 
 Tensor dropout_hip(const Tensor& x_, double keep_prob, int64_t seed) {
   chk_dropout(x_, keep_prob);
   Tensor x = dev(x_, "x", at::kFloat);
-  c10::hip::HIPGuard g(x.device().index());
   Tensor out = at::empty(x.sizes(), f32(x));
-  if (x.numel() == 0) return out;
+  if (fake(x) || x.numel() == 0) return out;
+  c10::hip::HIPGuard g(x.device().index());
   check_rc(pn2_dropout(F(x), x.numel(), static_cast<float>(keep_prob),
                        static_cast<uint64_t>(seed), out.data_ptr<float>(), stream_of(x)),
            "dropout");
@@ -922,14 +982,15 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> softmax_xent_hip(const Tensor& logits
   Tensor logits = dev(logits_, "logits", at::kFloat), labels = dev(labels_, "labels", at::kInt);
   Tensor weights;
   if (has(weights_)) weights = dev(*weights_, "weights", at::kFloat);
-  c10::hip::HIPGuard g(logits.device().index());
   const int C = I(logits.size(-1));
   const int64_t rows = labels.numel();
   Tensor lse = at::empty(labels.sizes(), f32(logits));
   Tensor pred = at::empty(labels.sizes(), i32(logits));
-  if (rows == 0)  // no rows: TF's safe division gives 0
-    return {at::zeros({}, f32(logits)), lse, pred, at::zeros({}, i32(logits))};
   Tensor loss = at::empty({}, f32(logits)), num_present = at::empty({}, i32(logits));
+  if (fake(logits)) return {loss, lse, pred, num_present};
+  c10::hip::HIPGuard g(logits.device().index());
+  if (rows == 0)  // no rows: TF's safe division gives 0
+    return {loss.zero_(), lse, pred, num_present.zero_()};
   const size_t ws = pn2_softmax_xent_workspace_size(rows);
   Tensor w = workspace(logits, ws);
   check_rc(pn2_softmax_xent_fwd(F(logits), Ii(labels), F(weights), rows, C, lse.data_ptr<float>(),
@@ -948,10 +1009,10 @@ Tensor softmax_xent_grad_hip(const Tensor& grad_loss_, const Tensor& logits_, co
   Tensor lse = dev(lse_, "lse", at::kFloat), np = dev(num_present_, "num_present", at::kInt);
   Tensor weights;
   if (has(weights_)) weights = dev(*weights_, "weights", at::kFloat);
-  c10::hip::HIPGuard g(logits.device().index());
   Tensor grad = at::empty(logits.sizes(), f32(logits));
   const int64_t rows = labels.numel();
-  if (rows == 0) return grad;
+  if (fake(logits) || rows == 0) return grad;
+  c10::hip::HIPGuard g(logits.device().index());
   check_rc(pn2_softmax_xent_bwd(F(gl), F(logits), Ii(labels), F(weights), F(lse), Ii(np), rows,
                                 I(logits.size(-1)), grad.data_ptr<float>(), stream_of(logits)), op);
   return grad;
@@ -1017,7 +1078,7 @@ void adam_step_hip(at::TensorList params, at::TensorList grads, at::TensorList e
                    at::TensorList exp_avg_sq, double alpha, double beta1, double beta2,
                    double epsilon) {
   chk_adam(params, grads, exp_avg, exp_avg_sq);
-  if (params.empty()) return;
+  if (params.empty() || fake(params[0])) return;  // (chk_adam: all on params[0]'s device)
   std::vector<pn2_adam_slot> slots(params.size());
   for (size_t i = 0; i < params.size(); ++i) {
     TORCH_CHECK(params[i].is_cuda(), "params[", i, "] is on ", params[i].device(),
@@ -1041,6 +1102,7 @@ void seg_confusion_hip(const Tensor& labels_, const Tensor& pred_, const Tensor&
                        const Tensor& counts) {
   chk_seg_confusion(labels_, pred_, confusion, counts);
   Tensor labels = dev(labels_, "labels", at::kInt), pred = dev(pred_, "pred", at::kInt);
+  if (fake(labels)) return;
   c10::hip::HIPGuard g(labels.device().index());
   check_rc(pn2_seg_confusion(Ii(labels), Ii(pred), labels.numel(), I(confusion.size(0)),
                              reinterpret_cast<long long*>(confusion.data_ptr<int64_t>()),
@@ -1052,10 +1114,11 @@ void seg_confusion_hip(const Tensor& labels_, const Tensor& pred_, const Tensor&
 
 std::tuple<Tensor, Tensor> mean_iou_hip(const Tensor& confusion) {
   const int64_t C = chk_confusion(confusion, "mean_iou");
-  TORCH_CHECK(confusion.is_cuda(), "confusion is on ", confusion.device(),
+  TORCH_CHECK(confusion.is_cuda() || fake(confusion), "confusion is on ", confusion.device(),
               ": pn2hip ops run on the MI355X only (no CPU fallback)");
-  c10::hip::HIPGuard g(confusion.device().index());
   Tensor iou = at::empty({}, f32(confusion)), per_class = at::empty({C}, f32(confusion));
+  if (fake(confusion)) return {iou, per_class};
+  c10::hip::HIPGuard g(confusion.device().index());
   check_rc(pn2_mean_iou(reinterpret_cast<const long long*>(confusion.data_ptr<int64_t>()), I(C),
                         iou.data_ptr<float>(), per_class.data_ptr<float>(), stream_of(confusion)),
            "mean_iou");
@@ -1134,8 +1197,8 @@ template <bool HIP>
 Tensor scene_vote_impl(const std::optional<Tensor>& logits_, const Tensor& mask_,
                        const Tensor& orig_, int64_t row0, const Tensor& keys) {
   chk_scene_vote(logits_, mask_, orig_, row0, keys);
-  TORCH_CHECK(HIP ? mask_.is_cuda() : mask_.device().is_cpu(), "scene_vote: mask is on ",
-              mask_.device());
+  TORCH_CHECK(HIP ? mask_.is_cuda() || fake(mask_) : mask_.device().is_cpu(),
+              "scene_vote: mask is on ", mask_.device());
   Tensor mask = mask_.contiguous(), orig = orig_.contiguous(), logits;
   int C = 0;
   if (logits_.has_value()) {
@@ -1143,6 +1206,7 @@ Tensor scene_vote_impl(const std::optional<Tensor>& logits_, const Tensor& mask_
     C = I(logits.size(-1));
   }
   Tensor pred = at::empty(mask.sizes(), i32(mask));
+  if (fake(mask)) return pred;
   const long long rows = mask.numel(), n = keys.size(0);
   if (HIP) {
     c10::hip::HIPGuard g(mask.device().index());
@@ -1163,8 +1227,8 @@ std::tuple<Tensor, Tensor, Tensor> scene_labels_impl(const Tensor& keys,
   const char* op = "scene_labels";
   chk_keys(keys, op);
   chk_i32_dflt(dflt, op);
-  TORCH_CHECK(HIP ? keys.is_cuda() : keys.device().is_cpu(), "scene_labels: keys is on ",
-              keys.device());
+  TORCH_CHECK(HIP ? keys.is_cuda() || fake(keys) : keys.device().is_cpu(),
+              "scene_labels: keys is on ", keys.device());
   Tensor lut;
   if (lut_.has_value()) {
     chk_lut(*lut_, keys, op);
@@ -1173,6 +1237,7 @@ std::tuple<Tensor, Tensor, Tensor> scene_labels_impl(const Tensor& keys,
   const long long n = keys.size(0);
   Tensor labels = at::empty({n}, i32(keys)), winner = at::empty({n}, keys.options());
   Tensor mapped = at::empty({lut.defined() ? n : 0}, i32(keys));
+  if (fake(keys)) return {labels, mapped, winner};
   const int32_t* lp = lut.defined() ? Ii(lut) : nullptr;
   const int nlut = lut.defined() ? I(lut.numel()) : 0;
   int32_t* mp = lut.defined() ? mapped.data_ptr<int32_t>() : nullptr;
@@ -1191,9 +1256,10 @@ template <bool HIP>
 void map_back_rows_impl(const Tensor& values_, int64_t row0, const Tensor& keys,
                         const Tensor& out) {
   const int64_t row = chk_map_back(values_, row0, keys, out);
-  TORCH_CHECK(HIP ? keys.is_cuda() : keys.device().is_cpu(), "map_back_rows: keys is on ",
-              keys.device());
+  TORCH_CHECK(HIP ? keys.is_cuda() || fake(keys) : keys.device().is_cpu(),
+              "map_back_rows: keys is on ", keys.device());
   Tensor values = values_.contiguous();
+  if (fake(keys)) return;
   const long long rows = values.size(0), n = keys.size(0);
   if (HIP) {
     c10::hip::HIPGuard g(keys.device().index());
@@ -1213,10 +1279,11 @@ Tensor label_lut_impl(const Tensor& inp_, const Tensor& lut_, int64_t dflt) {
                     inp_.scalar_type());
   chk_lut(lut_, inp_, op);
   chk_i32_dflt(dflt, op);
-  TORCH_CHECK(HIP ? inp_.is_cuda() : inp_.device().is_cpu(), "label_lut: inp is on ",
-              inp_.device());
+  TORCH_CHECK(HIP ? inp_.is_cuda() || fake(inp_) : inp_.device().is_cpu(),
+              "label_lut: inp is on ", inp_.device());
   Tensor inp = inp_.contiguous(), lut = lut_.contiguous();
   Tensor out = at::empty(inp.sizes(), i32(inp));
+  if (fake(inp)) return out;
   if (HIP) {
     c10::hip::HIPGuard g(inp.device().index());
     check_rc(pn2_label_lut(Ii(inp), inp.numel(), Ii(lut), I(lut.numel()),
@@ -1280,12 +1347,12 @@ Tensor group_concat_train_grad_hip(const Tensor& grad_, const Tensor& idx_, int6
   const char* op = "group_concat_train_grad";
   chk_group_concat_grad(grad_, idx_, N, C, col0);
   Tensor grad = dev(grad_, "grad_new_points", at::kFloat), idx = dev(idx_, "idx", at::kInt);
-  c10::hip::HIPGuard g(grad.device().index());
   const int B = I(idx.size(0)), M = I(idx.size(1)), ns = I(idx.size(2));
   TORCH_CHECK_VALUE(idx.size(1) * idx.size(2) <= PN2_INV_MAX_SLOTS && N <= PN2_INV_MAX_KEYS, op,
                     ": more slots or points per cloud than the inverse index takes");
   Tensor gp = at::empty({B, N, C}, f32(grad));
-  if (gp.numel() == 0) return gp;
+  if (fake(grad) || gp.numel() == 0) return gp;
+  c10::hip::HIPGuard g(grad.device().index());
   Tensor inv = inverse_index(idx, B, M * ns, I(N), op);
   check_rc(pn2_group_point_grad_ordered(F(grad), I(grad.size(3)), I(col0), P(inv), B, I(N), I(C),
                                         M, ns, gp.data_ptr<float>(), stream_of(grad)), op);
@@ -1299,10 +1366,11 @@ Tensor fp_apply_train_hip(const Tensor& dist_, const Tensor& idx_,
   Tensor points2 = dev(points2_, "points2", at::kFloat);
   Tensor points1;
   if (points1_.has_value() && points1_->numel() > 0) points1 = dev(*points1_, "points1", at::kFloat);
-  c10::hip::HIPGuard g(dist.device().index());
   const int B = I(dist.size(0)), n = I(dist.size(1)), m = I(points2.size(1));
   const int C2 = I(points2.size(2)), C1 = points1.defined() ? I(points1.size(2)) : 0;
   Tensor out = at::empty({B, n, C2 + C1}, f32(dist));
+  if (fake(dist)) return out;
+  c10::hip::HIPGuard g(dist.device().index());
   check_rc(pn2_fp_apply(F(dist), Ii(idx), nullptr, F(points1), C1, F(points2), C2, B, n, m,
                         out.data_ptr<float>(), stream_of(dist)), "fp_apply_train");
   return out;
@@ -1315,13 +1383,13 @@ std::tuple<Tensor, Tensor> fp_apply_train_grad_hip(const Tensor& grad_out_, cons
   chk_fp_apply_train_grad(grad_out_, dist_, idx_, m, C2, C1);
   Tensor grad = dev(grad_out_, "grad_out", at::kFloat), dist = dev(dist_, "dist", at::kFloat);
   Tensor idx = dev(idx_, "idx", at::kInt);
-  c10::hip::HIPGuard g(grad.device().index());
   const int B = I(dist.size(0)), n = I(dist.size(1));
   TORCH_CHECK_VALUE(3 * dist.size(1) <= PN2_INV_MAX_SLOTS && m <= PN2_INV_MAX_KEYS, op,
                     ": more unknown or known points per cloud than the inverse index takes");
   Tensor g1 = grad.narrow(2, C2, C1).contiguous();  // the points1 columns: one strided copy
   Tensor g2 = at::empty({B, m, C2}, f32(grad));
-  if (g2.numel() == 0) return {g2, g1};
+  if (fake(grad) || g2.numel() == 0) return {g2, g1};
+  c10::hip::HIPGuard g(grad.device().index());
   Tensor weight = at::empty_like(dist);  // the bits of pn2_idw_weights: the forward's weights
   if (n > 0) check_rc(pn2_idw_weights(F(dist), B, n, weight.data_ptr<float>(), stream_of(grad)), op);
   Tensor inv = inverse_index(idx, B, 3 * n, I(m), op);
@@ -1331,307 +1399,11 @@ std::tuple<Tensor, Tensor> fp_apply_train_grad_hip(const Tensor& grad_out_, cons
   return {g2, g1};
 }
 
-// ------------------------------------------------------------------------- CPU kernels
-// (the reference's CPU-only ops; host twins in csrc/cpu_interp.cpp)
-Tensor host(const Tensor& t, const char* name, at::ScalarType dt) {
-  TORCH_CHECK(t.device().is_cpu(), name, " must be a CPU tensor here");
-  TORCH_CHECK_TYPE(t.scalar_type() == dt, name, " must be ", dt, ", got ", t.scalar_type());
-  return t.contiguous();
-}
-std::tuple<Tensor, Tensor> three_nn_cpu(const Tensor& xyz1_, const Tensor& xyz2_) {
-  chk_nn(xyz1_, xyz2_);
-  Tensor xyz1 = host(xyz1_, "xyz1", at::kFloat), xyz2 = host(xyz2_, "xyz2", at::kFloat);
-  const int B = I(xyz1.size(0)), n = I(xyz1.size(1)), m = I(xyz2.size(1));
-  Tensor dist = at::empty({B, n, 3}, f32(xyz1));
-  Tensor idx = at::empty({B, n, 3}, i32(xyz1));
-  check_rc(pn2cpu_three_nn(F(xyz1), F(xyz2), B, n, m, dist.data_ptr<float>(),
-                           idx.data_ptr<int32_t>()), "ThreeNN");
-  return {dist, idx};
-}
-Tensor three_interpolate_cpu(const Tensor& points_, const Tensor& idx_, const Tensor& weight_) {
-  chk_interp(points_, idx_, weight_, "ThreeInterpolate");
-  Tensor points = host(points_, "points", at::kFloat), idx = host(idx_, "idx", at::kInt);
-  Tensor weight = host(weight_, "weight", at::kFloat);
-  const int B = I(points.size(0)), m = I(points.size(1)), C = I(points.size(2)), n = I(idx.size(1));
-  Tensor out = at::empty({B, n, C}, f32(points));
-  check_rc(pn2cpu_three_interpolate(F(points), Ii(idx), F(weight), B, m, C, n,
-                                    out.data_ptr<float>()), "ThreeInterpolate");
-  return out;
-}
-Tensor three_interpolate_grad_cpu(const Tensor& points, const Tensor& idx_, const Tensor& weight_,
-                                  const Tensor& grad_out_) {
-  chk_interp(points, idx_, weight_, "ThreeInterpolateGrad");
-  const int B = I(points.size(0)), m = I(points.size(1)), C = I(points.size(2)), n = I(idx_.size(1));
-  TORCH_CHECK_VALUE(grad_out_.dim() == 3 && grad_out_.size(0) == B && grad_out_.size(1) == n &&
-                        grad_out_.size(2) == C,  // tf_interpolate.cpp:243
-                    "ThreeInterpolateGrad expects (b,n,c) grad_out shape");
-  Tensor idx = host(idx_, "idx", at::kInt), weight = host(weight_, "weight", at::kFloat);
-  Tensor grad_out = host(grad_out_, "grad_out", at::kFloat);
-  Tensor gp = at::empty({B, m, C}, f32(grad_out));
-  check_rc(pn2cpu_three_interpolate_grad(F(grad_out), Ii(idx), F(weight), B, n, C, m,
-                                         gp.data_ptr<float>()), "ThreeInterpolateGrad");
-  return gp;
-}
-
-// ------------------------------------------------------------------------- Meta kernels
-at::TensorOptions mf(const Tensor& t) { return t.options().dtype(at::kFloat); }
-at::TensorOptions mi(const Tensor& t) { return t.options().dtype(at::kInt); }
-
-std::tuple<Tensor, Tensor> fps_and_gather_meta(int64_t npoint, const Tensor& inp) {
-  chk_fps(npoint, inp);
-  return {at::empty({inp.size(0), npoint}, mi(inp)), at::empty({inp.size(0), npoint, 3}, mf(inp))};
-}
-Tensor fps_meta(int64_t npoint, const Tensor& inp) {
-  chk_fps(npoint, inp);
-  return at::empty({inp.size(0), npoint}, mi(inp));
-}
-Tensor gather_point_meta(const Tensor& inp, const Tensor& idx) {
-  chk_gather(inp, idx, "GatherPoint");
-  return at::empty({inp.size(0), idx.size(1), 3}, mf(inp));
-}
-Tensor gather_point_grad_meta(const Tensor& inp, const Tensor& idx, const Tensor& out_g) {
-  chk_gather(inp, idx, "GatherPointGradGpuOp");
-  return at::empty({inp.size(0), inp.size(1), 3}, mf(out_g));
-}
-Tensor prob_sample_meta(const Tensor& inp, const Tensor& inpr) {
-  chk_prob(inp, inpr);
-  return at::empty({inp.size(0), inpr.size(1)}, mi(inp));
-}
-std::tuple<Tensor, Tensor> query_ball_point_meta(double radius, int64_t nsample, const Tensor& xyz1,
-                                                 const Tensor& xyz2) {
-  chk_ball(radius, nsample, xyz1, xyz2);
-  return {at::empty({xyz1.size(0), xyz2.size(1), nsample}, mi(xyz1)),
-          at::empty({xyz1.size(0), xyz2.size(1)}, mi(xyz1))};
-}
-std::tuple<Tensor, Tensor> select_top_k_meta(int64_t k, const Tensor& dist) {
-  TORCH_CHECK_VALUE(k > 0, "SelectionSort expects positive k");
-  TORCH_CHECK_VALUE(dist.dim() == 3, "SelectionSort expects (b,m,n) dist shape.");
-  return {at::empty(dist.sizes(), mi(dist)), at::empty(dist.sizes(), mf(dist))};
-}
-std::tuple<Tensor, Tensor> knn_point_meta(int64_t k, const Tensor& xyz1, const Tensor& xyz2) {
-  chk_knn(k, xyz1, xyz2);
-  return {at::empty({xyz1.size(0), xyz2.size(1), k}, mf(xyz1)),
-          at::empty({xyz1.size(0), xyz2.size(1), k}, mi(xyz1))};
-}
-Tensor group_point_meta(const Tensor& points, const Tensor& idx) {
-  chk_group(points, idx, "GroupPoint");
-  return at::empty({points.size(0), idx.size(1), idx.size(2), points.size(2)}, mf(points));
-}
-Tensor group_point_grad_meta(const Tensor& points, const Tensor& idx, const Tensor& grad_out) {
-  chk_group(points, idx, "GroupPointGrad");
-  return at::empty(points.sizes(), mf(grad_out));
-}
-std::tuple<Tensor, Tensor> group_concat_meta(const Tensor& xyz, const std::optional<Tensor>& points,
-                                             const Tensor& new_xyz, const Tensor& idx,
-                                             bool use_xyz, bool) {
-  chk_group_concat(xyz, points, new_xyz, idx);
-  const bool has = points.has_value() && points->numel() > 0;
-  const int64_t C = has ? points->size(2) : 0;
-  const int64_t cout = !has ? 3 : (use_xyz ? C + 3 : C);
-  return {at::empty({xyz.size(0), idx.size(1), idx.size(2), 3}, mf(xyz)),
-          at::empty({xyz.size(0), idx.size(1), idx.size(2), cout}, mf(xyz))};
-}
-std::tuple<Tensor, Tensor> three_nn_meta(const Tensor& xyz1, const Tensor& xyz2) {
-  chk_nn(xyz1, xyz2);
-  return {at::empty({xyz1.size(0), xyz1.size(1), 3}, mf(xyz1)),
-          at::empty({xyz1.size(0), xyz1.size(1), 3}, mi(xyz1))};
-}
-Tensor three_interpolate_meta(const Tensor& points, const Tensor& idx, const Tensor& weight) {
-  chk_interp(points, idx, weight, "ThreeInterpolate");
-  return at::empty({points.size(0), idx.size(1), points.size(2)}, mf(points));
-}
-Tensor three_interpolate_grad_meta(const Tensor& points, const Tensor& idx, const Tensor& weight,
-                                   const Tensor& grad_out) {
-  chk_interp(points, idx, weight, "ThreeInterpolateGrad");
-  return at::empty(points.sizes(), mf(grad_out));
-}
-Tensor idw_weights_meta(const Tensor& dist) {
-  TORCH_CHECK_VALUE(dist.dim() == 3 && dist.size(2) == 3, "idw_weights expects (b,n,3) dist shape");
-  return at::empty(dist.sizes(), mf(dist));
-}
-Tensor fp_fused_meta(const Tensor& xyz1, const Tensor& xyz2, const std::optional<Tensor>& points1,
-                     const Tensor& points2) {
-  chk_nn(xyz1, xyz2);
-  const int64_t C1 = (points1.has_value() && points1->numel() > 0) ? points1->size(2) : 0;
-  return at::empty({xyz1.size(0), xyz1.size(1), points2.size(2) + C1}, mf(xyz1));
-}
-Tensor attn_reduce_meta(const Tensor& Q, const Tensor& K, const Tensor& V) {
-  chk_attn(Q, K, V);
-  return at::empty(Q.sizes(), mf(Q));
-}
-std::tuple<Tensor, Tensor, Tensor> attn_reduce_grad_meta(const Tensor& Q, const Tensor& K,
-                                                         const Tensor& V, const Tensor&) {
-  chk_attn(Q, K, V);
-  return {at::empty(Q.sizes(), mf(Q)), at::empty(K.sizes(), mf(K)), at::empty(V.sizes(), mf(V))};
-}
-Tensor group_pool_meta(const Tensor& x, const std::optional<Tensor>& gxyz, int64_t mode) {
-  chk_group_pool(x, gxyz, mode);
-  return at::empty({x.size(0), x.size(1), mode == PN2_POOL_MAX_AND_AVG ? 2 * x.size(3) : x.size(3)},
-                   mf(x));
-}
-std::tuple<Tensor, Tensor, Tensor, Tensor> mlp_layer_train_meta(
-    const Tensor& x, const Tensor& weight, const std::optional<Tensor>& bias,
-    const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta, double, bool) {
-  chk_mlp_layer(x, weight, bias, gamma, beta, "mlp_layer_train");
-  const int64_t cout = weight.size(1), nstat = has(gamma) ? cout : 0;
-  return {at::empty(with_last(x, cout), mf(x)), at::empty(with_last(x, cout), mf(x)),
-          at::empty({nstat}, mf(x)), at::empty({nstat}, mf(x))};
-}
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_grad_meta(
-    const Tensor&, const Tensor& x, const Tensor& weight, const Tensor&,
-    const std::optional<Tensor>&, const std::optional<Tensor>&, const std::optional<Tensor>& gamma,
-    const std::optional<Tensor>& beta, double, bool, bool need_grad_x) {
-  chk_mlp_layer(x, weight, std::nullopt, gamma, beta, "mlp_layer_train_grad");
-  const int64_t cout = weight.size(1), nstat = has(gamma) ? cout : 0;
-  return {need_grad_x ? at::empty(x.sizes(), mf(x)) : at::empty({0}, mf(x)),
-          at::empty(weight.sizes(), mf(x)), at::empty({cout}, mf(x)), at::empty({nstat}, mf(x)),
-          at::empty({nstat}, mf(x))};
-}
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_pool_meta(
-    const Tensor& x, const Tensor& weight, const std::optional<Tensor>& bias,
-    const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta, double, bool) {
-  chk_mlp_pool(x, weight, bias, gamma, beta, "mlp_layer_train_pool");
-  const int64_t cout = weight.size(1), nstat = has(gamma) ? cout : 0;
-  return {at::empty(pooled_sizes(x, cout), mf(x)), at::empty(with_last(x, cout), mf(x)),
-          at::empty({nstat}, mf(x)), at::empty({nstat}, mf(x)),
-          at::empty(pooled_sizes(x, cout), mi(x))};
-}
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_pool_grad_meta(
-    const Tensor& grad_out, const Tensor& arg, const Tensor& x, const Tensor& weight,
-    const Tensor& y, const std::optional<Tensor>& mean, const std::optional<Tensor>& var,
-    const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta, double, bool,
-    bool need_grad_x) {
-  chk_mlp_pool_grad(grad_out, arg, x, weight, y, mean, var, gamma, beta,
-                    "mlp_layer_train_pool_grad");
-  const int64_t cout = weight.size(1), nstat = has(gamma) ? cout : 0;
-  return {need_grad_x ? at::empty(x.sizes(), mf(x)) : at::empty({0}, mf(x)),
-          at::empty(weight.sizes(), mf(x)), at::empty({cout}, mf(x)), at::empty({nstat}, mf(x)),
-          at::empty({nstat}, mf(x))};
-}
-
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> attn_kv_train_meta(
-    const Tensor& x, const Tensor& wq, const Tensor& bq, const Tensor& wk, const Tensor& bk,
-    const Tensor& wv, const Tensor& bv, bool add_max) {
-  chk_attn_kv(x, wq, wk, wv, "attn_kv_train");
-  chk_attn_kv_bias(x, bq, bk, bv, "attn_kv_train");
-  const int64_t C = x.size(-1);
-  const std::vector<int64_t> pooled = pooled_sizes(x, C);
-  return {at::empty(pooled, mf(x)),
-          add_max ? at::empty(pooled, mf(x)) : at::empty({0}, mf(x)),
-          add_max ? at::empty(pooled, mi(x)) : at::empty({0}, mi(x)),
-          at::empty(pooled, mf(x)), at::empty(with_last(x, 2 * C), mf(x))};
-}
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> attn_kv_train_grad_meta(
-    const Tensor& grad_att, const std::optional<Tensor>& grad_pmax, const Tensor& arg,
-    const Tensor& x, const Tensor& wq, const Tensor& wk, const Tensor& wv, const Tensor& q,
-    const Tensor& kv, bool need_grad_x) {
-  chk_attn_kv_grad(grad_att, grad_pmax, arg, x, wq, wk, wv, q, kv, "attn_kv_train_grad");
-  const int64_t C = x.size(-1);
-  return {need_grad_x ? at::empty(x.sizes(), mf(x)) : at::empty({0}, mf(x)),
-          at::empty({C, C}, mf(x)), at::empty({C}, mf(x)), at::empty({C, C}, mf(x)),
-          at::empty({C}, mf(x)), at::empty({C, C}, mf(x)), at::empty({C}, mf(x))};
-}
-std::tuple<Tensor, Tensor, Tensor> bn_train_meta(const Tensor& x, const Tensor& gamma,
-                                                 const Tensor& beta, double, bool) {
-  chk_bn(x, gamma, beta, "bn_train");
-  const int64_t C = x.size(-1);
-  return {at::empty(x.sizes(), mf(x)), at::empty({C}, mf(x)), at::empty({C}, mf(x))};
-}
-std::tuple<Tensor, Tensor, Tensor> bn_train_grad_meta(const Tensor& grad_out, const Tensor& x,
-                                                      const Tensor& mean, const Tensor& var,
-                                                      const Tensor& gamma, const Tensor& beta,
-                                                      double, bool) {
-  chk_bn(x, gamma, beta, "bn_train_grad");
-  TORCH_CHECK_VALUE(grad_out.sizes() == x.sizes(), "bn_train_grad expects grad_out shaped like x");
-  TORCH_CHECK_VALUE(mean.sizes() == gamma.sizes() && var.sizes() == gamma.sizes(),
-                    "bn_train_grad expects (C) mean and var");
-  const int64_t C = x.size(-1);
-  return {at::empty(x.sizes(), mf(x)), at::empty({C}, mf(x)), at::empty({C}, mf(x))};
-}
-
-Tensor dropout_meta(const Tensor& x, double keep_prob, int64_t) {
-  chk_dropout(x, keep_prob);
-  return at::empty(x.sizes(), mf(x));
-}
-std::tuple<Tensor, Tensor, Tensor, Tensor> softmax_xent_meta(const Tensor& logits,
-                                                             const Tensor& labels,
-                                                             const std::optional<Tensor>& weights) {
-  chk_xent(logits, labels, weights, "softmax_xent");
-  return {at::empty({}, mf(logits)), at::empty(labels.sizes(), mf(logits)),
-          at::empty(labels.sizes(), mi(logits)), at::empty({}, mi(logits))};
-}
-Tensor softmax_xent_grad_meta(const Tensor& grad_loss, const Tensor& logits, const Tensor& labels,
-                              const std::optional<Tensor>& weights, const Tensor& lse,
-                              const Tensor& num_present) {
-  chk_xent_grad(grad_loss, logits, labels, weights, lse, num_present, "softmax_xent_grad");
-  return at::empty(logits.sizes(), mf(logits));
-}
-void adam_step_meta(at::TensorList params, at::TensorList grads, at::TensorList exp_avg,
-                    at::TensorList exp_avg_sq, double, double, double, double) {
-  chk_adam(params, grads, exp_avg, exp_avg_sq);
-}
-void seg_confusion_meta(const Tensor& labels, const Tensor& pred, const Tensor& confusion,
-                        const Tensor& counts) {
-  chk_seg_confusion(labels, pred, confusion, counts);
-}
-std::tuple<Tensor, Tensor> mean_iou_meta(const Tensor& confusion) {
-  const int64_t C = chk_confusion(confusion, "mean_iou");
-  return {at::empty({}, mf(confusion)), at::empty({C}, mf(confusion))};
-}
-Tensor scene_vote_meta(const std::optional<Tensor>& logits, const Tensor& mask, const Tensor& orig,
-                       int64_t row0, const Tensor& keys) {
-  chk_scene_vote(logits, mask, orig, row0, keys);
-  return at::empty(mask.sizes(), mi(mask));
-}
-std::tuple<Tensor, Tensor, Tensor> scene_labels_meta(const Tensor& keys,
-                                                     const std::optional<Tensor>& lut,
-                                                     int64_t dflt) {
-  chk_keys(keys, "scene_labels");
-  chk_i32_dflt(dflt, "scene_labels");
-  if (lut.has_value()) chk_lut(*lut, keys, "scene_labels");
-  const int64_t n = keys.size(0);
-  return {at::empty({n}, mi(keys)), at::empty({lut.has_value() ? n : 0}, mi(keys)),
-          at::empty({n}, keys.options())};
-}
-void map_back_rows_meta(const Tensor& values, int64_t row0, const Tensor& keys, const Tensor& out) {
-  chk_map_back(values, row0, keys, out);
-}
-Tensor label_lut_meta(const Tensor& inp, const Tensor& lut, int64_t dflt) {
-  TORCH_CHECK_VALUE(inp.scalar_type() == at::kInt, "label_lut expects int32 inp, got ",
-                    inp.scalar_type());
-  chk_lut(lut, inp, "label_lut");
-  chk_i32_dflt(dflt, "label_lut");
-  return at::empty(inp.sizes(), mi(inp));
-}
-Tensor group_concat_train_meta(const Tensor& xyz, const std::optional<Tensor>& points,
-                               const Tensor& new_xyz, const Tensor& idx, bool use_xyz,
-                               bool xyz_last) {
-  return std::get<1>(group_concat_meta(xyz, points, new_xyz, idx, use_xyz, xyz_last));
-}
-Tensor group_concat_train_grad_meta(const Tensor& grad, const Tensor& idx, int64_t N, int64_t C,
-                                    int64_t col0) {
-  chk_group_concat_grad(grad, idx, N, C, col0);
-  return at::empty({idx.size(0), N, C}, mf(grad));
-}
-Tensor fp_apply_train_meta(const Tensor& dist, const Tensor& idx,
-                           const std::optional<Tensor>& points1, const Tensor& points2) {
-  chk_fp_apply_train(dist, idx, points1, points2);
-  const int64_t C1 = (points1.has_value() && points1->numel() > 0) ? points1->size(2) : 0;
-  return at::empty({dist.size(0), dist.size(1), points2.size(2) + C1}, mf(dist));
-}
-std::tuple<Tensor, Tensor> fp_apply_train_grad_meta(const Tensor& grad_out, const Tensor& dist,
-                                                    const Tensor& idx, int64_t m, int64_t C2,
-                                                    int64_t C1) {
-  chk_fp_apply_train_grad(grad_out, dist, idx, m, C2, C1);
-  return {at::empty({dist.size(0), m, C2}, mf(grad_out)),
-          at::empty({dist.size(0), dist.size(1), C1}, mf(grad_out))};
-}
-
 // ------------------------------------------------------------------------- autograd (C++)
 // The two ops of the training head carry their autograd here instead of in _torch_ops.py: the
 // head is bound by launches and host time, and a Python-registered backward
 // costs more host time per call than both kernels take on the device. Forward and backward go
-// back through the dispatcher, so the HIP and Meta kernels above serve both.
+// back through the dispatcher, so the bodies above serve both, on the device and under Meta.
 using torch::autograd::AutogradContext;
 using torch::autograd::variable_list;
 
@@ -1849,8 +1621,9 @@ TORCH_LIBRARY(pn2, m) {
   m.def("label_lut(Tensor inp, Tensor lut, int dflt) -> Tensor");
 }
 
-// ROCm builds of PyTorch dispatch HIP tensors under the CUDA key.
-TORCH_LIBRARY_IMPL(pn2, CUDA, m) {
+// Each op's one body, registered under CUDA (ROCm builds of PyTorch dispatch HIP tensors under
+// the CUDA key) and under Meta.
+static void register_bodies(torch::Library& m) {
   m.impl("farthest_point_sample", &fps_hip);
   m.impl("farthest_point_sample_and_gather", &fps_and_gather_hip);
   m.impl("gather_point", &gather_point_hip);
@@ -1862,9 +1635,9 @@ TORCH_LIBRARY_IMPL(pn2, CUDA, m) {
   m.impl("group_point", &group_point_hip);
   m.impl("group_point_grad", &group_point_grad_hip);
   m.impl("group_concat", &group_concat_hip);
-  m.impl("three_nn", &three_nn_hip);
-  m.impl("three_interpolate", &three_interpolate_hip);
-  m.impl("three_interpolate_grad", &three_interpolate_grad_hip);
+  m.impl("three_nn", &three_nn_impl<true>);
+  m.impl("three_interpolate", &three_interpolate_impl<true>);
+  m.impl("three_interpolate_grad", &three_interpolate_grad_impl<true>);
   m.impl("idw_weights", &idw_weights_hip);
   m.impl("fp_fused", &fp_fused_hip);
   m.impl("attn_reduce", &attn_reduce_hip);
@@ -1893,6 +1666,8 @@ TORCH_LIBRARY_IMPL(pn2, CUDA, m) {
   m.impl("map_back_rows", &map_back_rows_impl<true>);
   m.impl("label_lut", &label_lut_impl<true>);
 }
+TORCH_LIBRARY_IMPL(pn2, CUDA, m) { register_bodies(m); }
+TORCH_LIBRARY_IMPL(pn2, Meta, m) { register_bodies(m); }
 
 TORCH_LIBRARY_IMPL(pn2, Autograd, m) {
   m.impl("dropout", &dropout_autograd);
@@ -1902,56 +1677,12 @@ TORCH_LIBRARY_IMPL(pn2, Autograd, m) {
 }
 
 TORCH_LIBRARY_IMPL(pn2, CPU, m) {
-  m.impl("three_nn", &three_nn_cpu);
-  m.impl("three_interpolate", &three_interpolate_cpu);
-  m.impl("three_interpolate_grad", &three_interpolate_grad_cpu);
+  m.impl("three_nn", &three_nn_impl<false>);
+  m.impl("three_interpolate", &three_interpolate_impl<false>);
+  m.impl("three_interpolate_grad", &three_interpolate_grad_impl<false>);
   // the prediction ops' host twins (csrc/cpu_predict.cpp)
   m.impl("scene_vote", &scene_vote_impl<false>);
   m.impl("scene_labels", &scene_labels_impl<false>);
   m.impl("map_back_rows", &map_back_rows_impl<false>);
   m.impl("label_lut", &label_lut_impl<false>);
-}
-
-TORCH_LIBRARY_IMPL(pn2, Meta, m) {
-  m.impl("farthest_point_sample", &fps_meta);
-  m.impl("farthest_point_sample_and_gather", &fps_and_gather_meta);
-  m.impl("gather_point", &gather_point_meta);
-  m.impl("gather_point_grad", &gather_point_grad_meta);
-  m.impl("prob_sample", &prob_sample_meta);
-  m.impl("query_ball_point", &query_ball_point_meta);
-  m.impl("select_top_k", &select_top_k_meta);
-  m.impl("knn_point", &knn_point_meta);
-  m.impl("group_point", &group_point_meta);
-  m.impl("group_point_grad", &group_point_grad_meta);
-  m.impl("group_concat", &group_concat_meta);
-  m.impl("three_nn", &three_nn_meta);
-  m.impl("three_interpolate", &three_interpolate_meta);
-  m.impl("three_interpolate_grad", &three_interpolate_grad_meta);
-  m.impl("idw_weights", &idw_weights_meta);
-  m.impl("fp_fused", &fp_fused_meta);
-  m.impl("attn_reduce", &attn_reduce_meta);
-  m.impl("attn_reduce_grad", &attn_reduce_grad_meta);
-  m.impl("group_pool", &group_pool_meta);
-  m.impl("mlp_layer_train", &mlp_layer_train_meta);
-  m.impl("mlp_layer_train_grad", &mlp_layer_train_grad_meta);
-  m.impl("mlp_layer_train_pool", &mlp_layer_train_pool_meta);
-  m.impl("mlp_layer_train_pool_grad", &mlp_layer_train_pool_grad_meta);
-  m.impl("attn_kv_train", &attn_kv_train_meta);
-  m.impl("attn_kv_train_grad", &attn_kv_train_grad_meta);
-  m.impl("bn_train", &bn_train_meta);
-  m.impl("bn_train_grad", &bn_train_grad_meta);
-  m.impl("dropout", &dropout_meta);
-  m.impl("softmax_xent", &softmax_xent_meta);
-  m.impl("softmax_xent_grad", &softmax_xent_grad_meta);
-  m.impl("adam_step", &adam_step_meta);
-  m.impl("seg_confusion", &seg_confusion_meta);
-  m.impl("mean_iou", &mean_iou_meta);
-  m.impl("group_concat_train", &group_concat_train_meta);
-  m.impl("group_concat_train_grad", &group_concat_train_grad_meta);
-  m.impl("fp_apply_train", &fp_apply_train_meta);
-  m.impl("fp_apply_train_grad", &fp_apply_train_grad_meta);
-  m.impl("scene_vote", &scene_vote_meta);
-  m.impl("scene_labels", &scene_labels_meta);
-  m.impl("map_back_rows", &map_back_rows_meta);
-  m.impl("label_lut", &label_lut_meta);
 }

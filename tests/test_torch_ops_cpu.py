@@ -1,8 +1,9 @@
 """CPU: the torch.ops.pn2 operator library (csrc/torch_ops.cpp -> libpn2torch.so) loads, every
-schema is registered under the reference's names and argument order, the Meta kernels give the
-reference output shapes (fake tensors / torch.compile), the shape checks raise ValueError with
-the reference's OP_REQUIRES texts, and a CPU tensor is refused (no CPU fallback). No kernel
-runs here; tests/test_gpu_torch_ops.py runs them on the MI355X."""
+schema is registered under the reference's names and argument order, the ops under the Meta key
+give the reference output shapes (fake tensors / torch.compile), the shape checks raise ValueError
+with the reference's OP_REQUIRES texts, a Meta call raises what the device call would, and a CPU
+tensor is refused (no CPU fallback). No kernel runs here; tests/test_gpu_torch_ops.py runs them
+on the MI355X, and tests/test_gpu_meta_agrees.py compares Meta with the device op by op."""
 import pytest
 import torch
 
@@ -79,6 +80,65 @@ def test_reference_errors(ops, call, msg):
     with pytest.raises(ValueError) as e:
         call(ops, m)
     assert msg in str(e.value)
+
+
+def _inv_max_slots():
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, "include", "pn2hip.h")).read()
+    return 1 << int(re.search(r"#define PN2_INV_MAX_SLOTS \(1 << (\d+)\)", text).group(1))
+
+
+MAX_SLOTS = _inv_max_slots()
+_FP = lambda o, m, p1, p2: o.fp_fused(m(1, 10, 3), m(1, 4, 3), p1, p2)  # noqa: E731
+
+
+@pytest.mark.parametrize("call,exc,msg", [
+    (lambda o, m, i: o.select_top_k(5, m(1, 4, 3)), ValueError, "SelectionSort expects k <= n"),
+    (lambda o, m, i: o.gather_point_grad(m(1, 10, 3), i(1, 4), m(1, 5, 3)), ValueError,
+     "GatherPointGradGpuOp expects (batch_size,num_result,3) out_g shape"),
+    (lambda o, m, i: o.group_point_grad(m(1, 10, 6), i(1, 4, 8), m(1, 4, 8, 5)), ValueError,
+     "GroupPointGrad expects (batch_size, npoints, nsample, channel) grad_out shape"),
+    (lambda o, m, i: o.three_interpolate_grad(m(1, 4, 5), i(1, 10, 3), m(1, 10, 3), m(1, 10, 6)),
+     ValueError, "ThreeInterpolateGrad expects (b,n,c) grad_out shape"),
+    (lambda o, m, i: o.attn_reduce_grad(m(1, 4, 8), m(1, 4, 2, 8), m(1, 4, 2, 8), m(1, 4, 4)),
+     ValueError, "attn_reduce_grad expects grad_out shaped like Q"),
+    (lambda o, m, i: _FP(o, m, None, m(1, 5, 16)), ValueError, "fp_fused expects (b,m,c2) points2"),
+    (lambda o, m, i: _FP(o, m, m(1, 9, 5), m(1, 4, 16)), ValueError,
+     "fp_fused expects (b,n,c1) points1"),
+    (lambda o, m, i: o.mlp_layer_train_grad(m(10, 32), m(10, 9), m(9, 32), m(10, 31), None, None,
+                                            None, None, 1e-3, True, True),
+     ValueError, "mlp_layer_train_grad expects (..., cout) grad_out and y for (..., cin) x"),
+    # one slot past what the inverse index takes (Meta tensors cost no memory)
+    (lambda o, m, i: o.group_concat_train_grad(m(1, MAX_SLOTS + 1, 1, 4), i(1, MAX_SLOTS + 1, 1),
+                                               10, 4, 0),
+     ValueError, "group_concat_train_grad: more slots or points per cloud than the inverse index "
+                 "takes"),
+    (lambda o, m, i: o.fp_apply_train_grad(m(1, MAX_SLOTS // 3 + 1, 4), m(1, MAX_SLOTS // 3 + 1, 3),
+                                           i(1, MAX_SLOTS // 3 + 1, 3), 10, 4, 0),
+     ValueError, "fp_apply_train_grad: more unknown or known points per cloud than the inverse "
+                 "index takes"),
+    (lambda o, m, i: o.gather_point(m(1, 10, 3), m(1, 4)), TypeError, "idx must be Int"),
+])
+def test_meta_raises_what_the_device_call_raises(ops, call, exc, msg):
+    """One body serves CUDA and Meta (csrc/torch_ops.cpp), so every check of the device call,
+    the dtype checks included, is met under fake tensors too."""
+    m = lambda *s: torch.empty(s, device="meta")  # noqa: E731
+    i = lambda *s: torch.empty(s, device="meta", dtype=torch.int32)  # noqa: E731
+    with pytest.raises(exc) as e:
+        call(ops, m, i)
+    assert msg in str(e.value)
+
+
+def test_inverse_index_limit_is_the_first_refused(ops):
+    m = lambda *s: torch.empty(s, device="meta")  # noqa: E731
+    i = lambda *s: torch.empty(s, device="meta", dtype=torch.int32)  # noqa: E731
+    assert ops.group_concat_train_grad(m(1, MAX_SLOTS, 1, 4), i(1, MAX_SLOTS, 1), 10, 4,
+                                       0).shape == (1, 10, 4)
+    n = MAX_SLOTS // 3
+    g2, g1 = ops.fp_apply_train_grad(m(1, n, 4), m(1, n, 3), i(1, n, 3), 10, 4, 0)
+    assert g2.shape == (1, 10, 4) and g1.shape == (1, n, 0)
 
 
 def test_no_cpu_kernel(ops):
