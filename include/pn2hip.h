@@ -890,6 +890,79 @@ int pn2cpu_map_back_rows(const void* values, int row_bytes, long long row0, long
 int pn2cpu_label_lut(const int32_t* in, long long n, const int32_t* lut, int nlut, int32_t dflt,
                      int32_t* out);
 
+/* ---------------------------------------------------------------- training feed -------- */
+
+/* What stands between a stored crop and the training step (attention_points/train.py:74-109,
+ * scannet_dataset/data_transformation.py:270-352). csrc/feed.hip and csrc/scene.hip, with host
+ * twins in csrc/cpu_feed.cpp.
+ *
+ * get_data_tensors (train.py:94-108) and random_rotate (data_transformation.py:334-352) of a
+ * whole batch in one launch. Inputs: points (B,N,3), labels (B,N), colors (B,N,3) int32 or NULL,
+ * normals (B,N,3) or NULL, sample_weight (B,N) as stored, cs (B,2) = each cloud's (cos, sin) or
+ * NULL, class_weights (L). Outputs: xyz (B,N,3), features (B,N,F) with F = 3 use_color +
+ * 3 use_normal, colours first (NULL when F = 0), smpw (B,N).
+ *   rotation   x' = x c + y s, y' = y c - x s, z' = z: each product rounded, then the sum (the
+ *              row vector times [[c,-s,0],[s,c,0],[0,0,1]]); the points, and the normals when
+ *              use_normal. cs NULL: nothing is rotated, the coordinates are copied.
+ *   colour     (float)c / 255.0f, a correctly rounded fp32 division
+ *   smpw       (0 <= label < L ? class_weights[label] : 0) * (sample_weight != 0 ? 1 : 0):
+ *              -0.0 gives mask 0 and NaN mask 1, as tf.not_equal does
+ * Every access is one 4-byte element: any 4-byte aligned pointer is taken and the bits do not
+ * depend on it. PN2_EINVAL before any launch: B, N or L negative, a NULL points, labels,
+ * sample_weight, xyz or smpw, use_color without colors, use_normal without normals, F > 0
+ * without features, L > 0 without class_weights. B * N = 0 is a no-op. */
+int pn2_feed_batch(const float* points, const int32_t* labels, const int32_t* colors,
+                   const float* normals, const float* sample_weight, const float* cs,
+                   const float* class_weights, int L, int B, int N, int use_color,
+                   int use_normal, float* xyz, float* features, float* smpw,
+                   pn2_stream_t stream);
+/* The validation chunker get_all_subsets_for_scene_numpy (data_transformation.py:270-331),
+ * selection part: pn2_subvolume_select's kernels with the inner test's margin as a parameter
+ * (the reference masks with curmin - 0.001 .. curmax + 0.001 in float64, :309) and one count per
+ * column: counts (S), sel (S,N), inner (S,N). workspace: pn2_val_select_workspace_size(N, S)
+ * bytes. PN2_EINVAL: N or S negative, S * N > 2^31 - 1, S > 65535, a NULL buffer, a workspace
+ * too small. S = 0 is a no-op; N = 0 zeroes counts. */
+size_t pn2_val_select_workspace_size(int N, int S);
+int pn2_val_select(const float* points, int N, const double* bounds, int S, double margin,
+                   double inner_margin, void* workspace, size_t workspace_bytes, int32_t* counts,
+                   int32_t* sel, uint8_t* inner, pn2_stream_t stream);
+/* The validation chunker, draw and gather part (:311-325). For each column s with
+ * n = counts[s] > 0, draw r is choice[s*K + r] when choice (S,K) is given (clamped to
+ * [0, n - 1]; the caller's np.random.choice), else min(max((int)(u[s*K + r] * (float)n), 0),
+ * n - 1) (pn2_crop_sample's rule); point, label, colour and normal are gathered through sel,
+ * mask = inner, weight = (0 <= label < L ? label_weights[label] : 0) * mask. The chunk is kept
+ * unless (double)sum(mask) / (double)K < min_inside (:317, 0.01). Kept chunks are written
+ * compacted in column order into the outputs, which hold S chunks: out_points (S,K,3),
+ * out_labels (S,K), out_colors (S,K,3) (with colors, else NULL), out_normals likewise,
+ * out_weights (S,K); column (S) = the column of each kept chunk, -1 past them; kept (1) = their
+ * number. The chunks past `kept` are zeroed. Mask sums are integer adds and the slots come from
+ * one scan over the columns, so the outputs are the same bits in every run. workspace:
+ * pn2_val_chunks_workspace_size(S) bytes. PN2_EINVAL: N, S, K or L negative, S * N or S * K
+ * > 2^31 - 1, S > 65535, kept NULL, a NULL buffer that is needed, neither choice nor u with
+ * K > 0, a workspace too small. */
+size_t pn2_val_chunks_workspace_size(int S);
+int pn2_val_chunks(const float* points, const int32_t* labels, const int32_t* colors,
+                   const float* normals, int N, const int32_t* counts, const int32_t* sel,
+                   const uint8_t* inner, int S, const int32_t* choice, const float* u, int K,
+                   const float* label_weights, int L, double min_inside, void* workspace,
+                   size_t workspace_bytes, float* out_points, int32_t* out_labels,
+                   int32_t* out_colors, float* out_normals, float* out_weights, int32_t* column,
+                   int32_t* kept, pn2_stream_t stream);
+/* The same three functions on HOST pointers in plain C++, synchronous, without workspace:
+ * equal bits. */
+int pn2cpu_feed_batch(const float* points, const int32_t* labels, const int32_t* colors,
+                      const float* normals, const float* sample_weight, const float* cs,
+                      const float* class_weights, int L, int B, int N, int use_color,
+                      int use_normal, float* xyz, float* features, float* smpw);
+int pn2cpu_val_select(const float* points, int N, const double* bounds, int S, double margin,
+                      double inner_margin, int32_t* counts, int32_t* sel, uint8_t* inner);
+int pn2cpu_val_chunks(const float* points, const int32_t* labels, const int32_t* colors,
+                      const float* normals, int N, const int32_t* counts, const int32_t* sel,
+                      const uint8_t* inner, int S, const int32_t* choice, const float* u, int K,
+                      const float* label_weights, int L, double min_inside, float* out_points,
+                      int32_t* out_labels, int32_t* out_colors, float* out_normals,
+                      float* out_weights, int32_t* column, int32_t* kept);
+
 #ifdef __cplusplus
 }
 #endif

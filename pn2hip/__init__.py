@@ -30,7 +30,9 @@ _impl = importlib.import_module("pointcloud-segmentation-attention_amd")
 MODULES = ("tf_sampling", "tf_grouping", "tf_interpolate", "pointnet_util", "tf_util",
            "attention_layer", "data_transformation", "complete_scene_loader", "grid", "stack",
            "shard", "synth", "pointnet2_sem_seg", "pointnet2_sem_seg_features", "train",
-           "generate_predictions", "evaluate")
+           "generate_predictions", "evaluate", "pointnet2_sem_seg_attention",
+           "pointnet2_sem_seg_attention_and_pooling", "pointnet2_sem_seg_attention_single_layer",
+           "compute_class_weights")
 for _name in MODULES:
     _mod = getattr(_impl, _name)
     globals()[_name] = _mod
@@ -42,7 +44,7 @@ InvalidArgumentError = _impl.InvalidArgumentError
 Pn2RuntimeError = _impl.Pn2RuntimeError
 # the training loop's names (train.py): pn2hip.AdamOptimizer, pn2hip.train_step, ...
 TRAIN_NAMES = ("AdamOptimizer", "SegMetrics", "get_learning_rate", "get_bn_decay", "train_step",
-               "eval_step")
+               "eval_step", "train_step_with", "CLASS_WEIGHTS", "get_data_tensors", "eval_model")
 for _name in TRAIN_NAMES:
     globals()[_name] = getattr(_impl.train, _name)
 

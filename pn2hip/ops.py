@@ -88,6 +88,19 @@ four are listed in HOST_NAMES, not NAMES: next to the CUDA and Meta keys they ha
     scene_labels(keys, lut, dflt)                       -> (labels, mapped, winner)
     map_back_rows(values, row0, keys, out)              out[p] = values[winner(p) - row0]
     label_lut(inp, lut, dflt)                           0 <= inp < len(lut) ? lut[inp] : dflt
+
+and the training feed (csrc/feed.hip, pn2_val_select in csrc/scene.hip; attention_points/
+train.py:74-109, scannet_dataset/data_transformation.py:270-352), listed in FEED_NAMES: CUDA,
+Meta and CPU kernels too (host twins with equal bits, csrc/cpu_feed.cpp):
+
+    feed_batch(points, labels, colors, normals, sample_weight, cs, class_weights, use_color,
+               use_normal)                              get_data_tensors + random_rotate of a
+                         batch in one launch   -> (xyz, features, smpw)
+    val_select(points, bounds, margin, inner_margin)    the validation chunker's columns
+                                                         -> (counts, sel, inner)
+    val_chunks(points, labels, colors, normals, counts, sel, inner, choice, u, npoints,
+               label_weights, min_inside)               draws, keep test, compaction, gathers
+                         -> (points, labels, colors, normals, weights, column, kept)
 """
 import importlib
 
@@ -105,7 +118,8 @@ NAMES = ("farthest_point_sample", "farthest_point_sample_and_gather", "gather_po
 # the ops that also run on CPU tensors (every op in NAMES is device-only, three_nn and the two
 # three_interpolate ops excepted)
 HOST_NAMES = ("scene_vote", "scene_labels", "map_back_rows", "label_lut")
-for _n in NAMES + HOST_NAMES:
+FEED_NAMES = ("feed_batch", "val_select", "val_chunks")
+for _n in NAMES + HOST_NAMES + FEED_NAMES:
     globals()[_n] = getattr(_ops, _n)
 
-__all__ = list(NAMES + HOST_NAMES)
+__all__ = list(NAMES + HOST_NAMES + FEED_NAMES)

@@ -12,10 +12,16 @@ Drop-in modules (reference names, argument order, shapes, dtypes, error messages
   pointnet2_sem_seg      get_model, get_loss (the SSG segmentation model and its weighted loss)
   pointnet2_sem_seg_features  get_model(point_cloud, features, ...): the same model on points
                          that carry features
+  pointnet2_sem_seg_attention, pointnet2_sem_seg_attention_and_pooling,
+  pointnet2_sem_seg_attention_single_layer  the three attention models' get_model
   train                  get_learning_rate, get_bn_decay, AdamOptimizer, SegMetrics, train_step,
-                         eval_step (attention_points/train.py's optimiser, schedules, metrics
-                         and validation step)
-  data_transformation    get_subset (the ScanNet crop sampler) on the GPU, label_map
+                         eval_step, train_step_with, CLASS_WEIGHTS, get_data_tensors, eval_model, train
+                         (attention_points/train.py: optimiser, schedules, metrics, the batch
+                         feed, the validation pass and the epoch loop)
+  data_transformation    get_subset (the ScanNet crop sampler) on the GPU, label_map,
+                         random_rotate, get_all_subsets_for_scene_numpy / scene_val_chunks (the
+                         validation chunker)
+  compute_class_weights  weights_from_counts, get_weights
   generate_predictions   map_back, map_to_nyu40, export_ids, predict_scene, generate_predictions
                          (attention_points/benchmark: a label for every point of a scene)
   evaluate               evaluate_scan, get_iou, evaluate, write_result_file (the ScanNet
@@ -27,14 +33,21 @@ Everything runs the gfx950 kernels of libpn2hip.so (C ABI: include/pn2hip.h).
 The directory name has hyphens, so import it with importlib:
     pn2 = importlib.import_module("pointcloud-segmentation-attention_amd")
 """
-from . import attention_layer, complete_scene_loader, data_transformation, evaluate, generate_predictions, grid, \
-    plan, pointnet2_sem_seg, pointnet2_sem_seg_features, pointnet_util, shard, stack, synth, tf_grouping, \
-    tf_interpolate, tf_sampling, tf_util, train
+from . import attention_layer, complete_scene_loader, compute_class_weights, data_transformation, evaluate, \
+    generate_predictions, grid, plan, pointnet2_sem_seg, pointnet2_sem_seg_attention, \
+    pointnet2_sem_seg_attention_and_pooling, pointnet2_sem_seg_attention_single_layer, \
+    pointnet2_sem_seg_features, pointnet_util, shard, stack, synth, tf_grouping, tf_interpolate, tf_sampling, \
+    tf_util, train
+from .data_transformation import random_rotate, rotation_cs, scene_val_chunks
 from .generate_predictions import predict_scene
-from .train import AdamOptimizer, SegMetrics, eval_step, get_bn_decay, get_learning_rate, train_step
+from .train import (CLASS_WEIGHTS, AdamOptimizer, SegMetrics, eval_model, eval_step, get_bn_decay,
+                    get_data_tensors, get_learning_rate, train_step, train_step_with)
 from ._lib import LIB_PATH, InvalidArgumentError, Pn2RuntimeError, lib
 
 __all__ = ["tf_sampling", "tf_grouping", "tf_interpolate", "pointnet_util", "attention_layer", "grid", "tf_util", "data_transformation", "complete_scene_loader",
            "synth", "stack", "shard", "plan", "pointnet2_sem_seg", "pointnet2_sem_seg_features", "train",
            "generate_predictions", "evaluate", "predict_scene", "eval_step",
+           "pointnet2_sem_seg_attention", "pointnet2_sem_seg_attention_and_pooling",
+           "pointnet2_sem_seg_attention_single_layer", "compute_class_weights", "random_rotate", "rotation_cs",
+           "scene_val_chunks", "CLASS_WEIGHTS", "get_data_tensors", "eval_model", "train_step_with",
            "AdamOptimizer", "SegMetrics", "get_learning_rate", "get_bn_decay", "train_step", "lib", "LIB_PATH", "InvalidArgumentError", "Pn2RuntimeError"]

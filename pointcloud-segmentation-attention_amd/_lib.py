@@ -201,6 +201,17 @@ SIGNATURES = {
     "pn2cpu_scene_labels": (_I, [_P, _LL, _P, _I, ctypes.c_int32, _P, _P, _P]),
     "pn2cpu_map_back_rows": (_I, [_P, _I, _LL, _LL, _P, _LL, _P]),
     "pn2cpu_label_lut": (_I, [_P, _LL, _P, _I, ctypes.c_int32, _P]),
+    "pn2_feed_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "pn2_val_select_workspace_size": (_S, [_I, _I]),
+    "pn2_val_select": (_I, [_P, _I, _P, _I, ctypes.c_double, ctypes.c_double, _P, _S, _P, _P, _P,
+                            _P]),
+    "pn2_val_chunks_workspace_size": (_S, [_I]),
+    "pn2_val_chunks": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _I,
+                            ctypes.c_double, _P, _S, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pn2cpu_feed_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "pn2cpu_val_select": (_I, [_P, _I, _P, _I, ctypes.c_double, ctypes.c_double, _P, _P, _P]),
+    "pn2cpu_val_chunks": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _I,
+                               ctypes.c_double, _P, _P, _P, _P, _P, _P, _P]),
     # include/pn2plan.h: the native step executor
     "pn2_plan_create": (_P, []),
     "pn2_plan_destroy": (None, [_P]),

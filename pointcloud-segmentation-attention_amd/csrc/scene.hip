@@ -228,7 +228,7 @@ __global__ __launch_bounds__(kBlock) void subvol_count_kernel(const float* __res
 
 __global__ __launch_bounds__(kBlock) void subvol_compact_kernel(
     const float* __restrict__ p, int N, const double* __restrict__ bounds, double margin,
-    int nslices, const int32_t* __restrict__ cnt, int32_t* __restrict__ sel,
+    double inner_margin, int nslices, const int32_t* __restrict__ cnt, int32_t* __restrict__ sel,
     uint8_t* __restrict__ inner) {
   const int s = blockIdx.y, sl = blockIdx.x;
   double bd[6];
@@ -254,14 +254,27 @@ __global__ __launch_bounds__(kBlock) void subvol_compact_kernel(
     for (int k = 0; k < w; ++k) off += s_wave[k];
     if (in) {
       sel[(size_t)s * N + off + rank] = i;
-      // mask = (cur >= curmin) * (cur <= curmax), no margin (:40)
-      inner[(size_t)s * N + off + rank] = in_box_d(p + (size_t)i * 3, bd, 0.0) ? 1 : 0;
+      // mask = (cur >= curmin - inner_margin) * (cur <= curmax + inner_margin): no margin in
+      // the test-time chunker (:40; bd -+ 0.0 is bd), 0.001 in the validation chunker
+      // (data_transformation.py:309)
+      inner[(size_t)s * N + off + rank] = in_box_d(p + (size_t)i * 3, bd, inner_margin) ? 1 : 0;
     }
     int tot = 0;
     for (int k = 0; k < kBlock / kWave; ++k) tot += s_wave[k];
     base += tot;
     __syncthreads();
   }
+}
+
+// counts[s] = the sum of column s's slice counts (pn2_val_select)
+__global__ __launch_bounds__(kBlock) void subvol_total_kernel(const int32_t* __restrict__ cnt,
+                                                              int S, int nslices,
+                                                              int32_t* __restrict__ counts) {
+  const int s = blockIdx.x * kBlock + threadIdx.x;
+  if (s >= S) return;
+  int n = 0;
+  for (int k = 0; k < nslices; ++k) n += cnt[(size_t)s * nslices + k];
+  counts[s] = n;
 }
 
 // out[r] = src[idx[r]] for rows of row_bytes bytes (16-byte units when aligned).
@@ -361,7 +374,39 @@ int pn2_subvolume_select(const float* points, int N, const double* bounds, int S
   hipLaunchKernelGGL(pn2::subvol_count_kernel, dim3(ns, (unsigned)S), dim3(pn2::kBlock), 0, s,
                      points, N, bounds, margin, (int)ns, counts);
   hipLaunchKernelGGL(pn2::subvol_compact_kernel, dim3(ns, (unsigned)S), dim3(pn2::kBlock), 0, s,
-                     points, N, bounds, margin, (int)ns, counts, sel, inner);
+                     points, N, bounds, margin, 0.0, (int)ns, counts, sel, inner);
+  PN2_RETURN_LAUNCH();
+}
+
+size_t pn2_val_select_workspace_size(int N, int S) {
+  if (N <= 0 || S <= 0) return 0;
+  return (size_t)S * pn2::nslices_of(N) * sizeof(int32_t);
+}
+
+int pn2_val_select(const float* points, int N, const double* bounds, int S, double margin,
+                   double inner_margin, void* workspace, size_t workspace_bytes, int32_t* counts,
+                   int32_t* sel, uint8_t* inner, pn2_stream_t stream) {
+  if (N < 0 || S < 0) return PN2_EINVAL;
+  if ((long long)N * S > 0x7fffffffLL || S > 65535) return PN2_EINVAL;  // sel's index, grid.y
+  if (S == 0) return PN2_OK;
+  if (!counts) return PN2_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (N == 0) {  // no point: every column is empty
+    if (hipMemsetAsync(counts, 0, (size_t)S * sizeof(int32_t), s) != hipSuccess)
+      return (int)hipGetLastError();
+    return PN2_OK;
+  }
+  if (!points || !bounds || !sel || !inner || !workspace) return PN2_EINVAL;
+  if (workspace_bytes < pn2_val_select_workspace_size(N, S)) return PN2_EINVAL;
+  const unsigned ns = pn2::nslices_of(N);
+  int32_t* cnt = static_cast<int32_t*>(workspace);
+  hipLaunchKernelGGL(pn2::subvol_count_kernel, dim3(ns, (unsigned)S), dim3(pn2::kBlock), 0, s,
+                     points, N, bounds, margin, (int)ns, cnt);
+  hipLaunchKernelGGL(pn2::subvol_compact_kernel, dim3(ns, (unsigned)S), dim3(pn2::kBlock), 0, s,
+                     points, N, bounds, margin, inner_margin, (int)ns, cnt, sel, inner);
+  hipLaunchKernelGGL(pn2::subvol_total_kernel,
+                     dim3((unsigned)((S + pn2::kBlock - 1) / pn2::kBlock)), dim3(pn2::kBlock), 0, s,
+                     cnt, S, (int)ns, counts);
   PN2_RETURN_LAUNCH();
 }
 

@@ -23,8 +23,9 @@
 // ThreeInterpolate, ThreeInterpolateGrad: registered for DEVICE_CPU only,
 // tf_interpolate.cpp:187,222,262), through the host twins pn2cpu_* (csrc/cpu_interp.cpp);
 // and for the four prediction ops (scene_vote, scene_labels, map_back_rows, label_lut: integers
-// and copied bytes, host twins in csrc/cpu_predict.cpp with equal bits). Those seven bodies are
-// templates over HIP / CPU; every other op has no CPU kernel, so a CPU tensor fails in the
+// and copied bytes, host twins in csrc/cpu_predict.cpp with equal bits) and the three feed ops
+// (feed_batch, val_select, val_chunks: host twins in csrc/cpu_feed.cpp with equal bits). Those ten
+// bodies are templates over HIP / CPU; every other op has no CPU kernel, so a CPU tensor fails in the
 // dispatcher (no CPU fallback).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPGuard.h>
@@ -1295,6 +1296,196 @@ Tensor label_lut_impl(const Tensor& inp_, const Tensor& lut_, int64_t dflt) {
   return out;
 }
 
+// ---- the training feed (csrc/feed.hip, pn2_val_select in csrc/scene.hip): get_data_tensors and
+// random_rotate in one launch, and the validation chunker. CUDA, Meta and CPU (the host twins
+// of csrc/cpu_feed.cpp: equal bits) from one body each, as the prediction ops above.
+// an argument of the feed ops: on the body's device, of dtype dt, made contiguous
+Tensor feed_arg(const Tensor& t, const Tensor& like, at::ScalarType dt, const char* op,
+                const char* name) {
+  TORCH_CHECK_VALUE(t.scalar_type() == dt, op, " expects ", dt, " ", name, ", got ",
+                    t.scalar_type());
+  TORCH_CHECK_VALUE(t.device() == like.device(), op, " expects every tensor on one device");
+  return t.contiguous();
+}
+template <bool HIP>
+void feed_device(const Tensor& t, const char* op) {
+  TORCH_CHECK(HIP ? t.is_cuda() || fake(t) : t.device().is_cpu(), op, ": points is on ",
+              t.device());
+}
+
+template <bool HIP>
+std::tuple<Tensor, Tensor, Tensor> feed_batch_impl(
+    const Tensor& points_, const Tensor& labels_, const std::optional<Tensor>& colors_,
+    const std::optional<Tensor>& normals_, const Tensor& sample_weight_,
+    const std::optional<Tensor>& cs_, const Tensor& class_weights_, bool use_color,
+    bool use_normal) {
+  const char* op = "feed_batch";
+  TORCH_CHECK_VALUE(points_.dim() == 3 && points_.size(2) == 3, op,
+                    " expects (B,N,3) points, got ", points_.sizes());
+  const int64_t B = points_.size(0), N = points_.size(1);
+  TORCH_CHECK_VALUE(B <= INT32_MAX && N <= INT32_MAX, op, " expects B and N below 2^31");
+  feed_device<HIP>(points_, op);
+  Tensor points = feed_arg(points_, points_, at::kFloat, op, "points");
+  Tensor labels = feed_arg(labels_, points_, at::kInt, op, "labels");
+  Tensor sw = feed_arg(sample_weight_, points_, at::kFloat, op, "sample_weight");
+  Tensor cw = feed_arg(class_weights_, points_, at::kFloat, op, "class_weights");
+  TORCH_CHECK_VALUE(labels.dim() == 2 && labels.size(0) == B && labels.size(1) == N &&
+                        sw.sizes() == labels.sizes(),
+                    op, " expects (B,N) labels and sample_weight, got ", labels.sizes(), " and ",
+                    sw.sizes());
+  TORCH_CHECK_VALUE(cw.dim() == 1, op, " expects (L) class_weights, got ", cw.sizes());
+  Tensor colors, normals, cs;
+  if (use_color) {
+    TORCH_CHECK_VALUE(has(colors_), op, ": use_color needs colors");
+    colors = feed_arg(*colors_, points_, at::kInt, op, "colors");
+    TORCH_CHECK_VALUE(colors.sizes() == points.sizes(), op, " expects (B,N,3) colors, got ",
+                      colors.sizes());
+  }
+  if (use_normal) {
+    TORCH_CHECK_VALUE(has(normals_), op, ": use_normal needs normals");
+    normals = feed_arg(*normals_, points_, at::kFloat, op, "normals");
+    TORCH_CHECK_VALUE(normals.sizes() == points.sizes(), op, " expects (B,N,3) normals, got ",
+                      normals.sizes());
+  }
+  if (has(cs_)) {
+    cs = feed_arg(*cs_, points_, at::kFloat, op, "cs");
+    TORCH_CHECK_VALUE(cs.dim() == 2 && cs.size(0) == B && cs.size(1) == 2, op,
+                      " expects (B,2) cs, got ", cs.sizes());
+  }
+  const int64_t nf = (use_color ? 3 : 0) + (use_normal ? 3 : 0);
+  Tensor xyz = at::empty({B, N, 3}, f32(points)), features = at::empty({B, N, nf}, f32(points));
+  Tensor smpw = at::empty({B, N}, f32(points));
+  if (fake(points) || B * N == 0) return {xyz, features, smpw};
+  const int32_t* cp = colors.defined() ? Ii(colors) : nullptr;
+  float* fp = nf ? features.data_ptr<float>() : nullptr;
+  if (HIP) {
+    c10::hip::HIPGuard g(points.device().index());
+    check_rc(pn2_feed_batch(F(points), Ii(labels), cp, F(normals), F(sw), F(cs), F(cw),
+                            I(cw.numel()), I(B), I(N), use_color, use_normal,
+                            xyz.data_ptr<float>(), fp, smpw.data_ptr<float>(), stream_of(points)),
+             op);
+  } else {
+    check_rc(pn2cpu_feed_batch(F(points), Ii(labels), cp, F(normals), F(sw), F(cs), F(cw),
+                               I(cw.numel()), I(B), I(N), use_color, use_normal,
+                               xyz.data_ptr<float>(), fp, smpw.data_ptr<float>()), op);
+  }
+  return {xyz, features, smpw};
+}
+
+template <bool HIP>
+std::tuple<Tensor, Tensor, Tensor> val_select_impl(const Tensor& points_, const Tensor& bounds_,
+                                                   double margin, double inner_margin) {
+  const char* op = "val_select";
+  TORCH_CHECK_VALUE(points_.dim() == 2 && points_.size(1) == 3, op, " expects (N,3) points, got ",
+                    points_.sizes());
+  TORCH_CHECK_VALUE(bounds_.dim() == 2 && bounds_.size(1) == 6, op,
+                    " expects (S,6) float64 bounds, got ", bounds_.sizes());
+  feed_device<HIP>(points_, op);
+  Tensor points = feed_arg(points_, points_, at::kFloat, op, "points");
+  Tensor bounds = feed_arg(bounds_, points_, at::kDouble, op, "bounds");
+  const int64_t N = points.size(0), S = bounds.size(0);
+  TORCH_CHECK_VALUE(S <= 65535 && N * S <= INT32_MAX, op, " expects S <= 65535 and S * N <= 2^31 - 1, got S = ",
+                    S, ", N = ", N);
+  Tensor counts = at::empty({S}, i32(points)), sel = at::empty({S, N}, i32(points));
+  Tensor inner = at::empty({S, N}, points.options().dtype(at::kByte));
+  if (HIP) {
+    Tensor ws = at::empty({static_cast<int64_t>(pn2_val_select_workspace_size(I(N), I(S)) / 4)},
+                          i32(points));
+    if (fake(points) || S == 0) return {counts, sel, inner};
+    c10::hip::HIPGuard g(points.device().index());
+    check_rc(pn2_val_select(F(points), I(N), bounds.data_ptr<double>(), I(S), margin, inner_margin,
+                            ws.data_ptr(), ws.numel() * 4, counts.data_ptr<int32_t>(),
+                            sel.data_ptr<int32_t>(), inner.data_ptr<uint8_t>(),
+                            stream_of(points)), op);
+  } else {
+    if (S == 0) return {counts, sel, inner};
+    check_rc(pn2cpu_val_select(F(points), I(N), bounds.data_ptr<double>(), I(S), margin,
+                               inner_margin, counts.data_ptr<int32_t>(), sel.data_ptr<int32_t>(),
+                               inner.data_ptr<uint8_t>()), op);
+  }
+  return {counts, sel, inner};
+}
+
+using Tensor7 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
+template <bool HIP>
+Tensor7 val_chunks_impl(const Tensor& points_, const Tensor& labels_,
+                        const std::optional<Tensor>& colors_,
+                        const std::optional<Tensor>& normals_, const Tensor& counts_,
+                        const Tensor& sel_, const Tensor& inner_,
+                        const std::optional<Tensor>& choice_, const std::optional<Tensor>& u_,
+                        int64_t K, const Tensor& label_weights_, double min_inside) {
+  const char* op = "val_chunks";
+  TORCH_CHECK_VALUE(points_.dim() == 2 && points_.size(1) == 3, op, " expects (N,3) points, got ",
+                    points_.sizes());
+  TORCH_CHECK_VALUE(K >= 0 && K <= INT32_MAX, op, " expects 0 <= npoints < 2^31, got ", K);
+  feed_device<HIP>(points_, op);
+  Tensor points = feed_arg(points_, points_, at::kFloat, op, "points");
+  Tensor labels = feed_arg(labels_, points_, at::kInt, op, "labels");
+  Tensor counts = feed_arg(counts_, points_, at::kInt, op, "counts");
+  Tensor sel = feed_arg(sel_, points_, at::kInt, op, "sel");
+  Tensor inner = feed_arg(inner_, points_, at::kByte, op, "inner");
+  Tensor lw = feed_arg(label_weights_, points_, at::kFloat, op, "label_weights");
+  const int64_t N = points.size(0), S = counts.numel();
+  TORCH_CHECK_VALUE(labels.dim() == 1 && labels.size(0) == N, op, " expects (N) labels, got ",
+                    labels.sizes());
+  TORCH_CHECK_VALUE(counts.dim() == 1 && sel.dim() == 2 && sel.size(0) == S && sel.size(1) == N &&
+                        inner.sizes() == sel.sizes(),
+                    op, " expects counts (S), sel (S,N) and inner (S,N), got ", counts.sizes(), ", ",
+                    sel.sizes(), " and ", inner.sizes());
+  TORCH_CHECK_VALUE(lw.dim() == 1, op, " expects (L) label_weights, got ", lw.sizes());
+  TORCH_CHECK_VALUE(S <= 65535 && N * S <= INT32_MAX && K * S <= INT32_MAX, op,
+                    " expects S <= 65535, S * N <= 2^31 - 1 and S * npoints <= 2^31 - 1");
+  Tensor colors, normals, choice, u;
+  if (has(colors_)) {
+    colors = feed_arg(*colors_, points_, at::kInt, op, "colors");
+    TORCH_CHECK_VALUE(colors.sizes() == points.sizes(), op, " expects (N,3) colors, got ",
+                      colors.sizes());
+  }
+  if (has(normals_)) {
+    normals = feed_arg(*normals_, points_, at::kFloat, op, "normals");
+    TORCH_CHECK_VALUE(normals.sizes() == points.sizes(), op, " expects (N,3) normals, got ",
+                      normals.sizes());
+  }
+  if (has(choice_)) {
+    choice = feed_arg(*choice_, points_, at::kInt, op, "choice");
+    TORCH_CHECK_VALUE(choice.dim() == 2 && choice.size(0) == S && choice.size(1) == K, op,
+                      " expects (S,npoints) choice, got ", choice.sizes());
+  } else {
+    TORCH_CHECK_VALUE(has(u_), op, " expects choice or u");
+    u = feed_arg(*u_, points_, at::kFloat, op, "u");
+    TORCH_CHECK_VALUE(u.dim() == 2 && u.size(0) == S && u.size(1) == K, op,
+                      " expects (S,npoints) u, got ", u.sizes());
+  }
+  Tensor op_ = at::empty({S, K, 3}, f32(points)), ol = at::empty({S, K}, i32(points));
+  Tensor oc = colors.defined() ? at::empty({S, K, 3}, i32(points)) : at::empty({0}, i32(points));
+  Tensor on = normals.defined() ? at::empty({S, K, 3}, f32(points)) : at::empty({0}, f32(points));
+  Tensor ow = at::empty({S, K}, f32(points)), column = at::empty({S}, i32(points));
+  Tensor kept = at::empty({1}, i32(points));
+  if (fake(points)) return {op_, ol, oc, on, ow, column, kept};
+  const int32_t* cp = colors.defined() ? Ii(colors) : nullptr;
+  const int32_t* chp = choice.defined() ? Ii(choice) : nullptr;
+  int32_t* ocp = colors.defined() ? oc.data_ptr<int32_t>() : nullptr;
+  float* onp = normals.defined() ? on.data_ptr<float>() : nullptr;
+  if (HIP) {
+    Tensor ws = at::empty({static_cast<int64_t>(pn2_val_chunks_workspace_size(I(S)) / 4)},
+                          i32(points));
+    c10::hip::HIPGuard g(points.device().index());
+    check_rc(pn2_val_chunks(F(points), Ii(labels), cp, F(normals), I(N), Ii(counts), Ii(sel),
+                            inner.data_ptr<uint8_t>(), I(S), chp, F(u), I(K), F(lw),
+                            I(lw.numel()), min_inside, ws.data_ptr(), ws.numel() * 4,
+                            op_.data_ptr<float>(), ol.data_ptr<int32_t>(), ocp, onp,
+                            ow.data_ptr<float>(), column.data_ptr<int32_t>(),
+                            kept.data_ptr<int32_t>(), stream_of(points)), op);
+  } else {
+    check_rc(pn2cpu_val_chunks(F(points), Ii(labels), cp, F(normals), I(N), Ii(counts), Ii(sel),
+                               inner.data_ptr<uint8_t>(), I(S), chp, F(u), I(K), F(lw),
+                               I(lw.numel()), min_inside, op_.data_ptr<float>(),
+                               ol.data_ptr<int32_t>(), ocp, onp, ow.data_ptr<float>(),
+                               column.data_ptr<int32_t>(), kept.data_ptr<int32_t>()), op);
+  }
+  return {op_, ol, oc, on, ow, column, kept};
+}
+
 // ---- training-mode geometry (csrc/geom_train.hip): the fused forward kernels of the SA and FP
 // modules with their gradients as ordered gathers (no float atomics, no zero fill, no slices)
 void chk_group_concat_grad(const Tensor& grad, const Tensor& idx, int64_t N, int64_t C,
@@ -1619,6 +1810,15 @@ TORCH_LIBRARY(pn2, m) {
         "(Tensor labels, Tensor mapped, Tensor winner)");
   m.def("map_back_rows(Tensor values, int row0, Tensor keys, Tensor(a!) out) -> ()");
   m.def("label_lut(Tensor inp, Tensor lut, int dflt) -> Tensor");
+  m.def("feed_batch(Tensor points, Tensor labels, Tensor? colors, Tensor? normals, "
+        "Tensor sample_weight, Tensor? cs, Tensor class_weights, bool use_color, bool use_normal) "
+        "-> (Tensor xyz, Tensor features, Tensor smpw)");
+  m.def("val_select(Tensor points, Tensor bounds, float margin, float inner_margin) -> "
+        "(Tensor counts, Tensor sel, Tensor inner)");
+  m.def("val_chunks(Tensor points, Tensor labels, Tensor? colors, Tensor? normals, Tensor counts, "
+        "Tensor sel, Tensor inner, Tensor? choice, Tensor? u, int npoints, Tensor label_weights, "
+        "float min_inside) -> (Tensor points, Tensor labels, Tensor colors, Tensor normals, "
+        "Tensor weights, Tensor column, Tensor kept)");
 }
 
 // Each op's one body, registered under CUDA (ROCm builds of PyTorch dispatch HIP tensors under
@@ -1665,6 +1865,9 @@ static void register_bodies(torch::Library& m) {
   m.impl("scene_labels", &scene_labels_impl<true>);
   m.impl("map_back_rows", &map_back_rows_impl<true>);
   m.impl("label_lut", &label_lut_impl<true>);
+  m.impl("feed_batch", &feed_batch_impl<true>);
+  m.impl("val_select", &val_select_impl<true>);
+  m.impl("val_chunks", &val_chunks_impl<true>);
 }
 TORCH_LIBRARY_IMPL(pn2, CUDA, m) { register_bodies(m); }
 TORCH_LIBRARY_IMPL(pn2, Meta, m) { register_bodies(m); }
@@ -1685,4 +1888,8 @@ TORCH_LIBRARY_IMPL(pn2, CPU, m) {
   m.impl("scene_labels", &scene_labels_impl<false>);
   m.impl("map_back_rows", &map_back_rows_impl<false>);
   m.impl("label_lut", &label_lut_impl<false>);
+  // the training feed's host twins (csrc/cpu_feed.cpp)
+  m.impl("feed_batch", &feed_batch_impl<false>);
+  m.impl("val_select", &val_select_impl<false>);
+  m.impl("val_chunks", &val_chunks_impl<false>);
 }

@@ -23,16 +23,23 @@ FP_LAYERS = (("fa_layer1", [256, 256]), ("fa_layer2", [256, 256]), ("fa_layer3",
 
 
 def model_body(point_cloud, l0_points, is_training, num_class, bn_decay=None, params=None,
-               seed=None):
+               seed=None, sa_modules=None):
     """The layers of get_model, shared with pointnet2_sem_seg_features.get_model: l0_points is
     None here and the per-point features (B, N, C) there (attention_points/models/
     pointnet2_sem_seg_features.py:25). `seed`: the dropout seed (tf_util.dropout), None to draw
-    one from torch's CPU generator."""
+    one from torch's CPU generator. `sa_modules`: the set-abstraction module of each of the four
+    layers, callables with pointnet_sa_module's signature (the attention models pass
+    attention_layer.pointnet_sa_module_attention / _and_pooling); None: pointnet_sa_module
+    everywhere."""
     store = params if params is not None else tf_util.default_store()
     end_points = {"l0_xyz": point_cloud}
     xyz, points = [point_cloud], [l0_points]
-    for scope, npoint, radius, nsample, mlp in SA_LAYERS:
-        new_xyz, new_points, _ = pointnet_sa_module(
+    if sa_modules is None:
+        sa_modules = (pointnet_sa_module,) * len(SA_LAYERS)
+    if len(sa_modules) != len(SA_LAYERS):
+        raise ValueError(f"model_body expects {len(SA_LAYERS)} sa_modules, got {len(sa_modules)}")
+    for sa_module, (scope, npoint, radius, nsample, mlp) in zip(sa_modules, SA_LAYERS):
+        new_xyz, new_points, _ = sa_module(
             xyz[-1], points[-1], npoint, radius, nsample, mlp, None, False, is_training, bn_decay,
             scope, params=store)
         xyz.append(new_xyz)

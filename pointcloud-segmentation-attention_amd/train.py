@@ -6,9 +6,14 @@ model, on the gfx950 kernels of csrc/optim.hip.
                                       variable in ceil(n / 64) launches (torch.ops.pn2.adam_step)
     SegMetrics                        get_metrics (:145-163): the accuracy over the annotated
                                       points and the streaming tf.metrics.mean_iou
-    train_step                        one step: forward, weighted loss, backward, Adam, metrics
+    train_step, train_step_with       one step: forward, weighted loss, backward, Adam, metrics
+                                      (train_step_with takes the model: the attention models)
     eval_step                         one validation batch (eval_model, :221-285): the inference
                                       path, the same loss and metrics, nothing updated
+    CLASS_WEIGHTS, get_data_tensors   a stored batch as model inputs (:74-109) in one launch
+                                      (torch.ops.pn2.feed_batch, csrc/feed.hip)
+    choose_model, eval_model, train   the model choice (:291-293, :323-330), the validation pass
+                                      (:221-285) and the epoch loop (:288-387)
 
 A loop written against this module never reads the device back inside a step:
 
@@ -21,17 +26,20 @@ A loop written against this module never reads the device back inside a step:
     mean_iou, per_class = metrics.iou()
 """
 import math
+import os
 
 import numpy as np
 import torch
 
-from . import _torch_ops
+from . import _torch_ops, pointnet2_sem_seg_attention, pointnet2_sem_seg_attention_single_layer
+from .data_transformation import LABEL_WEIGHTS
 from .pointnet2_sem_seg import model_body
 from .tf_util import ParamStore
 
 BATCH_SIZE = 16         # train.py:17
 N_TRAIN_SAMPLES = 1201  # train.py:15, the number of train scenes
 DECAY_EPOCHS = 80       # train.py:37, :54: decay_steps = N_TRAIN_SAMPLES * 80
+CLASS_WEIGHTS = list(LABEL_WEIGHTS)  # train.py:20-24, the table of data_transformation.py:82-86
 
 
 def _staircase(batch, batch_size, n_train_samples):
@@ -203,16 +211,17 @@ class SegMetrics:
         self.confusion.zero_()
 
 
-def train_step(store, opt, metrics, point_cloud, labels, smpw, num_class, bn_decay=None,
-               learning_rate=None, features=None, seed=None):
-    """One training step of train.py's loop on a trainable store: zero_grad, the model with
-    is_training=True (pointnet2_sem_seg, or pointnet2_sem_seg_features when `features` (B, N, C)
-    is given), the weighted loss, backward, opt.step(learning_rate), metrics.update with the
-    loss kernel's own argmax (no second pass over the logits). `seed`: the dropout seed, so a
-    step is reproducible. Returns (loss, counts), device tensors: nothing here reads the device
-    back."""
+def train_step_with(model, store, opt, metrics, point_cloud, labels, smpw, num_class,
+                    bn_decay=None, learning_rate=None, features=None, seed=None):
+    """One training step of train.py's loop on a trainable store with `model`, a callable with
+    pointnet2_sem_seg.model_body's signature (the attention models' `body`; None: model_body
+    itself): zero_grad, the model with is_training=True, the weighted loss, backward,
+    opt.step(learning_rate), metrics.update with the loss kernel's own argmax (no second pass
+    over the logits). `seed`: the dropout seed, so a step is reproducible. Returns (loss,
+    counts), device tensors: nothing here reads the device back."""
     opt.zero_grad()
-    logits, _ = model_body(point_cloud, features, True, num_class, bn_decay, store, seed=seed)
+    body = model_body if model is None else model
+    logits, _ = body(point_cloud, features, True, num_class, bn_decay, store, seed=seed)
     if labels.dtype in (torch.int64, torch.int16, torch.uint8, torch.int8):
         labels = labels.to(torch.int32)
     loss, _, pred, _ = _torch_ops.call("softmax_xent", logits, labels, smpw)
@@ -222,16 +231,183 @@ def train_step(store, opt, metrics, point_cloud, labels, smpw, num_class, bn_dec
     return loss.detach(), counts
 
 
+def train_step(store, opt, metrics, point_cloud, labels, smpw, num_class, bn_decay=None,
+               learning_rate=None, features=None, seed=None):
+    """train_step_with on pointnet2_sem_seg.model_body: pointnet2_sem_seg, or
+    pointnet2_sem_seg_features when `features` (B, N, C) is given. Its parameter list is kept as
+    it was; the attention models train through train_step_with(model, ...)."""
+    return train_step_with(None, store, opt, metrics, point_cloud, labels, smpw, num_class,
+                           bn_decay, learning_rate, features, seed)
+
+
 @torch.no_grad()
-def eval_step(store, metrics, point_cloud, labels, smpw, num_class, features=None):
+def eval_step(store, metrics, point_cloud, labels, smpw, num_class, features=None, model=None):
     """One batch of train.py's validation pass (eval_model, :221-285): train_step without
     zero_grad, backward and the optimiser, with is_training=False, so the model runs its inference
     path on the moving statistics and no variable of the store changes. The weighted loss and the
-    metrics are train_step's: softmax_xent's loss and argmax, metrics.update. Returns (loss,
-    counts), device tensors: nothing here reads the device back."""
-    logits, _ = model_body(point_cloud, features, False, num_class, None, store)
+    metrics are train_step's: softmax_xent's loss and argmax, metrics.update. `model`: as in
+    train_step. Returns (loss, counts), device tensors: nothing here reads the device back."""
+    body = model_body if model is None else model
+    logits, _ = body(point_cloud, features, False, num_class, None, store)
     if labels.dtype in (torch.int64, torch.int16, torch.uint8, torch.int8):
         labels = labels.to(torch.int32)
     loss, _, pred, _ = _torch_ops.call("softmax_xent", logits, labels, smpw)
     counts = metrics.update(labels, pred)
     return loss, counts
+
+
+def get_data_tensors(batch, color=True, normal=True, device="cuda"):
+    """train.py:74-109 for one stored batch = (points (B,N,3) float32, labels (B,N), colors
+    (B,N,3) integers, normals (B,N,3) float32, sample_weight (B,N)), numpy or tensors:
+    colors / 255, features = colors ++ normals (either alone, or None), and sample_weight =
+    CLASS_WEIGHTS[labels] * (stored weight != 0), in ONE launch (torch.ops.pn2.feed_batch;
+    csrc/feed.hip) instead of eight. Returns (xyz, labels int32, features or None, smpw) on
+    `device`."""
+    dev = torch.device(device)
+
+    def conv(a, dtype):
+        if a is None:
+            return None
+        t = torch.as_tensor(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+        return t.to(device=dev, dtype=dtype)
+    points, labels, colors, normals, weight = batch
+    points, labels = conv(points, torch.float32), conv(labels, torch.int32)
+    colors = conv(colors, torch.int32) if color else None
+    normals = conv(normals, torch.float32) if normal else None
+    cw = torch.tensor(CLASS_WEIGHTS, dtype=torch.float32, device=dev)
+    xyz, feats, smpw = _torch_ops.call("feed_batch", points, labels, colors, normals,
+                                       conv(weight, torch.float32), None, cw, bool(color),
+                                       bool(normal))
+    return xyz, labels.contiguous(), feats if (color or normal) else None, smpw
+
+
+def choose_model(use_color=True, use_normal=True, use_attention=False, attention_single_layer=-1):
+    """The reference's model choice with its three asserts (:291-293, :323-330) as a callable
+    with model_body's signature: features -> pointnet2_sem_seg_features, use_attention ->
+    pointnet2_sem_seg_attention, attention_single_layer != -1 ->
+    pointnet2_sem_seg_attention_single_layer, else pointnet2_sem_seg."""
+    assert use_color != use_attention, \
+        "Attention not supported in combination with the usage of color features"
+    assert use_normal != use_attention, \
+        "Attention not supported in combination with the usage of color features"
+    assert attention_single_layer == -1 or not use_attention, \
+        "Either attention on all or a single layer"
+    if use_normal or use_color:
+        return model_body
+    if use_attention:
+        return pointnet2_sem_seg_attention.body
+    if attention_single_layer != -1:
+        return pointnet2_sem_seg_attention_single_layer.body(attention_single_layer)
+    return model_body
+
+
+def _mean(xs):
+    """The mean of a list of 0-d device tensors as a float: one read."""
+    return float(torch.stack([x.detach().to(torch.float64) for x in xs]).mean()) if xs else \
+        float("nan")
+
+
+def _accuracies(counts):
+    """Per-batch correct / assigned (NaN for 0 / 0, as TensorFlow) of a list of counts: one
+    read."""
+    c = torch.stack(counts).to(torch.float64)
+    return c[:, 0] / c[:, 1]
+
+
+def eval_model(store, metrics, val_batches, use_color=True, use_normal=True, num_class=21,
+               model=None, eval_fn=eval_step, device="cuda"):
+    """eval_model (:221-285): one pass over `val_batches` (stored batches, get_data_tensors'
+    input) with eval_fn, then (mean loss, mean accuracy, IoU) as floats: the means over the
+    batches (:265-266) and the streaming mean IoU after the last one (:267). `metrics` is reset
+    afterwards (:279). Nothing is read back before the last batch has been enqueued.
+    Validation is weighted with its own sample weights; the reference passes the TRAINING
+    batch's weights to the validation loss (:344), which is not copied."""
+    losses, counts = [], []
+    for batch in val_batches:
+        xyz, labels, feats, smpw = get_data_tensors(batch, use_color, use_normal, device)
+        loss, cnt = eval_fn(store, metrics, xyz, labels, smpw, num_class, features=feats,
+                            model=model)
+        losses.append(loss)
+        counts.append(cnt)
+    iou = float(metrics.iou()[0]) if losses else float("nan")
+    acc = float(_accuracies(counts).mean()) if counts else float("nan")
+    metrics.reset()
+    return _mean(losses), acc, iou
+
+
+def train(store, train_batches, val_batches=None, epochs=1000, batch_size=BATCH_SIZE,
+          n_train_samples=N_TRAIN_SAMPLES, use_color=True, use_normal=True, use_attention=False,
+          attention_single_layer=-1, n_epochs_to_val=4, save_dir=None, step_fn=None,
+          eval_fn=eval_step, num_class=21, device="cuda", optimizer=None, seed=None,
+          metrics=None, val_metrics=None):
+    """The reference's training loop (:288-387) on a trainable store.
+
+    train_batches: an iterable of stored batches (get_data_tensors' input), re-started when it
+    runs out (the reference's dataset repeats); val_batches: a sequence of stored batches, walked
+    once per validation. Model choice and asserts: choose_model. step_fn: called with
+    train_step's arguments and model=<the chosen model>; None is train_step_with on that model.
+    eval_fn: eval_step's arguments, model= included. Epoch arithmetic as the
+    reference: batches_per_epoch = n_train_samples / batch_size (a float), int(epochs *
+    batches_per_epoch) steps, step i belongs to epoch int((i + 1) / batches_per_epoch) + 1 and an
+    epoch ends when (i + 1) % int(batches_per_epoch) == 0 (:358-377). Learning rate and batch-norm
+    decay follow the optimiser's step count (:319-321). At an epoch's end the mean loss and mean
+    accuracy (sums over batches_per_epoch, :209-210) and the streaming IoU are summarised and the
+    train metrics reset; every n_epochs_to_val epochs eval_model runs, and when the validation
+    IoU improves on the best so far (0 at the start) the store's and the optimiser's exports go
+    to save_dir/best_model_epoch_%03d.npz (:273-276). Inside an epoch nothing reads the device
+    back: losses and counts are kept as device tensors until the epoch's end. `seed`: step i's
+    dropout seed is seed + i (None: drawn per step). `optimizer`, `metrics`, `val_metrics`: an
+    AdamOptimizer and SegMetrics to go on from (default: fresh ones).
+
+    One deviation, documented and not copied: the reference weights the validation loss with
+    the training batch's sample weights (:344); here validation uses its own.
+    Returns the per-epoch history: a list of dicts with epoch, step, loss, accuracy, iou,
+    learning_rate, bn_decay and, on validation epochs, val_loss, val_accuracy, val_iou, saved."""
+    model = choose_model(use_color, use_normal, use_attention, attention_single_layer)
+    opt = optimizer if optimizer is not None else AdamOptimizer(store)
+    if step_fn is None:
+        def step_fn(*args, model=None, **kw):
+            return train_step_with(model, *args, **kw)
+    metrics = metrics if metrics is not None else SegMetrics(num_class, device)
+    val_metrics = val_metrics if val_metrics is not None else SegMetrics(num_class, device)
+    batches_per_epoch = n_train_samples / batch_size
+    history, losses, counts, best_iou = [], [], [], 0
+    it = iter(train_batches)
+    for i in range(int(epochs * batches_per_epoch)):
+        epoch = int((i + 1) / batches_per_epoch) + 1
+        try:
+            batch = next(it)
+        except StopIteration:
+            it = iter(train_batches)
+            batch = next(it)
+        xyz, labels, feats, smpw = get_data_tensors(batch, use_color, use_normal, device)
+        lr = get_learning_rate(opt.t, batch_size, n_train_samples)
+        bn_decay = get_bn_decay(opt.t, batch_size, n_train_samples)
+        loss, cnt = step_fn(store, opt, metrics, xyz, labels, smpw, num_class, bn_decay=bn_decay,
+                            learning_rate=lr, features=feats,
+                            seed=None if seed is None else seed + i, model=model)
+        losses.append(loss)
+        counts.append(cnt)
+        if (i + 1) % int(batches_per_epoch) == 0:
+            entry = {"epoch": epoch, "step": i + 1,
+                     "loss": float(torch.stack([x.detach().to(torch.float64)
+                                                for x in losses]).sum()) / batches_per_epoch,
+                     "accuracy": float(_accuracies(counts).sum()) / batches_per_epoch,
+                     "iou": float(metrics.iou()[0]),
+                     "learning_rate": get_learning_rate(opt.t, batch_size, n_train_samples),
+                     "bn_decay": get_bn_decay(opt.t, batch_size, n_train_samples)}
+            metrics.reset()
+            losses, counts = [], []
+            if val_batches is not None and epoch % n_epochs_to_val == 0:
+                vl, va, vi = eval_model(store, val_metrics, val_batches, use_color, use_normal,
+                                        num_class, model, eval_fn, device)
+                entry.update(val_loss=vl, val_accuracy=va, val_iou=vi, saved=None)
+                if vi > best_iou:
+                    best_iou = vi
+                    if save_dir is not None:
+                        os.makedirs(save_dir, exist_ok=True)
+                        path = os.path.join(save_dir, f"best_model_epoch_{epoch:03d}.npz")
+                        np.savez(path, **store.state_dict(), **opt.state_dict())
+                        entry["saved"] = path
+            history.append(entry)
+    return history
