@@ -157,8 +157,9 @@ int pn2_copy_f4(const void* src, void* dst, size_t bytes, int cus, pn2_stream_t 
  * argmax of the running min squared distance, ties broken exactly like the reference's
  * 512-thread block reduction: smallest (k mod 512), then smallest (k div 512)
  * (tf_sampling_g.cu:130-165). Distances are ((dx*dx+dy*dy)+dz*dz) in fp32 without FMA.
- * npoint must be > 0 (tf_sampling.cpp:99). N <= pn2_fps_max_points() needs no workspace;
- * larger N must use pn2_fps_ws. */
+ * npoint must be > 0 (tf_sampling.cpp:99). N <= PN2_FPS_MAX_POINTS (= pn2_fps_max_points())
+ * needs no workspace; larger N must use pn2_fps_ws. */
+#define PN2_FPS_MAX_POINTS 16384
 int pn2_fps(const float* xyz, int B, int N, int npoint, int32_t* idx, pn2_stream_t stream);
 /* Same, also writing new_xyz (B,npoint,3) = gather_point(xyz, idx) (pointnet_util.py:34). */
 int pn2_fps_gather(const float* xyz, int B, int N, int npoint, int32_t* idx, float* new_xyz,
@@ -181,17 +182,20 @@ int pn2_fps_ws(const float* xyz, int B, int N, int npoint, int32_t* idx, float* 
 /* The SSG sampler chain: stage 0 samples npoint[0] of the N points of each cloud, stage i
  * samples npoint[i] of stage i-1's output (pointnet2_sem_seg*.py:29-50 samples
  * 8192 -> 1024 -> 256 -> 64 -> 16). idx[i] (B,npoint[i]) and new_xyz[i] (B,npoint[i],3) are
- * exactly what pn2_fps_gather returns for that stage's input. N <= pn2_fps_max_points(),
- * npoint[i] <= 1024 for every stage that feeds another, 1 <= nstages <= 4. Host arrays of
- * device pointers. At most two launches on `stream`: a first stage over N > 1024 points as
- * the ordinary sampler, then every remaining stage fused in one launch, one workgroup per
- * cloud. Where those stages can be prefixes of their input (they are when that input is itself
- * a sampler's output -- SA2 sampling SA1's picks -- and no two points tie), the workgroup
+ * exactly what pn2_fps_gather returns for that stage's input. N <= PN2_FPS_MAX_POINTS,
+ * npoint[i] <= PN2_FPS_CHAIN_MAX_FEED for every stage that feeds another, 1 <= nstages <=
+ * PN2_FPS_CHAIN_MAX_STAGES. Host arrays of device pointers. At most two launches on `stream`:
+ * a first stage over N > PN2_FPS_CHAIN_MAX_FEED points as the ordinary sampler, then every
+ * remaining stage fused in one launch, one workgroup per cloud. Where those stages can be
+ * prefixes of their input (they are when that input is itself a sampler's output -- SA2
+ * sampling SA1's picks -- and no two points tie), the workgroup
  * checks that over every point of its cloud and writes the stages as copies of the prefix;
  * a cloud that fails the check (ties, duplicates, non-finite coordinates) has its stages run
  * as samplers by the same workgroup, the same picks either way (csrc/fps.hip
  * fps_chain_prefix_kernel). A single stage or stages that are not nested run on the hot-set
  * schedule (fps_chain_kernel). No output buffer is used as scratch. */
+#define PN2_FPS_CHAIN_MAX_FEED 1024
+#define PN2_FPS_CHAIN_MAX_STAGES 4
 int pn2_fps_chain(const float* xyz, int B, int N, int nstages, const int* npoint,
                   int32_t* const* idx, float* const* new_xyz, pn2_stream_t stream);
 /* pn2_fps_chain plus the automatic-edge grid of stage 0's picks (the known points of the last
@@ -238,7 +242,15 @@ float pn2_ball_threshold(float radius);
  *   `grid` = caller-owned device memory of pn2_grid_size(B, N) bytes, 16-byte aligned.
  * pn2_ball_query_grid: pn2_ball_query over a grid built on xyz1 (cell_edge = radius is the
  *   fast choice; any radius > 0 is exact). N <= 131072.
- * pn2_three_nn_grid (interpolation section): three_nn over a grid built on the known points. */
+ * pn2_three_nn_grid (interpolation section): three_nn over a grid built on the known points.
+ * Where the front ends (csrc/torch_ops.cpp, tf_grouping.py, tf_interpolate.py) switch from the
+ * scans to the grid, a speed choice only: a ball query over N >= PN2_BALL_GRID_MIN_POINTS points
+ * with B * M >= PN2_BALL_GRID_MIN_QUERIES queries, a three_nn over n * m >=
+ * PN2_NN_GRID_MIN_PAIRS pairs per cloud with m >= PN2_NN_GRID_MIN_KNOWN known points. */
+#define PN2_BALL_GRID_MIN_POINTS 2048
+#define PN2_BALL_GRID_MIN_QUERIES 1024
+#define PN2_NN_GRID_MIN_PAIRS (1 << 21)
+#define PN2_NN_GRID_MIN_KNOWN 512
 size_t pn2_grid_size(int B, int N);
 int pn2_grid_build(const float* xyz, int B, int N, float cell_edge, void* grid,
                    size_t grid_bytes, pn2_stream_t stream);
@@ -319,10 +331,13 @@ int pn2_sample_and_group(const float* xyz, const float* points, int B, int N, in
 /* Several set-abstraction layers' ball query + fused group/centre/concat in ONE launch
  * (the SSG stack's SA2..SA4, or one MSG level's radii, which all wait for the same sampler).
  * Per layer the outputs equal pn2_ball_query (idx, pts_cnt) followed by pn2_group_concat
- * (new_points, grouped_xyz) with the same arguments, bit for bit. Limits: N <= 1024 points
- * per cloud (the cloud is staged in LDS), nsample <= 128, at most PN2_SA_MAX_LAYERS layers;
- * every layer has the same B. grouped_xyz may be NULL. */
+ * (new_points, grouped_xyz) with the same arguments, bit for bit. Limits: N <=
+ * PN2_SA_GROUP_MAX_POINTS points per cloud (the cloud is staged in LDS), nsample <=
+ * PN2_SA_GROUP_MAX_NSAMPLE, at most PN2_SA_MAX_LAYERS layers; every layer has the same B.
+ * grouped_xyz may be NULL. */
 #define PN2_SA_MAX_LAYERS 4
+#define PN2_SA_GROUP_MAX_POINTS 1024
+#define PN2_SA_GROUP_MAX_NSAMPLE 128
 typedef struct pn2_sa_layer {
   const float* xyz;     /* (B,N,3) */
   const float* points;  /* (B,N,C) or NULL (then C is ignored and Cout = 3) */
@@ -399,11 +414,12 @@ int pn2_fp_apply(const float* dist, const int32_t* idx, const void* unknown_grid
 /* pn2_fp_fused for a large search (FP4: n = 8192 unknowns, m = 1024 known) in ONE launch:
  * every workgroup sorts the cloud's m known points into a grid in its own LDS (the automatic
  * edge of pn2_grid_build) and searches it, then writes its rows -- the output of
- * pn2_grid_build + pn2_three_nn_grid + pn2_fp_apply, bit for bit. 1 <= m <= 4096 (else
- * PN2_EINVAL); PN2_ENOTSUP when the known grid does not fit this device's LDS per workgroup
- * (use those three). `unknown_grid` (optional, a grid over the n unknown points)
+ * pn2_grid_build + pn2_three_nn_grid + pn2_fp_apply, bit for bit. 1 <= m <=
+ * PN2_FP_GRID_MAX_KNOWN (else PN2_EINVAL); PN2_ENOTSUP when the known grid does not fit this
+ * device's LDS per workgroup (use those three). `unknown_grid` (optional, a grid over the n unknown points)
  * orders the rows as in pn2_fp_apply; with it xyz1 may be NULL. dist / idx (B,n,3): the
  * three_nn result as well, or both NULL. C1 + C2 >= 1. */
+#define PN2_FP_GRID_MAX_KNOWN 4096
 int pn2_fp_grid_fused(const float* xyz1, const float* xyz2, const void* unknown_grid,
                       const float* points1, int C1, const float* points2, int C2, int B, int n,
                       int m, float* out, float* dist, int32_t* idx, pn2_stream_t stream);

@@ -113,8 +113,6 @@ __global__ void gather_point_grad_kernel(const float* __restrict__ out_g,
   atomicAdd(dst + 2, out_g[3 * (size_t)i + 2]);
 }
 
-constexpr int kMaxRegPoints = 1024 * 16;
-
 constexpr int kCullGridMax = 4096;  // picks whose grid the culled sampler builds itself
 
 // ---- device fault word ------------------------------------------------------------------
@@ -161,9 +159,9 @@ int take_fault() {
 // (BLOCK 256, or wave 0 alone). (Fusing the 8192-point stage too was measured slower: the
 // fused kernel's SA1 loop ran ~4% behind the same loop in its own kernel, more than the
 // launch it saved -- profiles/r1/chain_split.log.)
-constexpr int kChainMax = 4;
+// kChainMax stages of at most kChainNext points each (LDS: input copy + 2 hand-over arrays):
+// fps_cull.h defines both, and kMaxRegPoints, from include/pn2hip.h beside the pick packing.
 constexpr int kChainBlock = 256;  // 128 and 512 measured slower (profiles/r4/ab)
-constexpr int kChainNext = 1024;  // points per fused stage (LDS: input copy + 2 hand-over arrays)
 
 struct FpsChain {
   int stages;

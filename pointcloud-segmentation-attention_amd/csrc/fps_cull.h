@@ -220,6 +220,12 @@ PN2_DEV void hot_best4(const int (&hv)[4], const hf2 (&hx)[2], const hf2 (&hy)[2
 PN2_DEV uint32_t pick_tag(int p) { return ((uint32_t)(p + 1) & 0xFFFFu) << 16; }
 constexpr uint32_t kPickIdxMask = 0xFFFFu;  // point indices < 65536 (N <= 16384 here)
 constexpr int kPickTagMax = 0xFFFF;         // picks per launch below this: tags never repeat
+// the samplers' public limits (include/pn2hip.h), which the packing has to hold
+constexpr int kMaxRegPoints = PN2_FPS_MAX_POINTS;     // points per cloud of the register samplers
+constexpr int kChainNext = PN2_FPS_CHAIN_MAX_FEED;    // points per fused chain stage (fps.hip)
+constexpr int kChainMax = PN2_FPS_CHAIN_MAX_STAGES;   // stages of one chain launch
+static_assert(kMaxRegPoints <= kPickIdxMask + 1, "a point index must fit the slot's low half");
+static_assert(kChainMax * kChainNext < kPickTagMax, "a chain launch's pick tags must not repeat");
 #if PN2_PUBLISH_BROKEN
 __device__ unsigned int g_torn_reads;
 #define PN2_TORN_SEEN() if (lane == 0) atomicAdd(&g_torn_reads, 1u)

@@ -686,7 +686,8 @@ __global__ __launch_bounds__(kNNBlock) void fp_fused_kernel(FpLayer p, int tile)
 //   4. the rows (fp_write_rows).
 // A cloud's 128 workgroups each redo steps 1-2 over 12 KB of L2-resident points, which costs
 // less than the launch and the dependency they replace. Bit-identical to the three-launch path.
-constexpr int kFpGridMaxKnown = 4096;  // LDS: m float4 + (max(2m / ppc, 64) + 1) offsets
+// LDS: m float4 + (max(2m / ppc, 64) + 1) offsets
+constexpr int kFpGridMaxKnown = PN2_FP_GRID_MAX_KNOWN;
 constexpr float kFpgPointsPerCell = 2.0f;  // the LDS grid's points per cell (profiles/r4/ppc)
 // threads per workgroup (a quad per unknown: FB / 4 unknowns). The known grid is built (or
 // staged) once per workgroup, but fewer, bigger workgroups were slower at FP4: 512 / 1024

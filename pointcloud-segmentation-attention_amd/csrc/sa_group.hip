@@ -26,8 +26,8 @@ namespace {
 
 constexpr int kSgBlock = 256;
 constexpr int kSgWaves = kSgBlock / kWave;
-constexpr int kSgCap = 1024;    // points per cloud staged in LDS
-constexpr int kSgMaxNs = 128;   // nsample
+constexpr int kSgCap = PN2_SA_GROUP_MAX_POINTS;     // points per cloud staged in LDS
+constexpr int kSgMaxNs = PN2_SA_GROUP_MAX_NSAMPLE;  // nsample
 constexpr int kSgUnroll = 4;    // 64-point steps per scan iteration
 constexpr int kSgHits = 2048;   // hit slots per workgroup: qpb * nsample
 constexpr int kSgMaxQpb = 64;   // queries per workgroup

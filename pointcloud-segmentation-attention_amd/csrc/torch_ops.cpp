@@ -164,9 +164,10 @@ void chk_group_pool(const Tensor& x, const std::optional<Tensor>& gxyz, int64_t 
 }
 
 // Clouds / query batches at least this large take the spatial grid (identical results;
-// the same switch as tf_grouping.GRID_MIN_* and tf_interpolate.GRID_MIN_*).
-constexpr int64_t kBallGridMinPoints = 2048, kBallGridMinQueries = 1024;
-constexpr int64_t kNnGridMinPairs = int64_t(1) << 21, kNnGridMinKnown = 512;
+// tf_grouping.GRID_MIN_* and tf_interpolate.GRID_MIN_* read the same defines).
+constexpr int64_t kBallGridMinPoints = PN2_BALL_GRID_MIN_POINTS,
+                  kBallGridMinQueries = PN2_BALL_GRID_MIN_QUERIES;
+constexpr int64_t kNnGridMinPairs = PN2_NN_GRID_MIN_PAIRS, kNnGridMinKnown = PN2_NN_GRID_MIN_KNOWN;
 
 Tensor grid_over(const Tensor& xyz, double cell_edge, const char* op) {
   const int B = I(xyz.size(0)), N = I(xyz.size(1));

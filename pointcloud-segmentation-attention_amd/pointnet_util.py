@@ -30,9 +30,10 @@ import ctypes
 import torch
 
 from . import _torch_ops, tf_grouping, tf_interpolate, tf_sampling, tf_util
-from ._lib import (POOL_MODES, PN2_BQ_MAX_RADII, PN2_ENOTSUP, PN2_FP_MAX_LAYERS, PN2_POOL_NONE,
-                   PN2_SA_MAX_LAYERS, PN2_USE_XYZ, PN2_XYZ_LAST, FpLayer, InvalidArgumentError,
-                   SaLayer, check, device_tensor, lib, ptr, stream_of)
+from ._lib import (POOL_MODES, PN2_BQ_MAX_RADII, PN2_ENOTSUP, PN2_FP_GRID_MAX_KNOWN,
+                   PN2_FP_MAX_LAYERS, PN2_POOL_NONE, PN2_SA_GROUP_MAX_NSAMPLE,
+                   PN2_SA_GROUP_MAX_POINTS, PN2_SA_MAX_LAYERS, PN2_USE_XYZ, PN2_XYZ_LAST, FpLayer,
+                   InvalidArgumentError, SaLayer, check, device_tensor, lib, ptr, stream_of)
 
 
 def _is_empty_points(points):
@@ -183,8 +184,8 @@ def ball_group_xyz_radii(radii, nsamples, xyz, new_xyz, grid):
     return outs
 
 
-BALL_GROUP_MAX_POINTS = 1024  # pn2_ball_group_layers stages each cloud in LDS
-BALL_GROUP_MAX_NSAMPLE = 128
+BALL_GROUP_MAX_POINTS = PN2_SA_GROUP_MAX_POINTS  # pn2_ball_group_layers stages each cloud in LDS
+BALL_GROUP_MAX_NSAMPLE = PN2_SA_GROUP_MAX_NSAMPLE
 
 
 def ball_group_layers(layers, use_xyz=True, xyz_last=False, want_grouped_xyz=False):
@@ -310,7 +311,7 @@ def group_pool(new_points, pooling="max", grouped_xyz=None):
     return out
 
 
-FP_GRID_MAX_KNOWN = 4096  # pn2_fp_grid_fused's LDS bound on m
+FP_GRID_MAX_KNOWN = PN2_FP_GRID_MAX_KNOWN  # pn2_fp_grid_fused's LDS bound on m
 
 
 def fp_interpolate(xyz1, xyz2, points1, points2, known_grid=None, unknown_grid=None,

@@ -13,7 +13,8 @@ benchmark step's early grid) calls the C ABI directly.
 """
 import torch
 
-from ._lib import InvalidArgumentError, check, device_tensor, lib, ptr, stream_of
+from ._lib import (PN2_BALL_GRID_MIN_POINTS, PN2_BALL_GRID_MIN_QUERIES, InvalidArgumentError, check,
+                   device_tensor, lib, ptr, stream_of)
 from ._torch_ops import call
 from .grid import PointGrid
 
@@ -21,8 +22,8 @@ from .grid import PointGrid
 # Clouds at least this large (and query batches at least this large) use the spatial grid
 # (ball_grid.hip); smaller ones the in-order LDS scan (ball_query.hip). Both are exact and
 # return identical results; the switch is purely a speed choice (tools/tune_bq.py).
-GRID_MIN_POINTS = 2048
-GRID_MIN_QUERIES = 1024
+GRID_MIN_POINTS = PN2_BALL_GRID_MIN_POINTS
+GRID_MIN_QUERIES = PN2_BALL_GRID_MIN_QUERIES
 
 
 class BallGrid(PointGrid):

@@ -8,7 +8,8 @@ _torch_ops.py); three_nn with caller-built grids calls the C ABI directly.
 """
 import torch
 
-from ._lib import InvalidArgumentError, check, device_tensor, lib, ptr, stream_of
+from ._lib import (PN2_NN_GRID_MIN_KNOWN, PN2_NN_GRID_MIN_PAIRS, InvalidArgumentError, check,
+                   device_tensor, lib, ptr, stream_of)
 
 
 def _tensor(t, name, dtype):
@@ -27,8 +28,8 @@ from .grid import PointGrid
 # three_nn searches over a grid of the known points when the brute-force scan would test at
 # least this many (unknown, known) pairs per cloud and the known cloud is this large
 # (identical results either way; tools/tune_nn.py measured the switch).
-GRID_MIN_PAIRS = 1 << 21
-GRID_MIN_KNOWN = 512
+GRID_MIN_PAIRS = PN2_NN_GRID_MIN_PAIRS
+GRID_MIN_KNOWN = PN2_NN_GRID_MIN_KNOWN
 
 
 def use_grid(n, m):

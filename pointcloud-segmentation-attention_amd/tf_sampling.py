@@ -8,7 +8,8 @@ import ctypes
 
 import torch
 
-from ._lib import InvalidArgumentError, check, device_tensor, lib, ptr, stream_of
+from ._lib import (PN2_FPS_CHAIN_MAX_FEED, PN2_FPS_CHAIN_MAX_STAGES, PN2_FPS_MAX_POINTS,
+                   InvalidArgumentError, check, device_tensor, lib, ptr, stream_of)
 from ._torch_ops import call
 
 
@@ -54,9 +55,9 @@ def farthest_point_sample_and_gather(npoint, inp):
     return _fps(npoint, inp, True)
 
 
-CHAIN_MAX_POINTS = 16384  # pn2_fps_chain: first stage's points per cloud (pn2_fps_max_points)
-CHAIN_MAX_FEED = 1024     # points one stage hands to the next
-CHAIN_MAX_STAGES = 4
+CHAIN_MAX_POINTS = PN2_FPS_MAX_POINTS       # pn2_fps_chain: first stage's points per cloud
+CHAIN_MAX_FEED = PN2_FPS_CHAIN_MAX_FEED     # points one stage hands to the next
+CHAIN_MAX_STAGES = PN2_FPS_CHAIN_MAX_STAGES
 
 
 def chain_supported(N, npoints):

@@ -435,7 +435,7 @@ def test_publish_tag_check_catches_torn_reads(env):
     _exact("torn-build SA1 idx", idx.cpu().numpy(), ref)
     _exact("torn-build SA1 new_xyz", nx.cpu().numpy(), O.gather_point(x, ref))
     # the chain (1,024 -> 256 -> 64 -> 16) over a raw cloud: over the SA1 picks its stages
-    # would be prefixes (fps_prefix_holds) and no stage would sample
+    # would be prefixes (fps_chain_prefix_kernel) and no stage would sample
     nx1 = _cloud(pkg, "scannet", 8, 1024, seed=6)
     rc, outs = _chain_call(h, torch.from_numpy(nx1).to(dev), [256, 64, 16], dev, torch)
     assert rc == 0
@@ -471,7 +471,7 @@ def _chain_vs_oracle(pkg, O, torch, dev, p, npoints, what):
 def test_chain_over_sampler_output_is_prefix(env):
     """A chain over an earlier sampler's picks (SA2-4 over the SA1 sampler's new_xyz): every
     stage is the prefix of its input (pick j of the SA1 sampling was the farthest point of the
-    whole cloud, hence of its picks), which fps_prefix_holds verifies -- unique maxima at every
+    whole cloud, hence of its picks), which fps_chain_prefix_kernel verifies -- unique maxima at every
     step -- before the chain kernel writes the outputs as copies. Exact against the oracle's
     samplers stage by stage, on ScanNet and uniform clouds (and the property itself holds)."""
     pkg, O, torch, dev = env

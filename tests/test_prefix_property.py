@@ -1,4 +1,4 @@
-"""The property the chain's prefix check rests on (csrc/fps.hip fps_prefix_holds), on the C
+"""The property the chain's prefix check rests on (csrc/fps.hip fps_chain_prefix_kernel), on the C
 oracle's restatement of the reference sampler (oracle/pn2_oracle.c, tf_sampling_g.cu:105-170):
 sampling a sampler's picks returns their prefix (SA2's 256 of SA1's 1,024 are SA1's first 256,
 SA3's 64 of those their first 64, ...), and an exact tie between a pick and a later point is
