@@ -136,11 +136,15 @@ typedef void* pn2_stream_t; /* hipStream_t */
 /* shared-MLP layers (pn2_group_mlp / pn2_fp_mlp / pn2_shared_mlp) */
 #define PN2_MLP_MAX_LAYERS 6
 #define PN2_MLP_RELU 1 /* activation_fn = tf.nn.relu (tf_util.conv2d's default) */
+#define PN2_MLP_BF16 2 /* `packed` is pn2_mlp_pack_bf16's output: the layer's product runs on the
+                          bf16 matrix cores (opt-in; the contract is at pn2_mlp_pack_bf16)     */
 
 typedef struct pn2_mlp_layer {
-  const void* packed; /* pn2_mlp_pack output (device, 16-byte aligned)                    */
+  const void* packed; /* pn2_mlp_pack / pn2_mlp_pack_bf16 output (device, 16-byte aligned) */
   int cin, cout;      /* the conv's input / output channels                              */
-  int flags;          /* PN2_MLP_RELU                                                    */
+  int flags;          /* PN2_MLP_RELU | PN2_MLP_BF16; PN2_MLP_BF16 must be set exactly when
+                         `packed` came from pn2_mlp_pack_bf16 (the two layouts differ and
+                         nothing in the buffer tells them apart)                          */
 } pn2_mlp_layer;
 
 const char* pn2_version(void);
@@ -522,6 +526,32 @@ size_t pn2_mlp_packed_size(int cin, int cout);
 int pn2_mlp_pack(const float* weight, const float* bias, const float* bn_scale,
                  const float* bn_shift, int cin, int cout, void* packed, size_t packed_bytes,
                  pn2_stream_t stream);
+/* The same layer for the bf16 matrix cores (v_mfma_f32_32x32x16_bf16), an opt-in: nothing
+ * selects it but a caller that packs with this function and sets PN2_MLP_BF16 in the layer's
+ * flags. Numerical contract of a layer packed here:
+ *   y[o] = act((sum_f bf16(x[f]) * bf16(weight[f][o])) * scale[o] + shift[o])
+ * - bf16(.) is round-to-nearest-even from fp32; the weights are rounded once, here, the
+ *   activations at the layer's input (the layer before still hands over fp32 values);
+ * - the products are exact and the sums accumulate in fp32;
+ * - scale = bn_scale, shift = bias * bn_scale + bn_shift, the ReLU, the pooling, the gather and
+ *   centring, the IDW interpolation, the attention's query, scores, softmax, weighted sum and
+ *   batch norm, and everything written to HBM stay fp32 and unrounded;
+ * - a chain may mix bf16 and fp32 layers in any order;
+ * - subnormal operands (inputs, weights, and values that round to a bf16 subnormal) are out of
+ *   contract: the matrix cores may flush them.
+ * Layout: Wp[to][c][h][i][j] = bf16(weight[16c + 8h + j][32to + i]) for output tile to, input
+ * chunk c of 16, lane half h, lane i, element j = 0..7 (one 16-byte load per lane per MFMA), cin
+ * padded with zeros to a multiple of 16, cout to a multiple of 32; then fp32 scale and shift
+ * (32 * ceil(cout/32) each), as in pn2_mlp_pack's layout. pn2_mlp_packed_size_bf16 =
+ *   ceil(cout/32) * (ceil(cin/16) * 1024 + 256) bytes.
+ * pn2_group_mlp, pn2_fp_mlp, pn2_shared_mlp, pn2_shared_mlp_plan and pn2_group_mlp_attention
+ * honour the flag per layer; in pn2_group_mlp_attention qkv[1] and qkv[2] (key, value) may be
+ * bf16, qkv[0] (the query, VALU work on the fp32 layout) may not: PN2_EINVAL before any
+ * launch. The training entry points take no packed layers and stay fp32. */
+size_t pn2_mlp_packed_size_bf16(int cin, int cout);
+int pn2_mlp_pack_bf16(const float* weight, const float* bias, const float* bn_scale,
+                      const float* bn_shift, int cin, int cout, void* packed,
+                      size_t packed_bytes, pn2_stream_t stream);
 
 /* pointnet_sa_module after sampling and ball query (pointnet_util.py:106-145, MSG :184-200):
  * group + centre + concat exactly as pn2_group_concat (flags), then `nlayers` packed layers

@@ -209,7 +209,10 @@ def group_mlp_attention(xyz, points, new_xyz, idx, mlp, store, scope, and_poolin
         points = device_tensor(points, "points", torch.float32)
         Cin = int(points.shape[2])
     C = mlp.cout
-    qkv = [tf_util.packed_dense(store, d, C, C) for d in _attention_scopes(scope)]
+    # the query Dense is VALU work on the fp32 layout: fp32 whatever the store's precision
+    qs, ks, vs = _attention_scopes(scope)
+    qkv = [tf_util.packed_dense(store, qs, C, C, precision="fp32"),
+           tf_util.packed_dense(store, ks, C, C), tf_util.packed_dense(store, vs, C, C)]
     table = (type(mlp.table()[0][0]) * 3)(*[d.layers[0].struct() for d in qkv])
     scale, shift = tf_util.bn_affine(store, f"{scope}/{scope}", C, xyz.device)
     out = torch.empty((B, M, C), dtype=torch.float32, device=xyz.device)
@@ -229,7 +232,7 @@ def sa_attention_tail(X, store, scope, C, and_pooling=False):
     qs, ks, vs = _attention_scopes(scope)
     K = tf_util.packed_dense(store, ks, C, C)(X)
     V = tf_util.packed_dense(store, vs, C, C)(X)
-    Q = tf_util.packed_dense(store, qs, C, C)(X[:, :, 0].contiguous())
+    Q = tf_util.packed_dense(store, qs, C, C, precision="fp32")(X[:, :, 0].contiguous())
     out = attention_reduce(Q, K, V)
     scale, shift = tf_util.bn_affine(store, f"{scope}/{scope}", C, X.device)
     out = out * scale + shift

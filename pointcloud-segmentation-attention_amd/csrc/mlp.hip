@@ -25,6 +25,16 @@
 // Both orientations read the operands through the same lane maps, so one packed weight format
 // serves every layer: Wp[to][c][h][i][s] = W[8c + 4h + s][32*to + i] (pn2_mlp_pack), one
 // float4 per lane per 4 MFMAs, and activations are read as act[p][8c + 4h .. +3].
+//
+// bf16 layers (PN2_MLP_BF16, opt-in per layer; the contract is in include/pn2hip.h): the same
+// two orientations on v_mfma_f32_32x32x16_bf16, whose operand map puts k = 8h + j, j = 0..7, on
+// lane (i, h): Wp[to][c][h][i][j] = bf16(W[16c + 8h + j][32*to + i]) (pn2_mlp_pack_bf16), one
+// 16-byte load per lane per MFMA, and activations, fp32 in LDS as for every layer, are read as
+// act[p][16c + 8h .. +7] and rounded to bf16 (nearest even) on the way into the MFMA. A 16-feature
+// chunk of a bf16 tile takes the 1024 bytes an 8-feature chunk of an fp32 tile takes, so both
+// formats share the block arithmetic (chunks x 256 floats, then scale and shift). Kernels for
+// chains with a bf16 layer are instantiations of their own (template parameter BF): the fp32
+// chains run the code they ran before bf16 existed.
 #include <cstdio>
 #include <cstdlib>
 
@@ -34,6 +44,8 @@ namespace pn2 {
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / kWave;
@@ -43,11 +55,12 @@ enum Src : int { kSrcGroup = 0, kSrcFP = 1, kSrcRows = 2 };
 enum Layout : int { kPointsOnly = 0, kXyzOnly = 1, kXyzFirst = 2, kXyzLast = 3 };
 
 struct LayerDev {
-  const float4* w;     // packed weights [cout32][cin8][64] float4
+  const float4* w;     // packed weights [cout32][cin8][64] x 16 bytes
   const float* scale;  // [cout32*32]
   const float* shift;  // [cout32*32]
-  int cin8, cout32, cout, relu;
+  int cin8, cout32, cout, relu;  // cin8 = K chunks: of 8 input features (fp32), of 16 (bf16)
   int lofs;  // float offset of this layer's packed block in the LDS weight copy (WL kernels)
+  int bf;    // packed by pn2_mlp_pack_bf16 (read by the BF kernels only)
 };
 
 struct Params {
@@ -193,6 +206,91 @@ PN2_DEV void mma_item(const float4* __restrict__ wp, const float* ap, int rstrid
 #pragma unroll
     for (int r = 0; r < RG; ++r) mma4(w, act4(r, c), acc[r]);
   }
+}
+
+// Two fp32 to one packed bf16 pair (lo in bits 0..15), round to nearest even; no builtin.
+PN2_DEV uint32_t cvt_pk_bf16(float lo, float hi) {
+  uint32_t r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  return r;
+}
+
+// mma_item for a bf16 layer: kch chunks of 16 input features, one MFMA per chunk and row tile
+// (k = 16c + 8h + j, j = 0..7). wp = the tile's packed weights at this lane (16 bytes = the
+// lane's 8 bf16), ap = this lane's activation row (+8h) in the first row tile: two 16-byte
+// fp32 reads per chunk, rounded on the way into the MFMA. A chunk is one 32-cycle MFMA per row
+// tile where mma_item's is four 64-cycle ones, so the loads run further ahead in chunks: the
+// weights (global memory or the LDS copy) in a ring of D chunks, each slot refilled as soon as
+// it is consumed, the activations (LDS) AD chunks ahead, held as loaded (fp32).
+template <bool LAST, int RG>
+PN2_DEV void mma_item_bf16(const u32x4* __restrict__ wp, const float* ap, int rstride, int kch,
+                           f32x16 (&acc)[RG]) {
+  constexpr int D = 8, AD = RG >= 2 ? 1 : 2;
+#pragma unroll
+  for (int r = 0; r < RG; ++r)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[r][i] = 0.f;
+  struct Act {
+    float4 lo, hi;
+  };
+  auto mma1 = [&](const u32x4& w, const Act& a, f32x16& c) {
+    u32x4 p;
+    p.x = cvt_pk_bf16(a.lo.x, a.lo.y);
+    p.y = cvt_pk_bf16(a.lo.z, a.lo.w);
+    p.z = cvt_pk_bf16(a.hi.x, a.hi.y);
+    p.w = cvt_pk_bf16(a.hi.z, a.hi.w);
+    const bf16x8 av = __builtin_bit_cast(bf16x8, p), wv = __builtin_bit_cast(bf16x8, w);
+    if (LAST) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, wv, c, 0, 0, 0);
+    else c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv, av, c, 0, 0, 0);
+  };
+  auto act8 = [&](int r, int c) {
+    const float* q = ap + r * rstride + 16 * c;
+    return Act{*reinterpret_cast<const float4*>(q), *reinterpret_cast<const float4*>(q + 4)};
+  };
+  u32x4 w[D];
+  Act a[AD][RG];
+#pragma unroll
+  for (int u = 0; u < D; ++u)
+    if (u < kch) w[u] = wp[(size_t)u * kWave];
+#pragma unroll
+  for (int u = 0; u < AD; ++u)
+    if (u < kch) {
+#pragma unroll
+      for (int r = 0; r < RG; ++r) a[u][r] = act8(r, u);
+    }
+  for (int c0 = 0; c0 < kch; c0 += D) {
+#pragma unroll
+    for (int u = 0; u < D; ++u) {
+      const int c = c0 + u;
+      if (c >= kch) break;
+      const u32x4 wv = w[u];
+      Act av[RG];
+#pragma unroll
+      for (int r = 0; r < RG; ++r) av[r] = a[u % AD][r];
+      if (c + D < kch) w[u] = wp[(size_t)(c + D) * kWave];
+      if (c + AD < kch) {
+#pragma unroll
+        for (int r = 0; r < RG; ++r) a[u % AD][r] = act8(r, c + AD);
+      }
+#pragma unroll
+      for (int r = 0; r < RG; ++r) mma1(wv, av[r], acc[r]);
+    }
+  }
+}
+
+// The product of one item in the layer's own format. wp = the tile's packed block at this lane,
+// ap = this lane's activation row in the first row tile, + 4h (a bf16 lane starts at + 8h).
+template <bool LAST, int RG, bool BF>
+PN2_DEV void mma_layer(const LayerDev& Ld, const float4* wp, const float* ap, int h,
+                       int rstride, f32x16 (&acc)[RG]) {
+  if constexpr (BF) {
+    if (Ld.bf) {
+      mma_item_bf16<LAST, RG>(reinterpret_cast<const u32x4*>(wp), ap + 4 * h, rstride, Ld.cin8,
+                              acc);
+      return;
+    }
+  }
+  mma_item<LAST, RG>(wp, ap, rstride, Ld.cin8, acc);
 }
 
 // One segment of every slot's input row: n units per row (float4 chunks or floats), fetched
@@ -354,7 +452,7 @@ PN2_DEV void store_pooled(const Params& prm, int g, int fo, int cout, float mx, 
 // over row tile rt of X, written (scale/shift epilogue = bias) into dst at column
 // (to - to0)*32, rows 32*rt + col. For the query, row_of_lane maps lane col to X row
 // col*ns_pad (the first neighbour of group col) and only rows < nrows are written.
-template <int RG>
+template <int RG, bool BF>
 PN2_DEV void dense_item(const LayerDev& D, const float* X, int Sx, int xrow, int to, int to0,
                         float* dst, int Sd, int drow, int lane, int h) {
   float4 sc[4], sh[4];
@@ -365,8 +463,8 @@ PN2_DEV void dense_item(const LayerDev& D, const float* X, int Sx, int xrow, int
     sh[q] = *reinterpret_cast<const float4*>(D.shift + fb);
   }
   f32x16 acc[RG];
-  mma_item<false, RG>(D.w + (size_t)to * D.cin8 * kWave + lane, X + xrow * Sx + 4 * h, 32 * Sx,
-                      D.cin8, acc);
+  mma_layer<false, RG, BF>(D, D.w + (size_t)to * D.cin8 * kWave + lane, X + xrow * Sx + 4 * h, h,
+                           32 * Sx, acc);
 #pragma unroll
   for (int r = 0; r < RG; ++r) {
     float* op = dst + (drow + 32 * r) * Sd + 32 * (to - to0) + 4 * h;
@@ -521,7 +619,7 @@ PN2_DEV void attn_scores(const Params& prm, const float* X, int Sx, const float*
 // K and V (the tf.reshape quirk of :35-36): with C <= 4*ns that block spans whole rows (K and V
 // are computed whole, one segment); with C = k*4*ns it is the column block h % k of row h / k,
 // so K and V are computed k column segments at a time and each segment completes its heads.
-template <int R>
+template <int R, bool BF>
 PN2_DEV void attention_tail(const Params& prm, float* smem, const float* X, int Sx, int tile) {
   const int tid = threadIdx.x, lane = lane_id(), wave = tid / kWave;
   const int col = lane & 31, h = lane >> 5;
@@ -548,7 +646,7 @@ PN2_DEV void attention_tail(const Params& prm, float* smem, const float* X, int 
       const int which = item / (npair * t_seg);
       const int rem = item - which * (npair * t_seg);
       const int to = sgi * t_seg + rem / npair, rt = (rem % npair) * RGk;
-      dense_item<RGk>(prm.qkv[1 + which], X, Sx, 32 * rt + col, to, sgi * t_seg,
+      dense_item<RGk, BF>(prm.qkv[1 + which], X, Sx, 32 * rt + col, to, sgi * t_seg,
                       which ? Vb : Kb, Skv, 32 * rt + col, lane, h);
     }
     __syncthreads();
@@ -584,7 +682,7 @@ struct Ctx {
 // One item of layer l: the MFMA product, then either the intermediate epilogue (scale,
 // shift, activation, 16-byte writes into the other LDS buffer) or the last layer's (per-point
 // stores, or per-group pooling partials in LDS).
-template <int SRC, int R, int RG, bool WL>
+template <int SRC, int R, int RG, bool WL, bool BF>
 PN2_DEV void layer_item(const Ctx& cx, int l, bool last, int to, int rt0, int pass) {
   constexpr int P = 32 * R;
   const Params& prm = *cx.prm;
@@ -614,7 +712,7 @@ PN2_DEV void layer_item(const Ctx& cx, int l, bool last, int to, int rt0, int pa
       sc[q] = *reinterpret_cast<const float4*>(scale + fb);
       sh[q] = *reinterpret_cast<const float4*>(shift + fb);
     }
-    mma_item<false, RG>(wp, ap, 32 * Sin, Ld.cin8, acc);
+    mma_layer<false, RG, BF>(Ld, wp, ap, h, 32 * Sin, acc);
 #pragma unroll
     for (int r = 0; r < RG; ++r) {
       // rows = features 32*to + 8q + 4h + e (e = reg & 3), column = point 32*(rt0+r) + col
@@ -637,7 +735,7 @@ PN2_DEV void layer_item(const Ctx& cx, int l, bool last, int to, int rt0, int pa
   const bool st = prm.stamp && blockIdx.x < kStampWG && threadIdx.x == 0 && to == 0;
   if (st) prm.stamp[blockIdx.x * 16 + 10] = __builtin_amdgcn_s_memtime();
 #endif
-  mma_item<true, RG>(wp, ap, 32 * Sin, Ld.cin8, acc);
+  mma_layer<true, RG, BF>(Ld, wp, ap, h, 32 * Sin, acc);
 #ifdef PN2_MLP_STAMP
   if (st) {
     __builtin_amdgcn_s_waitcnt(0);
@@ -809,7 +907,7 @@ PN2_DEV void commit_meta(const Params& prm, int tile, int pass, int p, const Met
   s_pw[p] = pw;
 }
 
-template <int SRC, int R, bool WL>
+template <int SRC, int R, bool WL, bool BF>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) void mlp_kernel(const Params prm) {
   constexpr int P = 32 * R;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -928,15 +1026,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) 
       for (int item = wave; item < nitems; item += kWaves) {
         const int to = item / nsplit;
         const int rt0 = (item - to * nsplit) * rg_tiles;
-        if (rg_tiles == 1) layer_item<SRC, R, 1, WL>(ctx, l, last, to, rt0, pass);
-        else layer_item<SRC, R, (R >= 2 ? 2 : 1), WL>(ctx, l, last, to, rt0, pass);
+        if (rg_tiles == 1) layer_item<SRC, R, 1, WL, BF>(ctx, l, last, to, rt0, pass);
+        else layer_item<SRC, R, (R >= 2 ? 2 : 1), WL, BF>(ctx, l, last, to, rt0, pass);
       }
       __syncthreads();
       PN2_STAMP(3 + l);
     }
 
     if constexpr (SRC == kSrcGroup) {
-      if (prm.attn) attention_tail<R>(prm, smem, (prm.nl & 1) ? act1 : act0,
+      if (prm.attn) attention_tail<R, BF>(prm, smem, (prm.nl & 1) ? act1 : act0,
                                       (prm.nl & 1) ? prm.stride1 : prm.stride0, tile);
     } else if (prm.stage_out) {
       // the tile's output rows are contiguous in HBM: one wave per row, whole rows stored
@@ -1028,6 +1126,55 @@ __global__ void mlp_pack_kernel(const float* __restrict__ W, const float* __rest
   }
 }
 
+// fp32 to bf16, round to nearest even (the rounding of v_cvt_pk_bf16_f32)
+PN2_DEV uint16_t bf16_rne(float v) {
+  uint32_t u = __float_as_uint(v);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);  // NaN stays NaN
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
+
+// Packed bf16 layer: Wp [cout32][cin16][2][32][8] bf16 (Wp[to][c][h][i][j] =
+// bf16(W[16c + 8h + j][32to + i])), then scale and shift as mlp_pack_kernel (fp32).
+__global__ void mlp_pack_bf16_kernel(const float* __restrict__ W, const float* __restrict__ bias,
+                                     const float* __restrict__ bn_scale,
+                                     const float* __restrict__ bn_shift, int cin, int cout,
+                                     int cin16, int cout32, void* __restrict__ packed) {
+  const long long nw = (long long)cout32 * cin16 * 512;  // bf16 elements
+  const long long total = nw + 2LL * cout32 * 32;
+  uint16_t* wp = static_cast<uint16_t*>(packed);
+  float* sp = static_cast<float*>(packed) + nw / 2;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
+       e += (long long)gridDim.x * blockDim.x) {
+    if (e < nw) {
+      const int j = (int)(e & 7);
+      const int i = (int)((e >> 3) & 31);
+      const int hh = (int)((e >> 8) & 1);
+      const long long tc = e >> 9;
+      const int c = (int)(tc % cin16);
+      const int to = (int)(tc / cin16);
+      const int f = 16 * c + 8 * hh + j, o = 32 * to + i;
+      wp[e] = (f < cin && o < cout) ? bf16_rne(W[(size_t)f * cout + o]) : (uint16_t)0;
+    } else {
+      const long long r = e - nw;
+      const int which = (int)(r / (cout32 * 32));
+      const int o = (int)(r % (cout32 * 32));
+      float v = 0.f;
+      if (o < cout) {
+        const float sc = bn_scale ? bn_scale[o] : 1.f;
+        if (which == 0) v = sc;
+        else v = (bias ? bias[o] : 0.f) * sc + (bn_shift ? bn_shift[o] : 0.f);
+      }
+      sp[r] = v;
+    }
+  }
+}
+
+// K chunks of a layer in its packed format: 8 input features per chunk (fp32), 16 (bf16)
+int k_chunks(const pn2_mlp_layer& L) {
+  return (L.flags & PN2_MLP_BF16) ? (L.cin + 15) / 16 : (L.cin + 7) / 8;
+}
+
 int next_pow2(int v) {
   int p = 1;
   while (p < v) p <<= 1;
@@ -1046,10 +1193,13 @@ size_t plan(Params& prm, int nl, const pn2_mlp_layer* layers, int cin0, int R, b
             bool wl = false) {
   const int P = 32 * R;
   int wfloats = 0;
-  int w0 = ((cin0 + 7) / 8) * 8, w1 = 0;
+  // layer 0 reads whole chunks of its row: 8 features per chunk, 16 when it is bf16 (the
+  // gather zeroes the columns from cin0 up to this width)
+  const int width0 = k_chunks(layers[0]) * ((layers[0].flags & PN2_MLP_BF16) ? 16 : 8);
+  int w0 = width0, w1 = 0;
   for (int l = 0; l < nl; ++l) {
     const pn2_mlp_layer& L = layers[l];
-    const int cin8 = (L.cin + 7) / 8, cout32 = (L.cout + 31) / 32;
+    const int cin8 = k_chunks(L), cout32 = (L.cout + 31) / 32;
     const float* base = static_cast<const float*>(L.packed);
     prm.L[l].w = reinterpret_cast<const float4*>(base);
     prm.L[l].scale = base + (size_t)cout32 * cin8 * 256;
@@ -1058,6 +1208,7 @@ size_t plan(Params& prm, int nl, const pn2_mlp_layer* layers, int cin0, int R, b
     prm.L[l].cout32 = cout32;
     prm.L[l].cout = L.cout;
     prm.L[l].relu = (L.flags & PN2_MLP_RELU) ? 1 : 0;
+    prm.L[l].bf = (L.flags & PN2_MLP_BF16) ? 1 : 0;
     prm.L[l].lofs = wfloats;
     wfloats += cout32 * cin8 * 256 + cout32 * 64;
     if (l < nl - 1 || prm.attn || prm.stage_out) {  // layer l writes buffer (l+1)&1
@@ -1066,9 +1217,15 @@ size_t plan(Params& prm, int nl, const pn2_mlp_layer* layers, int cin0, int R, b
     }
   }
   prm.nl = nl;
-  prm.width0 = ((cin0 + 7) / 8) * 8;
+  prm.width0 = width0;
   // row strides = 4 (mod 32) floats: the 16-byte reads/writes of 8 consecutive rows hit
-  // distinct bank quads
+  // distinct bank quads. A bf16 layer reads two 16-byte pieces per lane (columns 8h and
+  // 8h + 4 of its row), each a ds_read_b128 of its own: the LDS serves one in four groups of
+  // 16 lanes, every group inside one lane half (one h), so a group reads one column of 16
+  // rows whose numbers cover every residue mod 16. Banks count mod 64 dwords for this read,
+  // and a stride of 4 or 36 (mod 64) dwords sends those 16 rows to the 16 distinct 16-byte
+  // slots of the 256-byte bank row (4r and 36r = 4 * 9r are bijections of r mod 16 onto the
+  // slots): no conflict in either piece, so the rule stands as it is.
   prm.stride0 = ((w0 + 31) / 32) * 32 + 4;
   prm.stride1 = ((w1 + 31) / 32) * 32 + 4;
   const int coutp = prm.L[nl - 1].cout32 * 32;
@@ -1130,7 +1287,7 @@ int check_layers(int nl, const pn2_mlp_layer* layers, int cin0) {
 }
 
 // Compute units of the current device (cached per device id).
-int device_cus() {
+[[maybe_unused]] int device_cus() {  // (unused by the PN2_MLP_STAMP build)
   static int cache[64] = {0};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
@@ -1162,10 +1319,10 @@ int choose_tpw(long long nblocks, size_t lds) {
 }
 
 // Dynamic LDS beyond the 64 KiB default is opted into once per instantiation.
-template <int SRC, int R, bool WL>
+template <int SRC, int R, bool WL, bool BF>
 int launch_one(Params prm, long long nblocks, size_t lds, hipStream_t s) {
   static const hipError_t attr = hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&mlp_kernel<SRC, R, WL>),
+      reinterpret_cast<const void*>(&mlp_kernel<SRC, R, WL, BF>),
       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit);
   if (attr != hipSuccess) return (int)attr;
   prm.ntiles = (int)nblocks;
@@ -1174,23 +1331,33 @@ int launch_one(Params prm, long long nblocks, size_t lds, hipStream_t s) {
 #ifdef PN2_MLP_STAMP
   prm.stamp = g_stamp;
 #endif
-  hipLaunchKernelGGL((mlp_kernel<SRC, R, WL>), dim3((unsigned)grid), dim3(kBlock), lds, s, prm);
+  hipLaunchKernelGGL((mlp_kernel<SRC, R, WL, BF>), dim3((unsigned)grid), dim3(kBlock), lds, s, prm);
   PN2_RETURN_LAUNCH();
+}
+
+template <int SRC, bool BF>
+int launch_rows_BF(Params& prm, int R, long long nblocks, size_t lds, hipStream_t s) {
+  if (prm.wfloats) {  // weights staged in LDS (small MLPs of the SA layers)
+    if (SRC != kSrcGroup) return PN2_EINVAL;
+    if (R == 1) return launch_one<kSrcGroup, 1, true, BF>(prm, nblocks, lds, s);
+    if (R == 2) return launch_one<kSrcGroup, 2, true, BF>(prm, nblocks, lds, s);
+    return launch_one<kSrcGroup, 4, true, BF>(prm, nblocks, lds, s);
+  }
+  if (R == 1) return launch_one<SRC, 1, false, BF>(prm, nblocks, lds, s);
+  if (R == 2) return launch_one<SRC, 2, false, BF>(prm, nblocks, lds, s);
+  return launch_one<SRC, 4, false, BF>(prm, nblocks, lds, s);
 }
 
 template <int SRC>
 int launch_rows_R(Params& prm, int R, long long nblocks, size_t lds, hipStream_t s) {
   if (nblocks <= 0) return PN2_OK;
   if (nblocks > 0x7fffffffLL) return PN2_EINVAL;
-  if (prm.wfloats) {  // weights staged in LDS (small MLPs of the SA layers)
-    if (SRC != kSrcGroup) return PN2_EINVAL;
-    if (R == 1) return launch_one<kSrcGroup, 1, true>(prm, nblocks, lds, s);
-    if (R == 2) return launch_one<kSrcGroup, 2, true>(prm, nblocks, lds, s);
-    return launch_one<kSrcGroup, 4, true>(prm, nblocks, lds, s);
-  }
-  if (R == 1) return launch_one<SRC, 1, false>(prm, nblocks, lds, s);
-  if (R == 2) return launch_one<SRC, 2, false>(prm, nblocks, lds, s);
-  return launch_one<SRC, 4, false>(prm, nblocks, lds, s);
+  // a chain with any bf16 layer (the attention's key / value Dense included) runs the BF
+  // instantiation; every other chain the fp32-only one
+  bool bf = prm.attn && (prm.qkv[1].bf || prm.qkv[2].bf);
+  for (int l = 0; l < prm.nl; ++l) bf = bf || prm.L[l].bf;
+  if (bf) return launch_rows_BF<SRC, true>(prm, R, nblocks, lds, s);
+  return launch_rows_BF<SRC, false>(prm, R, nblocks, lds, s);
 }
 
 // Row tiles per workgroup: prefer the cheapest R whose LDS lets two
@@ -1211,7 +1378,10 @@ int choose_R(Params& prm, int nl, const pn2_mlp_layer* layers, int cin0, bool po
       const int c32 = (layers[l].cout + 31) / 32, cin8 = (layers[l].cin + 7) / 8;
       const int nsplit = item_split(R, c32);
       const int items = nsplit * c32, rg = R / nsplit;
-      cost += (double)((items + kWaves - 1) / kWaves) * (rg * cin8 + 4) / R;
+      // a bf16 layer spends one 32-cycle MFMA where fp32 spends eight 64-cycle ones, so its
+      // 8-feature chunk costs 1/16; the exposed weight-load latency is the same
+      const double chunk = (layers[l].flags & PN2_MLP_BF16) ? 1.0 / 16 : 1.0;
+      cost += (double)((items + kWaves - 1) / kWaves) * (rg * cin8 * chunk + 4) / R;
     }
     const int occ = lds * 2 <= kLdsLimit ? 2 : 1;
     if (!best || occ > best_occ || (occ == best_occ && cost < best_cost)) {
@@ -1287,6 +1457,29 @@ int pn2_mlp_pack(const float* weight, const float* bias, const float* bn_scale,
   PN2_RETURN_LAUNCH();
 }
 
+size_t pn2_mlp_packed_size_bf16(int cin, int cout) {
+  if (cin <= 0 || cout <= 0) return 0;
+  const size_t cin16 = (size_t)(cin + 15) / 16, cout32 = (size_t)(cout + 31) / 32;
+  return cout32 * cin16 * 512 * sizeof(uint16_t) + 2 * cout32 * 32 * sizeof(float);
+}
+
+int pn2_mlp_pack_bf16(const float* weight, const float* bias, const float* bn_scale,
+                      const float* bn_shift, int cin, int cout, void* packed,
+                      size_t packed_bytes, pn2_stream_t stream) {
+  if (cin <= 0 || cout <= 0 || !weight || !packed) return PN2_EINVAL;
+  if (packed_bytes < pn2_mlp_packed_size_bf16(cin, cout)) return PN2_EINVAL;
+  if ((!bn_scale) != (!bn_shift)) return PN2_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0) return PN2_EINVAL;
+  const int cin16 = (cin + 15) / 16, cout32 = (cout + 31) / 32;
+  const long long total = (long long)cout32 * cin16 * 512 + 2LL * cout32 * 32;
+  long long blocks = (total + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(pn2::mlp_pack_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                     (hipStream_t)stream, weight, bias, bn_scale, bn_shift, cin, cout, cin16,
+                     cout32, packed);
+  PN2_RETURN_LAUNCH();
+}
+
 static int group_mlp_impl(const float* xyz, const float* points, const float* new_xyz,
                           const int32_t* idx, int B, int N, int C, int M, int nsample, int flags,
                           int nlayers, const pn2_mlp_layer* layers, int pool,
@@ -1313,6 +1506,8 @@ static int group_mlp_impl(const float* xyz, const float* points, const float* ne
         return PN2_EINVAL;
       if ((reinterpret_cast<uintptr_t>(qkv[i].packed) & 15) != 0) return PN2_EINVAL;
     }
+    // the query runs on the VALU from the fp32 layout (attn_query): it has no bf16 form
+    if (qkv[0].flags & PN2_MLP_BF16) return PN2_EINVAL;
     if (ns_pad > 128) return PN2_EINVAL;  // one pass: the group's rows all in one workgroup
     prm.attn = 1;
     // column segments of K and V: whole rows when a head spans rows (C <= 4 ns), else blocks
@@ -1342,7 +1537,7 @@ static int group_mlp_impl(const float* xyz, const float* points, const float* ne
   const int P = 32 * R;
   if (qkv) {
     for (int i = 0; i < 3; ++i) {
-      const int cin8 = (qkv[i].cin + 7) / 8, cout32 = qkv[i].cout / 32;
+      const int cin8 = k_chunks(qkv[i]), cout32 = qkv[i].cout / 32;
       const float* base = static_cast<const float*>(qkv[i].packed);
       prm.qkv[i].w = reinterpret_cast<const float4*>(base);
       prm.qkv[i].scale = base + (size_t)cout32 * cin8 * 256;
@@ -1351,6 +1546,7 @@ static int group_mlp_impl(const float* xyz, const float* points, const float* ne
       prm.qkv[i].cout32 = cout32;
       prm.qkv[i].cout = qkv[i].cout;
       prm.qkv[i].relu = 0;
+      prm.qkv[i].bf = (qkv[i].flags & PN2_MLP_BF16) ? 1 : 0;
     }
   }
   prm.xyz = xyz;

@@ -84,11 +84,15 @@ class SemSegModel:
     MLP carries the head: fa_layer4's three layers, then fc1 (128, batch norm, relu) and fc2
     (NUM_CLASSES, no batch norm, no activation) as the 4th and 5th layers of ONE kernel.
     attention=True: the SA layers of pointnet2_sem_seg_attention.py:27-42
-    (pointnet_sa_module_attention: attention + batch norm instead of max pooling)."""
+    (pointnet_sa_module_attention: attention + batch norm instead of max pooling).
+    precision: of the store made here when `params` is None ("fp32" / "bf16", tf_util); a
+    bf16 store packs every layer bf16 but fc2 and the attention's query Dense."""
 
-    def __init__(self, in_channels, params=None, device="cuda", attention=False):
+    def __init__(self, in_channels, params=None, device="cuda", attention=False,
+                 precision="fp32"):
         self.attention = attention
-        self.store = params if params is not None else tf_util.ParamStore(seed=7, device=device)
+        self.store = params if params is not None else tf_util.ParamStore(
+            seed=7, device=device, precision=precision)
         st = self.store
         self.sa, c = [], in_channels
         for i, widths in enumerate(SSG_SA_MLP):
@@ -103,22 +107,25 @@ class SemSegModel:
             layers = tf_util.packed_mlp(st, scopes, cin, widths).layers
             if k == 3:  # + the conv1d head (pointnet2_sem_seg.py:57-60)
                 head1 = tf_util.packed_mlp(st, ["fc1"], widths[-1], [128]).layers
+                # fc2 stays fp32 on a bf16 store (as model_body): a mixed chain
                 head2 = tf_util.packed_mlp(st, ["fc2"], 128, [NUM_CLASSES], bn=False,
-                                           relu=False).layers
+                                           relu=False, precision="fp32").layers
                 layers = layers + head1 + head2
             self.fp.append(tf_util.SharedMLP(layers))
             c2 = widths[-1]
         if attention:  # pack the Dense / batch-norm variables up front (not inside a capture)
             for i, widths in enumerate(SSG_SA_MLP):
                 C, sc = widths[-1], f"layer{i + 1}"
-                for d in attention_layer._attention_scopes(sc):
-                    tf_util.packed_dense(st, d, C, C)
+                for j, d in enumerate(attention_layer._attention_scopes(sc)):
+                    # the query Dense is fp32 at any precision (group_mlp_attention)
+                    tf_util.packed_dense(st, d, C, C, precision="fp32" if j == 0 else None)
                 tf_util.bn_affine(st, f"{sc}/{sc}", C, device)
 
 
-def make_inputs(config, cloud_ids, device, seed=1234, model=False):
+def make_inputs(config, cloud_ids, device, seed=1234, model=False, precision="fp32"):
     """Resident inputs of one step: the synthetic ScanNet crops and the stand-in MLP outputs
-    (or, with model=True, the packed weights of the whole segmentation model)."""
+    (or, with model=True, the packed weights of the whole segmentation model, packed at
+    `precision`)."""
     N, kind, with_feat, attn = CONFIGS[config]
     B = len(cloud_ids)
     xyz, feats = synth.batch(cloud_ids, N, "scannet", with_features=with_feat)
@@ -128,7 +135,8 @@ def make_inputs(config, cloud_ids, device, seed=1234, model=False):
     if model:
         if kind != "ssg":
             raise NotImplementedError("model=True: the SSG segmentation model (cfg2 / cfg3)")
-        inp["model"] = SemSegModel(6 if with_feat else 0, device=device, attention=attn)
+        inp["model"] = SemSegModel(6 if with_feat else 0, device=device, attention=attn,
+                                   precision=precision)
         return inp
     r = lambda shape, slot: _rand_per_cloud(cloud_ids, shape, device, seed, slot)  # noqa: E731
     if kind == "ssg":

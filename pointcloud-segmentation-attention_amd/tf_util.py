@@ -21,6 +21,15 @@ the HIP training layer torch.ops.pn2.mlp_layer_train (csrc/mlp_train.hip) throug
 leaves with gradients, moving averages updated in place on the device. The segmentation head's
 last operations train on csrc/head_train.hip: dropout (tf_util.py:594-612) and
 sparse_softmax_cross_entropy (the tf.losses call of pointnet2_sem_seg.get_loss).
+
+Precision. The packed inference layers are fp32 by default and can be packed for the bf16
+matrix cores instead: ParamStore(precision="bf16") or store.set_precision("bf16") makes every
+packed_mlp / packed_dense of that store bf16 unless the call names a precision itself (the
+models name "fp32" for fc2, whose 21 logits decide the argmax, and for the attention's query
+Dense, which is not matrix-core work). The numerical contract of a bf16 layer is written at
+pn2_mlp_pack_bf16 in include/pn2hip.h: operands rounded to bf16 (nearest even), exact products,
+fp32 sums and fp32 everything else. Training is untouched: is_training=True on a trainable
+store ignores the precision and runs the fp32 training layers.
 """
 import math
 
@@ -28,8 +37,8 @@ import numpy as np
 import torch
 
 from . import _torch_ops
-from ._lib import (PN2_MLP_MAX_LAYERS, PN2_MLP_RELU, InvalidArgumentError, MlpLayer, check,
-                   device_tensor, lib, ptr, stream_of)
+from ._lib import (PN2_MLP_BF16, PN2_MLP_MAX_LAYERS, PN2_MLP_RELU, InvalidArgumentError,
+                   MlpLayer, check, device_tensor, lib, ptr, stream_of)
 
 BN_EPSILON = 1e-3  # tf.contrib.layers.batch_norm's default epsilon
 MOVING_SUFFIXES = ("moving_mean", "moving_variance")  # batch norm's non-trainable variables
@@ -37,15 +46,23 @@ CONV_SUFFIXES = ("weights", "biases", "bn/gamma", "bn/beta", "bn/moving_mean",
                  "bn/moving_variance")
 DENSE_SUFFIXES = ("kernel", "bias")
 BN_SUFFIXES = ("gamma", "beta", "moving_mean", "moving_variance")
+PRECISIONS = ("fp32", "bf16")  # of a packed inference layer (pn2_mlp_pack / pn2_mlp_pack_bf16)
+
+
+def check_precision(precision):
+    if precision not in PRECISIONS:
+        raise InvalidArgumentError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+    return precision
 
 
 class ParamStore(dict):
     """TF variable name -> float32 tensor, with the reference's initialisers for misses."""
 
-    def __init__(self, *args, seed=0, device="cuda", **kw):
+    def __init__(self, *args, seed=0, device="cuda", precision="fp32", **kw):
         super().__init__()
         self.seed = seed
         self.device = device
+        self.precision = check_precision(precision)
         self.is_trainable = False
         self._packed = {}
         self._stamps = {}
@@ -76,6 +93,15 @@ class ParamStore(dict):
         self.is_trainable = True
         for name in list(self):
             self[name] = dict.__getitem__(self, name)
+        self.invalidate()
+        return self
+
+    def set_precision(self, precision):
+        """The precision of the store's packed inference layers from now on: "fp32" (the
+        default) or "bf16" (the opt-in matrix-core mode; see the module docstring). Drops the
+        packed copies, so the next call packs again. Training (is_training=True) ignores it.
+        Returns the store."""
+        self.precision = check_precision(precision)
         self.invalidate()
         return self
 
@@ -169,10 +195,13 @@ def default_store():
 
 
 class PackedLayer:
-    """One conv layer in pn2_mlp_pack's layout (device buffer) + its struct pn2_mlp_layer."""
+    """One conv layer in pn2_mlp_pack's layout, or with precision="bf16" in
+    pn2_mlp_pack_bf16's (device buffer) + its struct pn2_mlp_layer."""
 
     def __init__(self, weights, biases=None, gamma=None, beta=None, moving_mean=None,
-                 moving_variance=None, relu=True, eps=BN_EPSILON, device="cuda"):
+                 moving_variance=None, relu=True, eps=BN_EPSILON, device="cuda",
+                 precision="fp32"):
+        self.precision = check_precision(precision)
         # a trainable store's variables are packed by value (no autograd through the packing)
         weights, biases, gamma, beta, moving_mean, moving_variance = (
             v.detach() if isinstance(v, torch.Tensor) else v
@@ -197,15 +226,19 @@ class PackedLayer:
             s64 = g / torch.sqrt(var + eps)
             scale = s64.to(torch.float32).to(dev).contiguous()
             shift = (bt - mean * s64).to(torch.float32).to(dev).contiguous()
-        nbytes = int(lib().pn2_mlp_packed_size(self.cin, self.cout))
+        bf16 = self.precision == "bf16"
+        size, pack = ((lib().pn2_mlp_packed_size_bf16, lib().pn2_mlp_pack_bf16) if bf16 else
+                      (lib().pn2_mlp_packed_size, lib().pn2_mlp_pack))
+        nbytes = int(size(self.cin, self.cout))
         self.buf = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
-        check(lib().pn2_mlp_pack(ptr(w), ptr(b), ptr(scale), ptr(shift), self.cin, self.cout,
-                                 ptr(self.buf), nbytes, stream_of(self.buf)), "mlp_pack")
+        check(pack(ptr(w), ptr(b), ptr(scale), ptr(shift), self.cin, self.cout, ptr(self.buf),
+                   nbytes, stream_of(self.buf)), "mlp_pack_bf16" if bf16 else "mlp_pack")
         self.scale, self.shift, self.bias = scale, shift, b  # kept for the training path
 
     def struct(self):
         return MlpLayer(self.buf.data_ptr(), self.cin, self.cout,
-                        PN2_MLP_RELU if self.relu else 0)
+                        (PN2_MLP_RELU if self.relu else 0) |
+                        (PN2_MLP_BF16 if self.precision == "bf16" else 0))
 
 
 class SharedMLP:
@@ -239,10 +272,12 @@ class SharedMLP:
         return out
 
 
-def packed_mlp(store, scopes, cin, widths, bn=True, relu=True):
+def packed_mlp(store, scopes, cin, widths, bn=True, relu=True, precision=None):
     """SharedMLP over the store's variables for conv scopes `scopes` (one per width), cached
-    per scope tuple. `relu` applies to every layer (tf_util.conv2d's activation_fn)."""
-    key = (tuple(scopes), cin, tuple(widths), bn, relu)
+    per scope tuple. `relu` applies to every layer (tf_util.conv2d's activation_fn), and so
+    does `precision` ("fp32" / "bf16"; None: the store's)."""
+    precision = check_precision(store.precision if precision is None else precision)
+    key = (tuple(scopes), cin, tuple(widths), bn, relu, precision)
 
     def make():
         layers, c = [], cin
@@ -250,20 +285,23 @@ def packed_mlp(store, scopes, cin, widths, bn=True, relu=True):
             p = store.conv(scope, c, w, bn=bn)
             layers.append(PackedLayer(p["weights"], p["biases"], p.get("gamma"), p.get("beta"),
                                       p.get("moving_mean"), p.get("moving_variance"), relu=relu,
-                                      device=store.device))
+                                      device=store.device, precision=precision))
             c = w
         return SharedMLP(layers)
 
     return store.cached(key, scopes, CONV_SUFFIXES, make)
 
 
-def packed_dense(store, scope, cin, cout):
-    """SharedMLP of one tf.layers.Dense (no activation) over the store's variables, cached."""
-    key = ("dense", scope, cin, cout)
+def packed_dense(store, scope, cin, cout, precision=None):
+    """SharedMLP of one tf.layers.Dense (no activation) over the store's variables, cached.
+    `precision`: "fp32" / "bf16"; None: the store's."""
+    precision = check_precision(store.precision if precision is None else precision)
+    key = ("dense", scope, cin, cout, precision)
 
     def make():
         p = store.dense(scope, cin, cout)
-        return SharedMLP([PackedLayer(p["weights"], p["biases"], relu=False, device=store.device)])
+        return SharedMLP([PackedLayer(p["weights"], p["biases"], relu=False, device=store.device,
+                                      precision=precision)])
 
     return store.cached(key, [scope], DENSE_SUFFIXES, make)
 
@@ -283,11 +321,13 @@ def bn_affine(store, scope, c, device):
 
 def conv2d(inputs, num_output_channels, kernel_size, scope, stride=[1, 1], padding='SAME',
            data_format='NHWC', use_xavier=True, stddev=1e-3, weight_decay=None,
-           activation_fn=torch.relu, bn=False, bn_decay=None, is_training=None, params=None):
+           activation_fn=torch.relu, bn=False, bn_decay=None, is_training=None, params=None,
+           precision=None):
     """tf_util.conv2d (tf_util.py:120-185) for the 1x1 kernels PointNet++ uses, NHWC.
     Extra keyword `params`: the ParamStore (default: default_store()). is_training=True needs a
     trainable store (ParamStore.trainable()) and runs mlp_train: batch-statistics batch norm,
-    gradients for the input and every variable."""
+    gradients for the input and every variable. Extra keyword `precision`: of the packed
+    inference layer ("fp32" / "bf16"; None: the store's); the training layer is fp32."""
     if list(kernel_size) != [1, 1] or list(stride) != [1, 1] or data_format != 'NHWC':
         raise NotImplementedError("pn2hip's conv2d is the 1x1 NHWC shared MLP of PointNet++")
     store = params if params is not None else default_store()
@@ -302,19 +342,20 @@ def conv2d(inputs, num_output_channels, kernel_size, scope, stride=[1, 1], paddi
                               bn=bn, relu=activation_fn is not None)
         return mlp_train(inputs, layers, bn_decay)
     mlp = packed_mlp(store, [scope], int(inputs.shape[-1]), [num_output_channels], bn=bn,
-                     relu=activation_fn is not None)
+                     relu=activation_fn is not None, precision=precision)
     return mlp(inputs)
 
 
 def conv1d(inputs, num_output_channels, kernel_size, scope, stride=1, padding='SAME',
            data_format='NHWC', use_xavier=True, stddev=1e-3, weight_decay=None,
-           activation_fn=torch.relu, bn=False, bn_decay=None, is_training=None, params=None):
+           activation_fn=torch.relu, bn=False, bn_decay=None, is_training=None, params=None,
+           precision=None):
     """tf_util.conv1d (tf_util.py:52-117) with kernel 1 (the segmentation heads' fc layers)."""
     if kernel_size != 1 or stride != 1:
         raise NotImplementedError("pn2hip's conv1d is the kernel-1 per-point layer")
     return conv2d(inputs, num_output_channels, [1, 1], scope, data_format=data_format,
                   activation_fn=activation_fn, bn=bn, bn_decay=bn_decay,
-                  is_training=is_training, params=params)
+                  is_training=is_training, params=params, precision=precision)
 
 
 def mlp_torch(x, layers, is_training=False, bn_decay=None):

@@ -3,10 +3,14 @@
 (stack.SemSegModel, B clouds), one layer at a time on an otherwise idle GPU.
 
     python tools/bench_mlp.py [--batch 16] [--iters 20] [--lib path/to/libpn2hip.so]
+                              [--precision {fp32,bf16}] [--repeats 1]
 
 Prints one JSON line per layer: time per launch, the matrix-core FLOPs it does (padded to
 the kernel's tiles: 32 output columns, 8 input features) and the fraction of the fp32 MFMA
-peak (157.3 TFLOP/s, MI355X_MICROARCH.md).
+peak (157.3 TFLOP/s, MI355X_MICROARCH.md; the same yardstick at either precision, so the
+lines compare). --precision bf16 packs the model as a bf16 ParamStore does (tf_util: every
+layer but fc2 and the attention's query Dense). --repeats N times every layer N times and
+prints the median with the spread (min, max).
 """
 import argparse
 import importlib
@@ -25,6 +29,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--lib", default=None)
     ap.add_argument("--config", default="cfg2", choices=["cfg2", "cfg3"])
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"])
+    ap.add_argument("--repeats", type=int, default=1)
     args = ap.parse_args()
     if args.lib:
         os.environ["PN2HIP_LIB"] = args.lib
@@ -33,7 +39,8 @@ def main():
     S, pu = pkg.stack, pkg.pointnet_util
     dev = torch.device("cuda:0")
     B = args.batch
-    inp = S.make_inputs(args.config, list(range(B)), dev, model=True)
+    kw = {"precision": args.precision} if args.precision != "fp32" else {}  # (older libraries)
+    inp = S.make_inputs(args.config, list(range(B)), dev, model=True, **kw)
     mdl = inp["model"]
     xyz = [inp["xyz"]]
     for (m, _, _, _) in S.SSG_SA:
@@ -50,17 +57,25 @@ def main():
             f += 2 * rows * ((L.cin + 7) // 8 * 8) * ((L.cout + 31) // 32 * 32)
         return f
 
+    spread = {}
+
     def timeit(fn):
         for _ in range(3):
             fn()
         torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / args.iters * 1e3  # us
+        us = []
+        for _ in range(max(1, args.repeats)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) / args.iters * 1e3)
+        us.sort()
+        med = us[len(us) // 2]
+        spread[med] = (us[0], us[-1])
+        return med  # us
 
     rows_out = []
     pts = [inp["feats"]] + [feats(m, c) for (m, _, _, c) in S.SSG_SA]
@@ -86,9 +101,13 @@ def main():
         p2 = feats(int(xyz[lvl].shape[1]), mlp.cout if k < 3 else 128)
     tot_us = sum(r[1] for r in rows_out)
     for name, us, fl in rows_out:
-        print(json.dumps({"layer": name, "us": round(us, 1), "tflops": round(fl / us / 1e6, 1),
-                          "frac_fp32_mfma": round(fl / us / 1e6 / PEAK_TFLOPS, 3)}))
-    print(json.dumps({"total_us": round(tot_us, 1), "batch": B}))
+        line = {"layer": name, "us": round(us, 1), "tflops": round(fl / us / 1e6, 1),
+                "frac_fp32_mfma": round(fl / us / 1e6 / PEAK_TFLOPS, 3)}
+        if args.repeats > 1:
+            line["us_min"], line["us_max"] = (round(v, 1) for v in spread[us])
+        print(json.dumps(line))
+    print(json.dumps({"total_us": round(tot_us, 1), "batch": B, "config": args.config,
+                      "precision": args.precision}))
 
 
 if __name__ == "__main__":
