@@ -13,6 +13,8 @@ import math
 
 import numpy as np
 
+from support import raw_bits as bits  # noqa: F401  (used as oc.bits)
+
 CHUNK = 2048   # PN2_ADAM_CHUNK (the tests assert it against _lib)
 SLOTS = 64     # PN2_ADAM_SLOTS
 SIZES = (1, 3, 4, 5, CHUNK - 1, CHUNK, CHUNK + 1, 2 * CHUNK + 3)
@@ -108,10 +110,6 @@ def cycle_sizes(nslots, zero_at=None):
     if zero_at is not None:
         sizes[zero_at] = 0
     return sizes
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def confusion_inputs(rng, rows, C):

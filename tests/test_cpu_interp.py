@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import PKG_NAME
+from support import f32_bits
 
 pytestmark = pytest.mark.filterwarnings("ignore::UserWarning")
 
@@ -24,10 +25,6 @@ def env():
     except RuntimeError as e:  # the torch-linked library is part of the build
         pytest.fail(str(e))
     return pkg, O
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 def _clouds(kind, B, n, seed):
@@ -53,10 +50,10 @@ def test_three_nn_host(env, kind, B, n, m):
         return
     rd, ri = O.three_nn(x1, x2)
     assert np.array_equal(i.numpy(), ri)
-    assert np.array_equal(_bits(d.numpy()), _bits(rd))
+    assert np.array_equal(f32_bits(d.numpy()), f32_bits(rd))
     if O.have_ref_cpu():  # the reference's threenn_cpu itself
         fd, fi = O.ref_three_nn(x1, x2)
-        assert np.array_equal(i.numpy(), fi) and np.array_equal(_bits(d.numpy()), _bits(fd))
+        assert np.array_equal(i.numpy(), fi) and np.array_equal(f32_bits(d.numpy()), f32_bits(fd))
 
 
 @pytest.mark.parametrize("B,m,n,C", [(2, 64, 256, 16), (1, 3, 10, 1), (2, 128, 1024, 131),
@@ -70,20 +67,20 @@ def test_three_interpolate_host_and_grad(env, B, m, n, C):
     w = rng.random((B, n, 3)).astype(np.float32)
     out = pkg.tf_interpolate.three_interpolate(torch.from_numpy(pts), torch.from_numpy(idx),
                                                torch.from_numpy(w))
-    assert np.array_equal(_bits(out.numpy()), _bits(O.three_interpolate(pts, idx, w)))
+    assert np.array_equal(f32_bits(out.numpy()), f32_bits(O.three_interpolate(pts, idx, w)))
     go = rng.standard_normal((B, n, C)).astype(np.float32)
     g = pkg.tf_interpolate.three_interpolate_grad(torch.from_numpy(pts), torch.from_numpy(idx),
                                                   torch.from_numpy(w), torch.from_numpy(go))
     if O.have_ref_cpu():  # the reference's own loops: same values and same summation order
-        assert np.array_equal(_bits(out.numpy()), _bits(O.ref_three_interpolate(pts, idx, w)))
-        assert np.array_equal(_bits(g.numpy()), _bits(O.ref_three_interpolate_grad(m, idx, w, go)))
+        assert np.array_equal(f32_bits(out.numpy()), f32_bits(O.ref_three_interpolate(pts, idx, w)))
+        assert np.array_equal(f32_bits(g.numpy()), f32_bits(O.ref_three_interpolate_grad(m, idx, w, go)))
     np.testing.assert_allclose(g.numpy(), O.three_interpolate_grad(m, idx, w, go),
                                rtol=1e-5, atol=1e-5)
     # autograd w.r.t. points (tf_interpolate.py:29-34) runs the CPU gradient kernel
     p = torch.from_numpy(pts).requires_grad_(True)
     pkg.tf_interpolate.three_interpolate(p, torch.from_numpy(idx), torch.from_numpy(w)).backward(
         torch.from_numpy(go))
-    assert np.array_equal(_bits(p.grad.numpy()), _bits(g.numpy()))
+    assert np.array_equal(f32_bits(p.grad.numpy()), f32_bits(g.numpy()))
 
 
 def test_host_errors(env):

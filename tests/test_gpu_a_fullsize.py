@@ -24,10 +24,10 @@ import os
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, gpu_available
+from conftest import PKG_NAME
+from support import clouds, f32_bits, gpu_marks
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
 TOL = dict(rtol=1e-5, atol=1e-5)
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -43,16 +43,12 @@ def env():
     return pkg, O, torch, torch.device("cuda:0")
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
-
-
 def _exact(name, got, want):
     assert got.shape == want.shape, (name, got.shape, want.shape)
     if got.dtype == np.int32 or want.dtype == np.int32:
         bad = got != want
     else:
-        bad = _bits(got) != _bits(want)
+        bad = f32_bits(got) != f32_bits(want)
     assert not bad.any(), f"{name}: {int(bad.sum())} of {bad.size} values differ (bit-exact bar)"
 
 
@@ -260,22 +256,6 @@ def test_step_three_nn(env, config):
         _exact(f"nn{k + 1}.dist", d.cpu().numpy(), rd)
 
 
-def _cloud(pkg, kind, B, N, seed=0):
-    if kind in ("scannet", "uniform"):
-        return pkg.synth.batch(range(seed, seed + B), N, kind)[0]
-    if kind == "dup":  # every point the same: all distances tie
-        return np.tile(np.array([[0.25, 0.5, 0.75]], np.float32), (B, N, 1)).reshape(B, N, 3)
-    if kind == "grid":  # integer lattice: massive exact ties
-        g = np.stack(np.meshgrid(*[np.arange(16)] * 3, indexing="ij"), -1).reshape(-1, 3)
-        rng = np.random.default_rng(seed)
-        return np.stack([g[rng.integers(0, len(g), N)] for _ in range(B)]).astype(np.float32)
-    if kind == "fewuniq":  # 300 distinct points drawn with replacement: npoint > #unique
-        rng = np.random.default_rng(seed)
-        u = rng.random((300, 3)).astype(np.float32)
-        return np.stack([u[rng.integers(0, 300, N)] for _ in range(B)])
-    raise ValueError(kind)
-
-
 # SA1-size clouds (4096 < N <= 8192) run the culled hot-set sampler by default; every schedule
 # pn2_fps_gather_sched offers there (PN2_FPS_AUTO, PN2_FPS_BLOCKSCAN = the v9 block scan)
 # must give the oracle's
@@ -312,7 +292,7 @@ def _sched(pkg, torch, x, M, sched):
                          + [(s,) + c for s in (0, 1) for c in MSG_SAMPLER_CASES])
 def test_fps_sampler_schedules(env, sched, kind, B, N, M):
     pkg, O, torch, dev = env
-    x = _cloud(pkg, kind, B, N, seed=3)
+    x = clouds(pkg, kind, B, N, seed=3)
     rc, idx, new_xyz = _sched(pkg, torch, torch.from_numpy(x).to(dev), M, sched)
     assert rc == 0, rc
     torch.cuda.synchronize()
@@ -328,7 +308,7 @@ def test_fps_schedule_rejections(env):
     lean schedules, 6-8), never a silent fallback."""
     pkg, O, torch, dev = env
     L = pkg._lib
-    x = torch.from_numpy(_cloud(pkg, "scannet", 1, 16384)).to(dev)
+    x = torch.from_numpy(clouds(pkg, "scannet", 1, 16384)).to(dev)
     for gone in (6, 7, 8):
         assert _sched(pkg, torch, x[:, :8192].contiguous(), 64, gone)[0] == L.PN2_EINVAL
     assert _sched(pkg, torch, x[:, :4096].contiguous(), 64, L.PN2_FPS_BLOCKSCAN)[0] == L.PN2_EINVAL
@@ -351,7 +331,7 @@ def test_fps_poll_bound_reports_fault(env):
     for name in ("pn2_fps_gather", "pn2_fault_status"):
         fn = getattr(h, name)
         fn.restype, fn.argtypes = pkg._lib.SIGNATURES[name]
-    x = torch.from_numpy(_cloud(pkg, "scannet", 4, 8192)).to(dev)
+    x = torch.from_numpy(clouds(pkg, "scannet", 4, 8192)).to(dev)
     idx = torch.empty((4, 1024), dtype=torch.int32, device=dev)
     nx = torch.empty((4, 1024, 3), dtype=torch.float32, device=dev)
     st = torch.cuda.current_stream().cuda_stream
@@ -392,7 +372,7 @@ def test_fps_chain_poll_bound_reports_fault(env):
     for name in ("pn2_fps_chain", "pn2_fault_status"):
         fn = getattr(h, name)
         fn.restype, fn.argtypes = pkg._lib.SIGNATURES[name]
-    x = _cloud(pkg, "scannet", 2, 1024)
+    x = clouds(pkg, "scannet", 2, 1024)
     rc, outs = _chain_call(h, torch.from_numpy(x).to(dev), [256, 64], dev, torch)
     assert rc == 0
     torch.cuda.synchronize()
@@ -424,7 +404,7 @@ def test_publish_tag_check_catches_torn_reads(env):
     st = torch.cuda.current_stream().cuda_stream
     h.pn2_torn_reads()  # (clear)
     # the SA1 sampler
-    x = _cloud(pkg, "scannet", 8, 8192, seed=5)
+    x = clouds(pkg, "scannet", 8, 8192, seed=5)
     xt = torch.from_numpy(x).to(dev)
     idx = torch.empty((8, 1024), dtype=torch.int32, device=dev)
     nx = torch.empty((8, 1024, 3), dtype=torch.float32, device=dev)
@@ -436,7 +416,7 @@ def test_publish_tag_check_catches_torn_reads(env):
     _exact("torn-build SA1 new_xyz", nx.cpu().numpy(), O.gather_point(x, ref))
     # the chain (1,024 -> 256 -> 64 -> 16) over a raw cloud: over the SA1 picks its stages
     # would be prefixes (fps_chain_prefix_kernel) and no stage would sample
-    nx1 = _cloud(pkg, "scannet", 8, 1024, seed=6)
+    nx1 = clouds(pkg, "scannet", 8, 1024, seed=6)
     rc, outs = _chain_call(h, torch.from_numpy(nx1).to(dev), [256, 64, 16], dev, torch)
     assert rc == 0
     torch.cuda.synchronize()
@@ -476,7 +456,7 @@ def test_chain_over_sampler_output_is_prefix(env):
     samplers stage by stage, on ScanNet and uniform clouds (and the property itself holds)."""
     pkg, O, torch, dev = env
     for kind in ("scannet", "uniform"):
-        x = _cloud(pkg, kind, 4, 8192, seed=11)
+        x = clouds(pkg, kind, 4, 8192, seed=11)
         nx1 = O.gather_point(x, O.fps(x, 1024))
         refs = _chain_vs_oracle(pkg, O, torch, dev, nx1, [256, 64, 16], f"{kind} prefix chain")
         for r, m in zip(refs, [256, 64, 16]):
@@ -492,7 +472,7 @@ def test_chain_prefix_check_rejects(env):
     to the other point); a tie in the stage's last step; duplicates of pick 0 -- must fail the
     check and run the stages as samplers: exact against the oracle."""
     pkg, O, torch, dev = env
-    x = _cloud(pkg, "scannet", 4, 8192, seed=12)
+    x = clouds(pkg, "scannet", 4, 8192, seed=12)
     nx1 = O.gather_point(x, O.fps(x, 1024))
     cases = {}
     p = nx1.copy(); p[:, [100, 101]] = p[:, [101, 100]]; cases["swap 100/101"] = p

@@ -8,7 +8,7 @@ first sample that attains it, bn_train the bits of mlp_layer_train with an ident
 
 Backward: torch autograd on the CPU over the plain formulas (Dense, reshape(G, C/4, ns, 4),
 scores / 2, softmax, weighted sum; the pool as a gather at the `arg` of the forward under test),
-evaluated in float64 and in float32. Tolerance, the project's (test_gpu_mlp_train_pool.py):
+evaluated in float64 and in float32. Tolerance, the project's (tests/support.py):
 
     max |gpu - f64|  <=  max(4 * max |fp32 - f64|,  1e-6 * (1 + max |f64|))
 
@@ -27,10 +27,10 @@ import importlib
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, gpu_available
+from conftest import PKG_NAME
+from support import assert_close, gpu_marks, tolerance
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
 EPS = 1e-3
 
@@ -60,23 +60,6 @@ def env():
     pkg = importlib.import_module(PKG_NAME)
     import pn2hip
     return pkg, pn2hip.ops, torch, torch.device("cuda:0")
-
-
-def tolerance(ref64, ref32):
-    err32 = np.abs(ref32 - ref64).max() if ref64.size else 0.0
-    return max(4 * err32, 1e-6 * (1 + (np.abs(ref64).max() if ref64.size else 0.0))), err32
-
-
-def assert_close(got, ref64, ref32, what):
-    got = np.asarray(got.detach().cpu().numpy(), np.float64)
-    ref64 = ref64.detach().numpy()
-    ref32 = np.asarray(ref32.detach().numpy(), np.float64)
-    assert got.shape == ref64.shape, (what, got.shape, ref64.shape)
-    assert np.isfinite(got).all(), f"{what}: non-finite values"
-    err = np.abs(got - ref64).max() if got.size else 0.0
-    tol, err32 = tolerance(ref64, ref32)
-    print(f"{what}: err {err:.3g} tol {tol:.3g} (fp32 err {err32:.3g})")
-    assert err <= tol, f"{what}: max err {err:.3g} > tol {tol:.3g} (fp32 cpu err {err32:.3g})"
 
 
 def make_params(torch, G, ns, C, seed):
@@ -201,7 +184,7 @@ def test_reduction_gradient_c_abi(env, case):
     for name, n, o, a, b in zip(("grad_Q", "grad_K", "grad_V"), new, old, r64, r32):
         assert_close(n, a, b, name)
         assert_close(o[0], a, b, name + " (attn_reduce_grad)")
-        tol, _ = tolerance(a.numpy(), np.asarray(b.numpy(), np.float64))
+        tol, _ = tolerance(a, b)
         diff = float((n - o[0]).abs().max())
         assert diff <= 2 * tol, f"{name}: the two kernels differ by {diff:.3g} > {2 * tol:.3g}"
 

@@ -5,10 +5,10 @@ import importlib
 
 import pytest
 
-from conftest import PKG_NAME, gpu_available
+from conftest import PKG_NAME
+from support import gpu_marks
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
 
 @pytest.fixture(scope="module")

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import feed_cases as fc
+import support
 
 pytestmark = pytest.mark.gpu
 
@@ -33,7 +34,7 @@ def same_bits(torch, got, want):
     for k, (g, w) in enumerate(zip(got, want)):
         assert g.is_cuda and not w.is_cuda, k
         assert (g.shape, g.dtype) == (w.shape, w.dtype), k
-        assert np.array_equal(fc.bits(g.cpu().numpy()), fc.bits(w.numpy())), k
+        support.same_bits(g, w, k)
 
 
 # ------------------------------------------------------------------ feed_batch

@@ -12,10 +12,10 @@ import importlib
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, gpu_available
+from conftest import PKG_NAME
+from support import f32_bits, gpu_marks
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
 
 @pytest.fixture(scope="module")
@@ -26,10 +26,6 @@ def env():
     O.set_threads(16)
     pkg = importlib.import_module(PKG_NAME)
     return pkg, O, torch, torch.device("cuda:0")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 def _layer(pkg, O, kind, B, N, M, C, seed):
@@ -85,9 +81,9 @@ def test_ball_group_layers(env, li, use_xyz, xyz_last, want_gx):
         idx, cnt, new_points = out[:3]
         assert np.array_equal(cnt.cpu().numpy(), rcnt)
         assert np.array_equal(idx.cpu().numpy(), ridx)
-        assert np.array_equal(_bits(new_points.cpu().numpy()), _bits(rnp))
+        assert np.array_equal(f32_bits(new_points.cpu().numpy()), f32_bits(rnp))
         if want_gx:
-            assert np.array_equal(_bits(out[3].cpu().numpy()), _bits(rgx)), "grouped_xyz"
+            assert np.array_equal(f32_bits(out[3].cpu().numpy()), f32_bits(rgx)), "grouped_xyz"
 
 
 def test_ball_group_layers_rejects(env):
@@ -152,7 +148,7 @@ def test_ball_group_xyz(env, kind, B, N, M, r, ns):
     rg, _ = O.group_concat(x, None, q, ridx)
     assert np.array_equal(cnt.cpu().numpy(), rcnt)
     assert np.array_equal(idx.cpu().numpy(), ridx)
-    assert np.array_equal(_bits(grouped.cpu().numpy()), _bits(rg))
+    assert np.array_equal(f32_bits(grouped.cpu().numpy()), f32_bits(rg))
 
 
 GROUP_RADII_CASES = [
@@ -180,7 +176,7 @@ def test_ball_group_xyz_radii(env, kind, B, N, M, radii, nss, edge):
         rg, _ = O.group_concat(x, None, q, ridx)
         assert np.array_equal(cnt.cpu().numpy(), rcnt)
         assert np.array_equal(idx.cpu().numpy(), ridx)
-        assert np.array_equal(_bits(grouped.cpu().numpy()), _bits(rg))
+        assert np.array_equal(f32_bits(grouped.cpu().numpy()), f32_bits(rg))
         one = pkg.pointnet_util.ball_group_xyz(r, ns, xt, qt, grid)
         assert torch.equal(one[0], idx) and torch.equal(one[1], cnt)
         assert torch.equal(one[2].view(torch.int32), grouped.view(torch.int32))
@@ -212,10 +208,10 @@ def test_ball_group_features(env, kind, B, N, M, C, r, ns, xyz_last):
     rnp, _ = O.group_concat(x, p, q, ridx, use_xyz=True, xyz_last=xyz_last)
     assert np.array_equal(cnt.cpu().numpy(), rcnt)
     assert np.array_equal(idx.cpu().numpy(), ridx)
-    assert np.array_equal(_bits(new_points.cpu().numpy()), _bits(rnp))
+    assert np.array_equal(f32_bits(new_points.cpu().numpy()), f32_bits(rnp))
     i0, c0, g0 = pkg.pointnet_util.ball_group(r, ns, xt, None, qt, grid)
     rg, _ = O.group_concat(x, None, q, ridx)
-    assert torch.equal(i0, idx) and np.array_equal(_bits(g0.cpu().numpy()), _bits(rg))
+    assert torch.equal(i0, idx) and np.array_equal(f32_bits(g0.cpu().numpy()), f32_bits(rg))
 
 
 def test_ball_group_rejects(env):

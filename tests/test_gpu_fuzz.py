@@ -10,16 +10,12 @@ import importlib
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, gpu_available
+from conftest import PKG_NAME
+from support import f32_bits, gpu_marks
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
 CASES = 48
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 @pytest.fixture(scope="module")
@@ -60,21 +56,21 @@ def test_random_sa_fp_layer_vs_oracle(env, seed):
     idx, new_xyz = pkg.tf_sampling.farthest_point_sample_and_gather(M, T(xyz))
     assert np.array_equal(idx.cpu().numpy(), fidx), what
     ref_new = O.gather_point(xyz, fidx)
-    assert np.array_equal(_bits(new_xyz.cpu().numpy()), _bits(ref_new)), what
+    assert np.array_equal(f32_bits(new_xyz.cpu().numpy()), f32_bits(ref_new)), what
     bidx, cnt = pkg.tf_grouping.query_ball_point(radius, ns, T(xyz), new_xyz)
     ridx, rcnt = O.ball_query(xyz, ref_new, radius, ns)
     assert np.array_equal(cnt.cpu().numpy(), rcnt), what
     assert np.array_equal(bidx.cpu().numpy(), ridx), what
     got, gxyz = pkg.pointnet_util.group_concat(T(xyz), T(pts), new_xyz, bidx)
     rgot, rgxyz = O.group_concat(xyz, pts, ref_new, ridx)
-    assert np.array_equal(_bits(got.cpu().numpy()), _bits(rgot)), what
-    assert np.array_equal(_bits(gxyz.cpu().numpy()), _bits(rgxyz)), what
+    assert np.array_equal(f32_bits(got.cpu().numpy()), f32_bits(rgot)), what
+    assert np.array_equal(f32_bits(gxyz.cpu().numpy()), f32_bits(rgxyz)), what
 
     # FP: the sampled level back onto the cloud (three_nn + IDW + interpolate + concat)
     C2 = int(rng.choice([3, 16, 64]))
     p2 = rng.uniform(-1, 1, (B, M, C2)).astype(np.float32)
     out = pkg.pointnet_util.fp_interpolate(T(xyz), new_xyz, T(pts), T(p2))
-    assert np.array_equal(_bits(out.cpu().numpy()), _bits(O.fp_fused(xyz, ref_new, pts, p2))), what
+    assert np.array_equal(f32_bits(out.cpu().numpy()), f32_bits(O.fp_fused(xyz, ref_new, pts, p2))), what
 
 
 @pytest.mark.parametrize("seed", range(16))
@@ -95,7 +91,7 @@ def test_random_knn_and_grads_vs_oracle(env, seed):
     val, idx = pkg.tf_grouping.knn_point(k, T(xyz1), T(xyz2))
     rval, ridx = O.knn_point(k, xyz1, xyz2)
     assert np.array_equal(idx.cpu().numpy(), ridx), what
-    assert np.array_equal(_bits(val.cpu().numpy()), _bits(rval)), what
+    assert np.array_equal(f32_bits(val.cpu().numpy()), f32_bits(rval)), what
 
     C = int(rng.choice([3, 8, 64]))
     pts = T(rng.uniform(-1, 1, (B, n, C)).astype(np.float32))

@@ -11,7 +11,7 @@ so the sign of an untouched row is checked on the bit patterns as well).
                                   reference's CPU loop, tf_interpolate.cpp:131-153)
   the ops                         forward against the fused no-grad kernels; gradients against
                                   the `_grad` ops (bits) and against a float64 evaluation with
-                                  the project's tolerance (tests/test_gpu_mlp_train.py):
+                                  the project's tolerance (tests/support.py):
       max |gpu - f64|  <=  max(4 * max |fp32 - f64|,  1e-6 * (1 + max |f64|))
                                   where fp32 is the old composition's float-atomic gradient
   launch limits                   one case on each side of PN2_INV_MAX_KEYS, PN2_INV_MAX_SLOTS
@@ -26,10 +26,10 @@ import importlib
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, gpu_available
+from conftest import PKG_NAME
+from support import assert_close, gpu_marks
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
 E = -22
 MAX_KEYS, MAX_SLOTS, MAX_BATCH = 16384, 1 << 20, 65535  # include/pn2hip.h
@@ -41,19 +41,6 @@ def env():
     pkg = importlib.import_module(PKG_NAME)
     import pn2hip
     return pkg, pn2hip.ops, torch, torch.device("cuda:0")
-
-
-def assert_close(got, ref64, ref32, what):
-    """tests/test_gpu_mlp_train.py assert_close, on numpy arrays."""
-    got = np.asarray(got, np.float64)
-    ref32 = np.asarray(ref32, np.float64)
-    assert got.shape == ref64.shape, (what, got.shape, ref64.shape)
-    assert np.isfinite(got).all(), f"{what}: non-finite values"
-    err = np.abs(got - ref64).max() if got.size else 0.0
-    err32 = np.abs(ref32 - ref64).max() if got.size else 0.0
-    tol = max(4 * err32, 1e-6 * (1 + (np.abs(ref64).max() if got.size else 0.0)))
-    print(f"{what}: err {err:.3g} tol {tol:.3g} (fp32 err {err32:.3g})")
-    assert err <= tol, f"{what}: max err {err:.3g} > tol {tol:.3g} (fp32 err {err32:.3g})"
 
 
 def bits_equal(a, b):

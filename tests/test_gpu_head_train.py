@@ -5,7 +5,7 @@ Dropout is compared bit for bit with the host twin pn2cpu_dropout (which
 tests/test_head_train_cpu.py ties to a numpy restatement of Philox4x32-10 and to Random123's
 known answers). The loss is compared with the float64 formula lse - z[label] under TF's
 SUM_BY_NONZERO_WEIGHTS reduction and its autograd (head_train_ref.xent_ref). Tolerance (the
-project's, tests/test_gpu_mlp_train.py):
+project's, tests/support.py):
 
     max |gpu - f64|  <=  max(4 * max |fp32 - f64|,  1e-6 * (1 + max |f64|))
 
@@ -17,11 +17,11 @@ import importlib
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, gpu_available
+from conftest import PKG_NAME
 from head_train_ref import xent_ref
+from support import assert_close, gpu_marks, raw_bits
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
 BLOCK = 128  # PN2_XENT_BLOCK_ROWS (include/pn2hip.h)
 XENT_C = [1, 2, 21, 50, 64, 65, 200]   # both layouts, the even-C padding, the boundary
@@ -39,19 +39,6 @@ def env():
     return pkg, pn2hip.ops, torch, torch.device("cuda:0")
 
 
-def assert_close(got, ref64, ref32, what):
-    got = np.asarray(got.detach().cpu().numpy(), np.float64)
-    ref64 = ref64.detach().numpy()
-    ref32 = np.asarray(ref32.detach().numpy(), np.float64)
-    assert got.shape == ref64.shape, (what, got.shape, ref64.shape)
-    assert np.isfinite(got).all(), f"{what}: non-finite values"
-    err = np.abs(got - ref64).max() if got.size else 0.0
-    err32 = np.abs(ref32 - ref64).max() if got.size else 0.0
-    tol = max(4 * err32, 1e-6 * (1 + (np.abs(ref64).max() if got.size else 0.0)))
-    print(f"{what}: err {err:.3g} tol {tol:.3g} (fp32 err {err32:.3g})")
-    assert err <= tol, f"{what}: max err {err:.3g} > tol {tol:.3g} (fp32 cpu err {err32:.3g})"
-
-
 # ------------------------------------------------------------------------------ dropout
 def cpu_dropout(pkg, x_np, keep, seed):
     out = np.empty_like(x_np)
@@ -65,10 +52,6 @@ def drop_input(n):
     return x
 
 
-def bits(t):
-    return t.detach().cpu().numpy().view(np.uint32)
-
-
 @pytest.mark.parametrize("keep", DROP_KEEP)
 @pytest.mark.parametrize("n", DROP_N)
 def test_dropout_equals_the_host_twin(env, n, keep):
@@ -78,20 +61,20 @@ def test_dropout_equals_the_host_twin(env, n, keep):
     x = torch.from_numpy(x_np).to(dev)
     assert x.data_ptr() % 16 == 0
     out = ops.dropout(x, keep, SEED)
-    assert np.array_equal(bits(out), ref.view(np.uint32))
+    assert np.array_equal(raw_bits(out), ref.view(np.uint32))
     # a view whose storage starts one float into an allocation: the scalar path
     base = torch.empty(n + 1, device=dev)
     view = base[1:]
     view.copy_(x)
     assert view.is_contiguous() and view.data_ptr() % 16 == 4
-    assert np.array_equal(bits(ops.dropout(view, keep, SEED)), ref.view(np.uint32))
+    assert np.array_equal(raw_bits(ops.dropout(view, keep, SEED)), ref.view(np.uint32))
     # in place through the C ABI, aligned and not
     for t in (x.clone(), view):
         rc = pkg.lib().pn2_dropout(t.data_ptr(), n, keep, SEED, t.data_ptr(),
                                    torch.cuda.current_stream(dev).cuda_stream)
         assert rc == 0
         torch.cuda.synchronize()
-        assert np.array_equal(bits(t), ref.view(np.uint32))
+        assert np.array_equal(raw_bits(t), ref.view(np.uint32))
 
 
 def test_dropout_keep_prob_one_copies_and_empty(env):
@@ -109,10 +92,10 @@ def test_dropout_backward_is_the_op_on_the_gradient(env):
     go = torch.from_numpy(drop_input(n + 1)[:n]).to(dev).reshape(2, -1)
     out = ops.dropout(x, keep, SEED)
     out.backward(go)
-    assert np.array_equal(bits(x.grad), bits(ops.dropout(go, keep, SEED)))
+    assert np.array_equal(raw_bits(x.grad), raw_bits(ops.dropout(go, keep, SEED)))
     # supported exactly where the output is
     assert torch.equal(x.grad != 0, out != 0)
-    assert np.array_equal(bits(x.grad), cpu_dropout(pkg, go.cpu().numpy().reshape(-1), keep,
+    assert np.array_equal(raw_bits(x.grad), cpu_dropout(pkg, go.cpu().numpy().reshape(-1), keep,
                                                     SEED).view(np.uint32).reshape(2, -1))
 
 
@@ -120,7 +103,7 @@ def test_dropout_is_a_function_of_the_seed(env):
     pkg, ops, torch, dev = env
     x = torch.from_numpy(drop_input(128000)).to(dev)
     a, b = ops.dropout(x, 0.5, SEED), ops.dropout(x, 0.5, SEED)
-    assert np.array_equal(bits(a), bits(b))
+    assert np.array_equal(raw_bits(a), raw_bits(b))
     c = ops.dropout(x, 0.5, SEED + 1)
     d = ops.dropout(x, 0.5, SEED + (1 << 32))  # the high word is part of the key
     assert not torch.equal(a != 0, c != 0) and not torch.equal(a != 0, d != 0)
@@ -145,7 +128,7 @@ def test_tf_util_dropout_on_the_device(env):
     x = torch.from_numpy(drop_input(2 * 40 * 128)).to(dev).reshape(2, 40, 128)
     assert tu.dropout(x, False, "dp1") is x
     a = tu.dropout(x, True, "dp1", keep_prob=0.5, seed=SEED)
-    assert np.array_equal(bits(a), bits(ops.dropout(x, 0.5, SEED)))
+    assert np.array_equal(raw_bits(a), raw_bits(ops.dropout(x, 0.5, SEED)))
     torch.manual_seed(3)
     b = tu.dropout(x, True, "dp1")
     torch.manual_seed(3)

@@ -60,10 +60,10 @@ import importlib
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, gpu_available
+from conftest import PKG_NAME
+from support import f32_bits, gpu_marks
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
 TOL = dict(rtol=1e-5, atol=1e-5)  # README "Correctness targets"
 
@@ -88,12 +88,8 @@ def env():
     return pkg, O, torch, torch.device("cuda:0")
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
-
-
 def _same_bits(a, b):
-    return np.array_equal(_bits(a), _bits(b))
+    return np.array_equal(f32_bits(a), f32_bits(b))
 
 
 def _launches(B, *per_cloud):

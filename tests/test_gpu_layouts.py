@@ -21,16 +21,10 @@ import importlib
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, gpu_available
-
-gpu = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
-
-
-def on_gpu(f):
-    for m in gpu:
-        f = m(f)
-    return f
-
+import mlp_train_ref as R
+from conftest import PKG_NAME
+from mlp_ref import fused, make_layers, mlp_f32
+from support import assert_close, on_gpu, same_bits
 
 TOL = dict(rtol=1e-5, atol=1e-5)  # the README's bound for the floating-point attention kernels
 
@@ -63,31 +57,12 @@ def res(t):
     return 0 if t is None else t.data_ptr() % 16
 
 
-def bits(t):
-    a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
-def same_bits(a, b, what=""):
-    a, b = bits(a), bits(b)
-    assert a.shape == b.shape and np.array_equal(a, b), f"{what}: the bits differ"
-
-
 def stream(torch, dev):
     return torch.cuda.current_stream(dev).cuda_stream
 
 
 def tdev(torch, dev, a):
     return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def f32_close(got, ref64, ref32, what):
-    """tests/test_gpu_mlp_train.py assert_close (4 x the fp32 evaluation's error against
-    float64, floor 1e-6 relative) for numpy arrays: one definition of the tolerance."""
-    import torch
-    from test_gpu_mlp_train import assert_close
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dt)))  # noqa: E731
-    assert_close(t(got, np.float32), t(ref64, np.float64), t(ref32, np.float32), what)
 
 
 # =============================================================================== 1. sampler
@@ -237,7 +212,7 @@ def test_fp_interpolation_variants(env, fp_ref, C1, C2, k1, k2, kout, want):
                 ref64[b, fp_ref["idx"][b, j, t]] += w64[b, j, t] * g_np[b, j, :C2].astype(np.float64)
     ref32 = O.three_interpolate_grad(FP_M, fp_ref["idx"], O.idw_weights(fp_ref["dist"]),
                                      np.ascontiguousarray(g_np[:, :, :C2]))
-    f32_close(leaves[1].grad.cpu().numpy(), ref64, ref32, "grad_points2")
+    assert_close(leaves[1].grad.cpu().numpy(), ref64, ref32, "grad_points2")
     if C1:
         same_bits(leaves[0].grad, g_np[:, :, C2:], "grad_points1")
         same_bits(g1a, g_np[:, :, C2:], "grad_points1 (op)")
@@ -325,11 +300,6 @@ def test_fused_grouping_write_phases(env, sg_ref, ns, kp, ko, vec):
 # mlp.hip: a source segment is gathered as float4 only when its width is a multiple of 4 AND
 # its pointer is 16-byte aligned (x; points; points2, and points1 with C2 % 4 == 0 as well);
 # out_vec (float4 stores of the staged last layer) needs cout % 4 == 0 and an aligned out.
-def mlp_helpers():
-    import test_gpu_mlp as M
-    return M.make_layers, M.mlp_f32, M.assert_close, M.fused
-
-
 def seg_vec(width, r, extra=True):
     return width % 4 == 0 and r == 0 and extra
 
@@ -343,7 +313,6 @@ SHARED = [(cin, widths, which) for cin in (8, 12, 9) for widths in ([32, 21], [3
 @pytest.mark.parametrize("cin,widths,which", SHARED)
 def test_shared_mlp_on_offset_buffers(env, cin, widths, which):
     pkg, O, torch, dev, ops = env
-    make_layers, mlp_f32, assert_close, fused = mlp_helpers()
     rows, cout = 77, widths[-1]
     rng = np.random.default_rng(cin * 100 + cout)
     layers = make_layers(rng, cin, widths)
@@ -380,7 +349,6 @@ def test_shared_mlp_on_offset_buffers(env, cin, widths, which):
 @pytest.mark.parametrize("pooling", ["max", None])
 def test_group_mlp_on_offset_points(env, sg_ref, pooling):
     pkg, O, torch, dev, ops = env
-    make_layers, mlp_f32, assert_close, fused = mlp_helpers()
     T = lambda a: tdev(torch, dev, a)  # noqa: E731
     ns = 8
     idx_np, _, grouped = sg_ref[ns]
@@ -408,7 +376,6 @@ def test_group_mlp_attention_on_offset_points(env, sg_ref, add_max):
     tests/test_gpu_mlp.py test_fused_attention_matches_unfused."""
     pkg, O, torch, dev, ops = env
     import model_train_ref as MR
-    make_layers, mlp_f32, assert_close, fused = mlp_helpers()
     al, tu = pkg.attention_layer, pkg.tf_util
     T = lambda a: tdev(torch, dev, a)  # noqa: E731
     ns, C = 8, 32
@@ -444,7 +411,6 @@ def test_group_mlp_attention_on_offset_points(env, sg_ref, add_max):
 @pytest.mark.parametrize("which", ["points1", "points2"])
 def test_fp_module_on_offset_points(env, fp_ref, which):
     pkg, O, torch, dev, ops = env
-    make_layers, mlp_f32, assert_close, fused = mlp_helpers()
     T = lambda a: tdev(torch, dev, a)  # noqa: E731
     C1, C2, widths = 4, 8, [32, 16]
     rng = np.random.default_rng(21)
@@ -479,11 +445,9 @@ def test_training_layers_on_offset_buffers(env, pool):
     kernel (linear_rows in csrc/torch_ops.cpp -> pn2_shared_mlp) takes its per-float gather."""
     pkg, O, torch, dev, ops = env
     if pool:
-        import test_gpu_mlp_train_pool as R
         groups, ns, cin, cout = 26, 5, 8, 32   # 130 rows
-        p = R.make_params(torch, groups, ns, cin, cout, True, seed=9)
+        p = R.pool_make_params(torch, groups, ns, cin, cout, True, seed=9)
     else:
-        import test_gpu_mlp_train as R
         cin, cout = 8, 32
         p = R.make_params(torch, 130, cin, cout, True, seed=9)
     d = {k: v.to(dev) for k, v in p.items()}
@@ -504,24 +468,23 @@ def test_training_layers_on_offset_buffers(env, pool):
     mask = (plain > 0).cpu()
     if pool:
         assert torch.equal(out, plain.max(dim=1).values)
-        import test_gpu_mlp_train as R1
         flat = dict(p, x=p["x"].reshape(-1, cin))
-        f64, f32 = (R1.ref_layer(torch, flat, dt, True)[0] for dt in (torch.float64, torch.float32))
+        f64, f32 = (R.ref_layer(torch, flat, dt, True)[0] for dt in (torch.float64, torch.float32))
         pooled = lambda z: z.reshape(groups, ns, cout).max(dim=1).values  # noqa: E731
-        R.assert_close(out, pooled(f64[0]), pooled(f32[0]), "out")
-        R.assert_close(y.reshape(-1, cout), f64[1], f32[1], "y")
-        R.assert_close(mean, f64[2], f32[2], "mean")
-        R.assert_close(var, f64[3], f32[3], "var")
-        refs = {dt: R.ref_grads(torch, p, dt, True, mask, arg[0].cpu())
+        assert_close(out, pooled(f64[0]), pooled(f32[0]), "out")
+        assert_close(y.reshape(-1, cout), f64[1], f32[1], "y")
+        assert_close(mean, f64[2], f32[2], "mean")
+        assert_close(var, f64[3], f32[3], "var")
+        refs = {dt: R.pool_ref_grads(torch, p, dt, True, mask, arg[0].cpu())
                 for dt in (torch.float64, torch.float32)}
     else:
         f64, f32 = (R.ref_layer(torch, p, dt, True)[0] for dt in (torch.float64, torch.float32))
         for i, name in enumerate(("out", "y", "mean", "var")):
-            R.assert_close(got[i], f64[i], f32[i], name)
+            assert_close(got[i], f64[i], f32[i], name)
         refs = {dt: R.ref_grads(torch, p, dt, True, mask) for dt in (torch.float64, torch.float32)}
     r64, r32 = refs[torch.float64], refs[torch.float32]
     for g, k in zip(ggot, ("x", "w", "b", "gamma", "beta")):
-        R.assert_close(g, r64[k], r32[k], "grad_" + k)
+        assert_close(g, r64[k], r32[k], "grad_" + k)
 
 
 # ============================================================================ 5. row gathers
@@ -720,12 +683,12 @@ def test_attention_training_accepts_misaligned_tensors(env, which):
         same_bits(s, t, "attn_kv_train_grad vs aligned")
     f64 = MR.attention_core(x.double(), *[w.double() for w in weights])
     f32 = MR.attention_core(x, *weights)
-    f32_close(att.cpu().numpy(), f64.numpy(), f32.numpy(), "att")
+    assert_close(att.cpu().numpy(), f64.numpy(), f32.numpy(), "att")
     same_bits(pmax, x.max(dim=2).values, "pmax")
     r64 = MR.attention_op_grads(x, weights, ga, gp, arg, torch.float64)
     r32 = MR.attention_op_grads(x, weights, ga, gp, arg, torch.float32)
     for s, t64, t32, name in zip(got, r64, r32, ("x", "wq", "bq", "wk", "bk", "wv", "bv")):
-        f32_close(s.cpu().numpy(), t64.numpy(), t32.numpy(), "grad_" + name)
+        assert_close(s.cpu().numpy(), t64.numpy(), t32.numpy(), "grad_" + name)
 
 
 # ========================================================================= 7. strided inputs
@@ -758,7 +721,7 @@ def strided_sweep(torch, dev, call, args_np, ref=None, exact=True, skip=(), atom
     within TOL when not `exact`). atomic: the kernel sums with float atomics (the reference's
     gradient kernels, tf_sampling_g.cu / tf_grouping_g.cu / tf_interpolate.cpp), so two runs
     of it need not agree in the last bit: the clone comparison is within TOL too.
-    exact="f32": `ref` returns (float64, float32) pairs, compared by f32_close (the training
+    exact="f32": `ref` returns (float64, float32) pairs, compared by assert_close (the training
     layers' tolerance). A None in ref's result skips that output. ref_expand=False: no
     reference for the stride-0 batch (arguments saved by a forward no longer belong together
     once one of them has its batch entries replaced)."""
@@ -785,7 +748,7 @@ def strided_sweep(torch, dev, call, args_np, ref=None, exact=True, skip=(), atom
                     if w is None:
                         continue
                     if exact == "f32":
-                        f32_close(g.cpu().numpy(), w[0], w[1], f"arg {i} as {name}")
+                        assert_close(g.cpu().numpy(), w[0], w[1], f"arg {i} as {name}")
                     elif exact:
                         same_bits(g, w, f"arg {i} as {name} vs reference")
                     else:
@@ -937,8 +900,7 @@ def test_strided_attention_ops(env, attn_ref):
 
 
 def layer_ref(torch, x, w, b, gamma, beta, pool=False):
-    """tests/test_gpu_mlp_train.py ref_layer on x (groups, ns, cin): (out, y, mean, var) pairs."""
-    import test_gpu_mlp_train as R
+    """mlp_train_ref.ref_layer on x (groups, ns, cin): (out, y, mean, var) pairs."""
     shape = x.shape[:-1] + (w.shape[1],)
 
     def fn(x, w, b, gamma, beta):
@@ -1009,8 +971,6 @@ def test_strided_gradient_ops(env):
     see a strided grad_out)."""
     pkg, O, torch, dev, ops = env
     import head_train_ref as HR
-    import test_gpu_mlp_train as R
-    import test_gpu_mlp_train_pool as RP
     rng = np.random.default_rng(14)
     sw = lambda *a, **k: strided_sweep(torch, dev, *a, ref_expand=False, **k)  # noqa: E731
     D = lambda d: {k: None if v is None else v.to(dev) for k, v in d.items()}  # noqa: E731
@@ -1026,15 +986,15 @@ def test_strided_gradient_ops(env):
                                                                  True, True),
        [d["go"], d["x"], d["w"], y, mean, var, d["gamma"], d["beta"]], lambda *a: ref, exact="f32")
     # mlp_layer_train_pool_grad
-    p = RP.make_params(torch, 26, 5, 8, 32, True, seed=3)
+    p = R.pool_make_params(torch, 26, 5, 8, 32, True, seed=3)
     d = D(p)
     out, y, mean, var, arg = ops.mlp_layer_train_pool(d["x"], d["w"], d["b"], d["gamma"], d["beta"],
-                                                      RP.EPS, True)
-    full = ops.mlp_layer_train(d["x"], d["w"], d["b"], d["gamma"], d["beta"], RP.EPS, True)[0]
-    r = [RP.ref_grads(torch, p, dt, True, (full > 0).cpu(), arg.cpu()) for dt in both]
+                                                      R.EPS, True)
+    full = ops.mlp_layer_train(d["x"], d["w"], d["b"], d["gamma"], d["beta"], R.EPS, True)[0]
+    r = [R.pool_ref_grads(torch, p, dt, True, (full > 0).cpu(), arg.cpu()) for dt in both]
     ref2 = [(r[0][k].numpy(), r[1][k].numpy()) for k in names]
     sw(lambda go, a, x, w, y, m, v, g, bt: ops.mlp_layer_train_pool_grad(go, a, x, w, y, m, v, g, bt,
-                                                                         RP.EPS, True, True),
+                                                                         R.EPS, True, True),
        [d["go"], arg, d["x"], d["w"], y, mean, var, d["gamma"], d["beta"]], lambda *a: ref2,
        exact="f32")
     # bn_train_grad

@@ -15,10 +15,11 @@ import importlib
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, gpu_available
+from conftest import PKG_NAME
+from mlp_ref import fused, make_layers, mlp_f32
+from support import assert_close, gpu_marks
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
 
 @pytest.fixture(scope="module")
@@ -29,57 +30,6 @@ def env():
     O.set_threads(16)
     pkg = importlib.import_module(PKG_NAME)
     return pkg, O, torch, torch.device("cuda:0")
-
-
-def make_layers(rng, cin, widths, bn=True, relu=True, last_relu=None, last_bn=None):
-    layers, c = [], cin
-    for i, w in enumerate(widths):
-        last = i == len(widths) - 1
-        use_bn = bn if not (last and last_bn is not None) else last_bn
-        use_relu = relu if not (last and last_relu is not None) else last_relu
-        lim = np.sqrt(6.0 / (c + w))
-        L = {"weights": rng.uniform(-lim, lim, (c, w)).astype(np.float32),
-             "biases": rng.uniform(-0.1, 0.1, w).astype(np.float32), "relu": use_relu}
-        if use_bn:
-            L.update(gamma=rng.uniform(0.5, 1.5, w).astype(np.float32),
-                     beta=rng.uniform(-0.2, 0.2, w).astype(np.float32),
-                     moving_mean=rng.uniform(-0.1, 0.1, w).astype(np.float32),
-                     moving_variance=rng.uniform(0.5, 2.0, w).astype(np.float32))
-        layers.append(L)
-        c = w
-    return layers
-
-
-def fused(pkg, layers):
-    tu = pkg.tf_util
-    return tu.SharedMLP([tu.PackedLayer(L["weights"], L["biases"], L.get("gamma"), L.get("beta"),
-                                        L.get("moving_mean"), L.get("moving_variance"),
-                                        relu=L["relu"]) for L in layers])
-
-
-def mlp_f32(x, layers):
-    """The same layers in numpy float32 (the error yardstick of the tolerance)."""
-    y = np.asarray(x, np.float32)
-    for L in layers:
-        y = y @ L["weights"] + L["biases"]
-        if L.get("gamma") is not None:
-            s = (L["gamma"].astype(np.float64) / np.sqrt(L["moving_variance"].astype(np.float64)
-                                                         + 1e-3))
-            t = L["beta"] - L["moving_mean"] * s
-            y = (y * s.astype(np.float32) + t.astype(np.float32)).astype(np.float32)
-        if L["relu"]:
-            y = np.maximum(y, 0)
-    return y
-
-
-def assert_close(got, ref64, ref32, what):
-    got = np.asarray(got, np.float64)
-    err = np.abs(got - ref64).max() if got.size else 0.0
-    err32 = np.abs(np.asarray(ref32, np.float64) - ref64).max() if got.size else 0.0
-    tol = max(4 * err32, 1e-6 * (1 + np.abs(ref64).max() if got.size else 1.0))
-    assert got.shape == ref64.shape, (got.shape, ref64.shape)
-    assert np.isfinite(got).all(), f"{what}: non-finite outputs"
-    assert err <= tol, f"{what}: max err {err:.3g} > tol {tol:.3g} (fp32 numpy err {err32:.3g})"
 
 
 MLP_CASES = [

@@ -17,10 +17,10 @@ import numpy as np
 import pytest
 
 import mlp_bf16_ref as R
-from conftest import PKG_NAME, gpu_available
+from conftest import PKG_NAME
+from support import gpu_marks, same_bits, tolerance
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
 
 @pytest.fixture(scope="module")
@@ -95,14 +95,6 @@ def run_attention(env, xyz, points, new_xyz, idx, layers, dense, sc, sh, add_max
                                      lb.stream_of(out))
     lb.check(rc, "group_mlp_attention")
     return out.cpu().numpy()
-
-
-def same_bits(a, b, what):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    bad = np.flatnonzero(a.view(np.uint32).ravel() != b.view(np.uint32).ravel())
-    assert bad.size == 0, f"{what}: {bad.size} of {a.size} values differ, first at {bad[0]}: " \
-                          f"{a.ravel()[bad[0]]!r} vs {b.ravel()[bad[0]]!r}"
 
 
 # ---------------------------------------------------------------- 1. layout, exact
@@ -246,8 +238,7 @@ def test_single_layer_vs_contract(env, widths):
         x = rng.uniform(-1, 1, (rows, cin)).astype(np.float32)
         got = run_rows(env, x, [L]).astype(np.float64)
         E, E32 = R.layer_eval(x.astype(np.float64), L, "E"), R.layer_eval(x, L, "E32")
-        err, err32 = np.abs(got - E).max(), np.abs(E32.astype(np.float64) - E).max()
-        tol = max(4 * err32, 1e-6 * (1 + np.abs(E).max()))
+        err, (tol, err32) = np.abs(got - E).max(), tolerance(E, E32)
         print(f"rows {rows} {cin}->{cout}: max|gpu - E| = {err:.3g}, max|E32 - E| = {err32:.3g}")
         assert err <= tol, f"rows {rows} {cin}->{cout}: {err:.3g} > {tol:.3g}"
 

@@ -3,7 +3,7 @@ public tf_util / pointnet_util interfaces.
 
 Reference: torch float64 on the CPU with the formulas of tf_util.mlp_torch(is_training=True)
 (conv + bias, batch mean and BIASED variance over the rows, gamma / sqrt(var + 1e-3), ReLU),
-and its autograd. Tolerance (the project's, tests/test_gpu_mlp.py):
+and its autograd. Tolerance (the project's, tests/support.py):
 
     max |gpu - f64|  <=  max(4 * max |fp32 - f64|,  1e-6 * (1 + max |f64|))
 
@@ -13,19 +13,17 @@ A ReLU that flips at a pre-activation within rounding of zero is a discrete diff
 error, so the backward references multiply by the mask `out_gpu > 0` of the forward output
 under test (which the forward tests have validated) instead of applying their own ReLU.
 """
-import functools
 import importlib
 
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, gpu_available
+from conftest import PKG_NAME
+from mlp_train_ref import (B, EPS, FP_MLP, N, NPOINT, NS, RADIUS, SA_MLP, SLAB, bn_act_bwd,
+                           ids, make_params, ref_layer, run_case, sa_fp)
+from support import assert_close, gpu_marks
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
-
-EPS = 1e-3
-SLAB = 1024   # PN2_WGRAD_SLAB_ROWS and PN2_BN_BLOCK_ROWS (include/pn2hip.h)
+pytestmark = gpu_marks
 
 # (rows, cin, cout, batch norm, relu)
 CASES = [
@@ -52,77 +50,6 @@ def env():
     pkg = importlib.import_module(PKG_NAME)
     import pn2hip
     return pkg, pn2hip.ops, torch, torch.device("cuda:0")
-
-
-def assert_close(got, ref64, ref32, what):
-    got = np.asarray(got.detach().cpu().numpy(), np.float64)
-    ref64 = ref64.detach().numpy()
-    ref32 = np.asarray(ref32.detach().numpy(), np.float64)
-    assert got.shape == ref64.shape, (what, got.shape, ref64.shape)
-    assert np.isfinite(got).all(), f"{what}: non-finite values"
-    err = np.abs(got - ref64).max() if got.size else 0.0
-    err32 = np.abs(ref32 - ref64).max() if got.size else 0.0
-    tol = max(4 * err32, 1e-6 * (1 + (np.abs(ref64).max() if got.size else 0.0)))
-    print(f"{what}: err {err:.3g} tol {tol:.3g} (fp32 err {err32:.3g})")
-    assert err <= tol, f"{what}: max err {err:.3g} > tol {tol:.3g} (fp32 cpu err {err32:.3g})"
-
-
-def make_params(torch, rows, cin, cout, bn, seed, bias=None):
-    g = torch.Generator().manual_seed(seed)
-    u = lambda lo, hi, *s: torch.rand(*s, generator=g, dtype=torch.float64) * (hi - lo) + lo  # noqa: E731
-    lim = float(np.sqrt(6.0 / (cin + cout)))
-    p = {"x": u(-1, 1, rows, cin), "w": u(-lim, lim, cin, cout),
-         "b": u(-0.1, 0.1, cout) if bias is None else bias.double(),
-         "gamma": u(0.5, 1.5, cout) if bn else None, "beta": u(-0.2, 0.2, cout) if bn else None,
-         "go": u(-1, 1, rows, cout)}
-    # the values under test are float32: the references start from exactly those numbers
-    return {k: None if v is None else v.float() for k, v in p.items()}
-
-
-def ref_layer(torch, p, dt, relu, mask=None):
-    """One layer by tf_util.mlp_torch's formulas in dtype dt on the CPU. mask: the ReLU as a
-    product with a given 0/1 mask. Returns (out, y, mean, var) and the leaves."""
-    leaves = {k: None if v is None else v.to(dt).clone().requires_grad_(True)
-              for k, v in p.items() if k != "go"}
-    y = leaves["x"] @ leaves["w"] + leaves["b"]
-    mean = var = None
-    z = y
-    if leaves["gamma"] is not None:
-        mean = y.mean(dim=0)
-        var = y.var(dim=0, unbiased=False)
-        z = (y - mean) * (leaves["gamma"] / torch.sqrt(var + EPS)) + leaves["beta"]
-    if relu:
-        z = torch.relu(z) if mask is None else z * mask.to(dt)
-    return (z, y, mean, var), leaves
-
-
-def ref_grads(torch, p, dt, relu, mask):
-    (out, _, _, _), leaves = ref_layer(torch, p, dt, relu, mask)
-    (out * p["go"].to(dt)).sum().backward()
-    return {k: v.grad for k, v in leaves.items() if v is not None}
-
-
-@functools.lru_cache(maxsize=None)
-def run_case(case):
-    """Forward + backward of one case on the GPU and its references, computed once."""
-    import torch
-    import pn2hip
-    ops, dev = pn2hip.ops, torch.device("cuda:0")
-    rows, cin, cout, bn, relu = case
-    p = make_params(torch, rows, cin, cout, bn, seed=rows * 31 + cin)
-    d = {k: None if v is None else v.to(dev) for k, v in p.items()}
-    out, y, mean, var = ops.mlp_layer_train(d["x"], d["w"], d["b"], d["gamma"], d["beta"], EPS, relu)
-    grads = ops.mlp_layer_train_grad(d["go"], d["x"], d["w"], y, mean, var, d["gamma"], d["beta"],
-                                     EPS, relu, True)
-    torch.cuda.synchronize()
-    mask = (out > 0).cpu()
-    fwd = {dt: ref_layer(torch, p, dt, relu)[0] for dt in (torch.float64, torch.float32)}
-    bwd = {dt: ref_grads(torch, p, dt, relu, mask) for dt in (torch.float64, torch.float32)}
-    return p, d, (out, y, mean, var), grads, fwd, bwd
-
-
-def ids(case):
-    return "x".join(str(int(v)) for v in case)
 
 
 @pytest.mark.parametrize("case", CASES, ids=ids)
@@ -177,23 +104,6 @@ def test_layer_backward(env, case):
         assert_close(gbeta, r64["beta"], r32["beta"], "grad_beta")
     else:
         assert gg.numel() == 0 and gbeta.numel() == 0
-
-
-def bn_act_bwd(pkg, torch, go, y, mean, var, gamma, beta, relu):
-    """pn2_bn_act_bwd through the C ABI: (grad_y, grad_gamma or None, grad_beta)."""
-    L = importlib.import_module(PKG_NAME + "._lib")
-    rows, C = int(y.shape[0]), int(y.shape[1])
-    bn = gamma is not None
-    ws_bytes = int(L.lib().pn2_bn_workspace_size(rows, C))
-    ws = torch.empty(max(ws_bytes // 4, 4), dtype=torch.float32, device=y.device)
-    gy = torch.full_like(y, float("nan"))
-    gg = torch.full((C,), float("nan"), device=y.device) if bn else None
-    gbeta = torch.full((C,), float("nan"), device=y.device)
-    L.check(L.lib().pn2_bn_act_bwd(L.ptr(go), L.ptr(y), rows, C, L.ptr(mean) if bn else None,
-                                   L.ptr(var) if bn else None, L.ptr(gamma), L.ptr(beta), EPS,
-                                   int(relu), L.ptr(gy), L.ptr(gg), L.ptr(gbeta), L.ptr(ws),
-                                   ws_bytes, L.stream_of(y)), "bn_act_bwd")
-    return gy, gg, gbeta
 
 
 @pytest.mark.parametrize("case", [c for c in CASES if c[4]], ids=ids)
@@ -293,24 +203,11 @@ def test_need_grad_x_false(env):
 
 # ------------------------------------------------------------------- modules --------------
 
-B, N, NPOINT, RADIUS, NS = 2, 1024, 128, 0.2, 16
-SA_MLP, FP_MLP = [32, 64], [64, 32]
-
-
 @pytest.fixture(scope="module")
 def cloud(env):
     pkg, ops, torch, dev = env
     xyz, feats = pkg.synth.batch([0, 1], N, "scannet", with_features=True)
     return torch.from_numpy(xyz).to(dev), torch.from_numpy(feats).to(dev)
-
-
-def sa_fp(pkg, store, xyz, feats, is_training):
-    pu = pkg.pointnet_util
-    new_xyz, sa, idx = pu.pointnet_sa_module(xyz, feats, NPOINT, RADIUS, NS, SA_MLP, None, False,
-                                             is_training, None, "sa1", params=store)
-    fp = pu.pointnet_fp_module(xyz, new_xyz, feats, sa, FP_MLP, is_training, None, "fp1",
-                               params=store)
-    return new_xyz, sa, fp
 
 
 def test_modules_train_on_a_trainable_store(env, cloud):

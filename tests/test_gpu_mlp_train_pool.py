@@ -24,12 +24,14 @@ import importlib
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, gpu_available
+from conftest import PKG_NAME
+from mlp_train_ref import B, EPS, FP_MLP, N, NPOINT, NS, RADIUS, SA_MLP, ids
+from mlp_train_ref import pool_make_params as make_params
+from mlp_train_ref import pool_ref_grads as ref_grads
+from support import assert_close, gpu_marks
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
-EPS = 1e-3
 PG = 128      # PN2_BN_POOL_BLOCK_GROUPS (include/pn2hip.h): groups per stage-1 partial
 T, F = True, False
 
@@ -60,54 +62,6 @@ def env():
     return pkg, pn2hip.ops, torch, torch.device("cuda:0")
 
 
-def assert_close(got, ref64, ref32, what):
-    got = np.asarray(got.detach().cpu().numpy(), np.float64)
-    ref64 = ref64.detach().numpy()
-    ref32 = np.asarray(ref32.detach().numpy(), np.float64)
-    assert got.shape == ref64.shape, (what, got.shape, ref64.shape)
-    assert np.isfinite(got).all(), f"{what}: non-finite values"
-    err = np.abs(got - ref64).max() if got.size else 0.0
-    err32 = np.abs(ref32 - ref64).max() if got.size else 0.0
-    tol = max(4 * err32, 1e-6 * (1 + (np.abs(ref64).max() if got.size else 0.0)))
-    print(f"{what}: err {err:.3g} tol {tol:.3g} (fp32 err {err32:.3g})")
-    assert err <= tol, f"{what}: max err {err:.3g} > tol {tol:.3g} (fp32 cpu err {err32:.3g})"
-
-
-def make_params(torch, groups, ns, cin, cout, bn, seed):
-    """test_gpu_mlp_train.make_params over groups * ns rows, with gamma of either sign and a
-    (groups, cout) grad_out."""
-    g = torch.Generator().manual_seed(seed)
-    u = lambda lo, hi, *s: torch.rand(*s, generator=g, dtype=torch.float64) * (hi - lo) + lo  # noqa: E731
-    lim = float(np.sqrt(6.0 / (cin + cout)))
-    p = {"x": u(-1, 1, groups, ns, cin), "w": u(-lim, lim, cin, cout), "b": u(-0.1, 0.1, cout),
-         "gamma": None, "beta": None}
-    if bn:
-        mag, sign = u(0.5, 1.5, cout), u(-1, 1, cout)
-        p["gamma"] = torch.where(sign < 0, -mag, mag)
-        p["beta"] = u(-0.2, 0.2, cout)
-    p["go"] = u(-1, 1, groups, cout)
-    # the values under test are float32: the references start from exactly those numbers
-    return {k: None if v is None else v.float() for k, v in p.items()}
-
-
-def ref_grads(torch, p, dt, relu, mask, arg):
-    """Gradients of sum(go * pooled) in dtype dt on the CPU: tf_util.mlp_torch's formulas, the
-    ReLU as a product with `mask` (groups, ns, C), the pool as a gather at `arg` (groups, C)."""
-    leaves = {k: None if v is None else v.to(dt).clone().requires_grad_(True)
-              for k, v in p.items() if k != "go"}
-    y = leaves["x"] @ leaves["w"] + leaves["b"]
-    z = y
-    if leaves["gamma"] is not None:
-        flat = y.reshape(-1, y.shape[-1])
-        mean, var = flat.mean(dim=0), flat.var(dim=0, unbiased=False)
-        z = (y - mean) * (leaves["gamma"] / torch.sqrt(var + EPS)) + leaves["beta"]
-    if relu:
-        z = z * mask.to(dt)
-    pooled = z.gather(1, arg.long()[:, None, :]).squeeze(1)
-    (pooled * p["go"].to(dt)).sum().backward()
-    return {k: v.grad for k, v in leaves.items() if v is not None}
-
-
 def first_argmax(out_full, out):
     """(groups, C) lowest j with out_full[g, j, c] == out[g, c], on the CPU (numpy's argmax
     returns the first maximum)."""
@@ -134,10 +88,6 @@ def run_case(case):
     mask, arg_cpu = (plain[0] > 0).cpu(), arg.cpu()
     bwd = {dt: ref_grads(torch, p, dt, relu, mask, arg_cpu) for dt in (torch.float64, torch.float32)}
     return p, d, fused, grads, plain, bwd
-
-
-def ids(case):
-    return "x".join(str(int(v)) for v in case)
 
 
 @pytest.mark.parametrize("case", CASES, ids=ids)
@@ -337,8 +287,6 @@ def test_empty_input_and_no_samples(env):
 
 # ------------------------------------------------------------------- modules --------------
 
-B, N, NPOINT, RADIUS, NS = 2, 1024, 128, 0.2, 16
-SA_MLP, FP_MLP = [32, 64], [64, 32]
 VARS = (("w", "weights"), ("b", "biases"), ("gamma", "bn/gamma"), ("beta", "bn/beta"))
 
 

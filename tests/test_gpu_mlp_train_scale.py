@@ -28,14 +28,13 @@ import importlib
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, gpu_available
-from test_gpu_mlp import assert_close as assert_close_np
-from test_gpu_mlp import fused, make_layers, mlp_f32
-from test_gpu_mlp_train import (B, EPS, FP_MLP, N, NPOINT, NS, RADIUS, SA_MLP, SLAB, assert_close,
-                                bn_act_bwd, ids, make_params, ref_grads, ref_layer, run_case)
+from conftest import PKG_NAME
+from mlp_ref import fused, make_layers, mlp_f32
+from mlp_train_ref import (B, EPS, FP_MLP, N, NPOINT, NS, RADIUS, SA_MLP, SLAB, bn_act_bwd, ids,
+                           make_params, ref_grads, ref_layer, run_case)
+from support import assert_close, gpu_marks
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
 WGRAD_MAX_PARTS = 512   # PN2_WGRAD_MAX_PARTS (include/pn2hip.h)
 WGRAD_TILE_BYTES = 4096  # one 32 x 32 fp32 partial tile
@@ -108,7 +107,7 @@ def test_rows_kernel_multi_tile_vs_f64(env, case):
     layers = make_layers(rng, cin, widths)
     x = rng.uniform(-1, 1, (rows, cin)).astype(np.float32)
     got = fused(pkg, layers)(torch.from_numpy(x).to(dev)).cpu().numpy()
-    assert_close_np(got, O.mlp_f64(x, layers), mlp_f32(x, layers), "shared_mlp")
+    assert_close(got, O.mlp_f64(x, layers), mlp_f32(x, layers), "shared_mlp")
 
 
 def test_rows_cases_reach_every_plan():

@@ -21,7 +21,7 @@ tests/test_model_train_ref_cpu.py): plain torch on the CPU in float64, and in fl
 yardstick, on the discrete choices a recording spy around _torch_ops.call took from the GPU's
 own forward. Compared: logits, end_points["feats"], the loss, the gradient of every variable, the
 gradient of the input features, every moving mean and variance (0.8 * initial + 0.2 * batch
-statistic), with the project's rule, that of tests/test_gpu_mlp_train.py::assert_close, stated
+statistic), with the project's rule, that of tests/support.py::assert_close, stated
 once in Comparisons.close with the factor as a parameter
 
     max |gpu - f64|  <=  max(4 * max |fp32 - f64|,  1e-6 * (1 + max |f64|))
@@ -547,11 +547,11 @@ import numpy as np
 import pytest
 
 import model_train_ref as R
-from conftest import PKG_NAME, gpu_available
+from conftest import PKG_NAME
 from optim_cases import bits, numpy_adam
+from support import gpu_marks
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
 # The factor on the float32 yardstick, per case: the project's 4, except case (c) (see the
 # module docstring: the attention op itself is within 4 on the model's own inputs)
@@ -644,7 +644,7 @@ def gpu_model(pkg, spec, store, xyz, feats, seed):
 
 
 class Comparisons:
-    """The rule of tests/test_gpu_mlp_train.py::assert_close (same checks, same printed line) with
+    """The rule of tests/support.py::assert_close (same checks, same printed line) with
     the factor on the float32 yardstick as a parameter, on every tensor of a case; the failures
     are raised together at the end."""
 

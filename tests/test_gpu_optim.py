@@ -12,10 +12,10 @@ import numpy as np
 import pytest
 
 import optim_cases as oc
-from conftest import PKG_NAME, gpu_available
+from conftest import PKG_NAME
+from support import gpu_marks
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
 
 @pytest.fixture(scope="module")

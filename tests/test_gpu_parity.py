@@ -15,10 +15,10 @@ import os
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, gpu_available
+from conftest import PKG_NAME
+from support import clouds, f32_bits, gpu_marks
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
 TOL = dict(rtol=1e-5, atol=1e-5)
 
@@ -31,29 +31,6 @@ def env():
     O.set_threads(16)
     pkg = importlib.import_module(PKG_NAME)
     return pkg, O, torch, torch.device("cuda:0")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
-
-
-def _cloud(pkg, kind, B, N, seed=0):
-    if kind == "scannet":
-        return pkg.synth.batch(range(seed, seed + B), N, "scannet")[0]
-    if kind == "uniform":
-        return pkg.synth.batch(range(seed, seed + B), N, "uniform")[0]
-    if kind == "dup":  # every point the same: all distances tie
-        x = np.tile(np.array([[0.25, 0.5, 0.75]], np.float32), (B, N, 1))
-        return x.reshape(B, N, 3)
-    if kind == "grid":  # integer lattice: massive exact ties
-        g = np.stack(np.meshgrid(*[np.arange(16)] * 3, indexing="ij"), -1).reshape(-1, 3)
-        rng = np.random.default_rng(seed)
-        return np.stack([g[rng.integers(0, len(g), N)] for _ in range(B)]).astype(np.float32)
-    if kind == "fewuniq":  # 300 distinct points drawn with replacement: npoint > #unique
-        rng = np.random.default_rng(seed)
-        u = rng.random((300, 3)).astype(np.float32)
-        return np.stack([u[rng.integers(0, 300, N)] for _ in range(B)])
-    raise ValueError(kind)
 
 
 FPS_CASES = [
@@ -77,12 +54,12 @@ FPS_CASES = [
 @pytest.mark.parametrize("kind,B,N,M", FPS_CASES)
 def test_fps_vs_oracle(env, kind, B, N, M):
     pkg, O, torch, dev = env
-    x = _cloud(pkg, kind, B, N)
+    x = clouds(pkg, kind, B, N)
     idx, new_xyz = pkg.tf_sampling.farthest_point_sample_and_gather(M, torch.from_numpy(x).to(dev))
     ref = O.fps(x, M)
     got = idx.cpu().numpy()
     assert np.array_equal(got, ref), f"{(got != ref).sum()} FPS indices differ"
-    assert np.array_equal(_bits(new_xyz.cpu().numpy()), _bits(O.gather_point(x, ref)))
+    assert np.array_equal(f32_bits(new_xyz.cpu().numpy()), f32_bits(O.gather_point(x, ref)))
     only = pkg.tf_sampling.farthest_point_sample(M, torch.from_numpy(x).to(dev))
     assert np.array_equal(only.cpu().numpy(), ref)
 
@@ -98,7 +75,7 @@ def test_fps_vs_reference_kernel(env, kind, B, N, M):
     pkg, O, torch, dev = env
     if not O.have_ref_gpu():
         pytest.skip("oracle/_ref/libref_gpu.so not built")
-    x = _cloud(pkg, kind, B, N)
+    x = clouds(pkg, kind, B, N)
     xt = torch.from_numpy(x).to(dev)
     ref_out = torch.zeros((B, M), dtype=torch.int32, device=dev)
     assert O.ref_gpu().pn2ref_fps(xt.data_ptr(), B, N, M, ref_out.data_ptr()) == 0
@@ -162,16 +139,16 @@ def test_prob_sample_errors(env):
 
 def test_gather_point(env):
     pkg, O, torch, dev = env
-    x = _cloud(pkg, "scannet", 3, 2048)
+    x = clouds(pkg, "scannet", 3, 2048)
     idx = np.random.default_rng(1).integers(0, 2048, (3, 300)).astype(np.int32)
     got = pkg.tf_sampling.gather_point(torch.from_numpy(x).to(dev), torch.from_numpy(idx).to(dev))
-    assert np.array_equal(_bits(got.cpu().numpy()), _bits(O.gather_point(x, idx)))
+    assert np.array_equal(f32_bits(got.cpu().numpy()), f32_bits(O.gather_point(x, idx)))
     if O.have_ref_gpu():
         out = torch.zeros((3, 300, 3), device=dev)
         xt, it = torch.from_numpy(x).to(dev), torch.from_numpy(idx).to(dev)
         assert O.ref_gpu().pn2ref_gather_point(xt.data_ptr(), it.data_ptr(), 3, 2048, 300,
                                                out.data_ptr()) == 0
-        assert np.array_equal(_bits(out.cpu().numpy()), _bits(got.cpu().numpy()))
+        assert np.array_equal(f32_bits(out.cpu().numpy()), f32_bits(got.cpu().numpy()))
 
 
 BQ_CASES = [
@@ -191,7 +168,7 @@ BQ_CASES = [
 @pytest.mark.parametrize("kind,B,N,M,r,ns", BQ_CASES)
 def test_ball_query_vs_oracle(env, kind, B, N, M, r, ns):
     pkg, O, torch, dev = env
-    x = _cloud(pkg, kind, B, N)
+    x = clouds(pkg, kind, B, N)
     q = O.gather_point(x, O.fps(x, M)) if kind != "grid" else x[:, :M].copy()
     idx, cnt = pkg.tf_grouping.query_ball_point(r, ns, torch.from_numpy(x).to(dev),
                                                 torch.from_numpy(q).to(dev))
@@ -235,7 +212,7 @@ def test_ball_query_grid_equals_scan(env, kind, B, N, M, r, ns):
     """The spatial-grid path (ball_grid.hip) returns exactly the in-order scan's idx and
     pts_cnt, and the oracle's; queries also far outside the cloud's bounding box."""
     pkg, O, torch, dev = env
-    x = _cloud(pkg, kind, B, N)
+    x = clouds(pkg, kind, B, N)
     q = O.gather_point(x, O.fps(x, M)) if kind != "grid" else x[:, :M].copy()
     q[:, :3] = np.array([[50.0, 50.0, 50.0], [-3.0, 0.5, 0.5], [0.5, 0.5, 9.0]], np.float32)
     xt, qt = torch.from_numpy(x).to(dev), torch.from_numpy(q).to(dev)
@@ -263,7 +240,7 @@ def test_ball_query_vs_reference_kernel(env, kind, B, N, M, r, ns):
     pkg, O, torch, dev = env
     if not O.have_ref_gpu():
         pytest.skip("oracle/_ref/libref_gpu.so not built")
-    x = _cloud(pkg, kind, B, N)
+    x = clouds(pkg, kind, B, N)
     q = O.gather_point(x, O.fps(x, M))
     xt, qt = torch.from_numpy(x).to(dev), torch.from_numpy(q).to(dev)
     ri = torch.zeros((B, M, ns), dtype=torch.int32, device=dev)
@@ -282,7 +259,7 @@ def test_group_point(env, C):
     pts = rng.standard_normal((2, 500, C)).astype(np.float32)
     idx = rng.integers(0, 500, (2, 70, 32)).astype(np.int32)
     got = pkg.tf_grouping.group_point(torch.from_numpy(pts).to(dev), torch.from_numpy(idx).to(dev))
-    assert np.array_equal(_bits(got.cpu().numpy()), _bits(O.group_point(pts, idx)))
+    assert np.array_equal(f32_bits(got.cpu().numpy()), f32_bits(O.group_point(pts, idx)))
 
 
 @pytest.mark.parametrize("C,use_xyz,xyz_last", [(0, True, False), (6, True, False),
@@ -290,7 +267,7 @@ def test_group_point(env, C):
                                                 (320, True, True), (5, True, True)])
 def test_group_concat(env, C, use_xyz, xyz_last):
     pkg, O, torch, dev = env
-    x = _cloud(pkg, "scannet", 2, 2048)
+    x = clouds(pkg, "scannet", 2, 2048)
     q = O.gather_point(x, O.fps(x, 128))
     idx, _ = O.ball_query(x, q, 0.2, 32)
     pts = pkg.synth.features_uniform(C + 1, (2, 2048, C)) if C else None
@@ -298,8 +275,8 @@ def test_group_concat(env, C, use_xyz, xyz_last):
     got, gx = pkg.pointnet_util.group_concat(t(x), t(pts), t(q), t(idx), use_xyz=use_xyz,
                                              xyz_last=xyz_last)
     ref, rgx = O.group_concat(x, pts, q, idx, use_xyz=use_xyz, xyz_last=xyz_last)
-    assert np.array_equal(_bits(got.cpu().numpy()), _bits(ref))
-    assert np.array_equal(_bits(gx.cpu().numpy()), _bits(rgx))
+    assert np.array_equal(f32_bits(got.cpu().numpy()), f32_bits(ref))
+    assert np.array_equal(f32_bits(gx.cpu().numpy()), f32_bits(rgx))
 
 
 def test_sample_and_group_api(env):
@@ -310,10 +287,10 @@ def test_sample_and_group_api(env):
     nx = O.gather_point(x, O.fps(x, 512))
     bi, _ = O.ball_query(x, nx, 0.2, 32)
     npts, gx = O.group_concat(x, f, nx, bi)
-    assert np.array_equal(_bits(new_xyz.cpu().numpy()), _bits(nx))
+    assert np.array_equal(f32_bits(new_xyz.cpu().numpy()), f32_bits(nx))
     assert np.array_equal(idx.cpu().numpy(), bi)
-    assert np.array_equal(_bits(new_points.cpu().numpy()), _bits(npts))
-    assert np.array_equal(_bits(gxyz.cpu().numpy()), _bits(gx))
+    assert np.array_equal(f32_bits(new_points.cpu().numpy()), f32_bits(npts))
+    assert np.array_equal(f32_bits(gxyz.cpu().numpy()), f32_bits(gx))
 
 
 NN_CASES = [(2, 512, 128), (2, 8192, 1024), (2, 64, 16), (1, 100, 3), (1, 100, 2), (1, 7, 1),
@@ -323,22 +300,22 @@ NN_CASES = [(2, 512, 128), (2, 8192, 1024), (2, 64, 16), (1, 100, 3), (1, 100, 2
 @pytest.mark.parametrize("B,n,m", NN_CASES)
 def test_three_nn(env, B, n, m):
     pkg, O, torch, dev = env
-    x1 = _cloud(pkg, "scannet", B, n, seed=5)
-    x2 = _cloud(pkg, "scannet", B, m, seed=9)
+    x1 = clouds(pkg, "scannet", B, n, seed=5)
+    x2 = clouds(pkg, "scannet", B, m, seed=9)
     d, i = pkg.tf_interpolate.three_nn(torch.from_numpy(x1).to(dev), torch.from_numpy(x2).to(dev))
     rd, ri = O.three_nn(x1, x2)
     assert np.array_equal(i.cpu().numpy(), ri)
-    assert np.array_equal(_bits(d.cpu().numpy()), _bits(rd))
+    assert np.array_equal(f32_bits(d.cpu().numpy()), f32_bits(rd))
 
 
 def test_three_nn_ties(env):
     pkg, O, torch, dev = env
-    x2 = _cloud(pkg, "grid", 2, 300)
-    x1 = _cloud(pkg, "grid", 2, 500, seed=3) + np.float32(0.5)
+    x2 = clouds(pkg, "grid", 2, 300)
+    x1 = clouds(pkg, "grid", 2, 500, seed=3) + np.float32(0.5)
     d, i = pkg.tf_interpolate.three_nn(torch.from_numpy(x1).to(dev), torch.from_numpy(x2).to(dev))
     rd, ri = O.three_nn(x1, x2)
     assert np.array_equal(i.cpu().numpy(), ri)
-    assert np.array_equal(_bits(d.cpu().numpy()), _bits(rd))
+    assert np.array_equal(f32_bits(d.cpu().numpy()), f32_bits(rd))
 
 
 NN_GRID_CASES = [
@@ -359,14 +336,14 @@ def test_three_nn_grid(env, kind, B, n, m):
     ordering the work; fp_interpolate over it equals the fused scan."""
     pkg, O, torch, dev = env
     if kind == "fp4":
-        x1 = _cloud(pkg, "scannet", B, n, seed=4)
+        x1 = clouds(pkg, "scannet", B, n, seed=4)
         x2 = O.gather_point(x1, O.fps(x1, m))
     elif kind == "far":
-        x1 = _cloud(pkg, "uniform", B, n, seed=4) * np.float32(20.0) - np.float32(10.0)
-        x2 = _cloud(pkg, "scannet", B, m, seed=6)
+        x1 = clouds(pkg, "uniform", B, n, seed=4) * np.float32(20.0) - np.float32(10.0)
+        x2 = clouds(pkg, "scannet", B, m, seed=6)
     else:
-        x1 = _cloud(pkg, kind if kind != "dup" else "scannet", B, n, seed=4)
-        x2 = _cloud(pkg, kind, B, m, seed=8)
+        x1 = clouds(pkg, kind if kind != "dup" else "scannet", B, n, seed=4)
+        x2 = clouds(pkg, kind, B, m, seed=8)
         if kind == "grid":
             x1 = x1 + np.float32(0.5)
     t1, t2 = torch.from_numpy(x1).to(dev), torch.from_numpy(x2).to(dev)
@@ -378,7 +355,7 @@ def test_three_nn_grid(env, kind, B, n, m):
         for u in (None, ug):
             d, i = pkg.tf_interpolate.three_nn(t1, t2, known_grid=kg, unknown_grid=u)
             assert np.array_equal(i.cpu().numpy(), ri)
-            assert np.array_equal(_bits(d.cpu().numpy()), _bits(rd))
+            assert np.array_equal(f32_bits(d.cpu().numpy()), f32_bits(rd))
     if m >= 3:
         p1 = torch.from_numpy(pkg.synth.features_uniform(1, (B, n, 8))).to(dev)
         p2 = torch.from_numpy(pkg.synth.features_uniform(2, (B, m, 16))).to(dev)
@@ -402,14 +379,14 @@ def test_fp_grid_fused(env, kind, B, n, m, C1, C2):
     (pn2_fp_fused, bit for bit), with and without an unknown grid ordering the rows."""
     pkg, O, torch, dev = env
     if kind == "fp4":
-        x1 = _cloud(pkg, "scannet", B, n, seed=4)
+        x1 = clouds(pkg, "scannet", B, n, seed=4)
         x2 = O.gather_point(x1, O.fps(x1, m))
     elif kind == "far":
-        x1 = _cloud(pkg, "uniform", B, n, seed=4) * np.float32(20.0) - np.float32(10.0)
-        x2 = _cloud(pkg, "scannet", B, m, seed=6)
+        x1 = clouds(pkg, "uniform", B, n, seed=4) * np.float32(20.0) - np.float32(10.0)
+        x2 = clouds(pkg, "scannet", B, m, seed=6)
     else:
-        x1 = _cloud(pkg, kind if kind != "dup" else "scannet", B, n, seed=4)
-        x2 = _cloud(pkg, kind, B, m, seed=8)
+        x1 = clouds(pkg, kind if kind != "dup" else "scannet", B, n, seed=4)
+        x2 = clouds(pkg, kind, B, m, seed=8)
         if kind == "grid":
             x1 = x1 + np.float32(0.5)
     t1, t2 = torch.from_numpy(x1).to(dev), torch.from_numpy(x2).to(dev)
@@ -432,7 +409,7 @@ def test_fp_grid_fused(env, kind, B, n, m, C1, C2):
                                    p1.data_ptr() if C1 else None, C1, p2.data_ptr(), C2, B, n, m,
                                    out.data_ptr(), d.data_ptr(), i.data_ptr(), st) == 0
         assert np.array_equal(i.cpu().numpy(), ri)
-        assert np.array_equal(_bits(d.cpu().numpy()), _bits(rd))
+        assert np.array_equal(f32_bits(d.cpu().numpy()), f32_bits(rd))
         if m >= 3:
             assert torch.equal(out, ref)
             # the interpolated columns against the oracle too (not only the other HIP kernel),
@@ -440,7 +417,7 @@ def test_fp_grid_fused(env, kind, B, n, m, C1, C2):
             oref = O.fp_fused(x1, x2, p1.cpu().numpy() if C1 else None, p2.cpu().numpy())
             np.testing.assert_allclose(out.cpu().numpy(), oref, **TOL)
             if C1:
-                assert np.array_equal(_bits(out[..., C2:].cpu().numpy()), _bits(p1.cpu().numpy()))
+                assert np.array_equal(f32_bits(out[..., C2:].cpu().numpy()), f32_bits(p1.cpu().numpy()))
         # without the neighbour outputs, through the op wrapper
         a = pkg.pointnet_util.fp_interpolate(t1, t2, p1 if C1 else None, p2, unknown_grid=u)
         if m >= 3 and pkg.tf_interpolate.use_grid(n, m):
@@ -455,8 +432,8 @@ def test_fp_grid_fused(env, kind, B, n, m, C1, C2):
 @pytest.mark.parametrize("C", [1, 16, 128, 512])
 def test_three_interpolate_and_idw(env, C):
     pkg, O, torch, dev = env
-    x1 = _cloud(pkg, "scannet", 2, 1024, seed=2)
-    x2 = _cloud(pkg, "scannet", 2, 256, seed=7)
+    x1 = clouds(pkg, "scannet", 2, 1024, seed=2)
+    x2 = clouds(pkg, "scannet", 2, 256, seed=7)
     rd, ri = O.three_nn(x1, x2)
     w = pkg.tf_interpolate.idw_weights(torch.from_numpy(rd).to(dev)).cpu().numpy()
     rw = O.idw_weights(rd)
@@ -465,7 +442,7 @@ def test_three_interpolate_and_idw(env, C):
     got = pkg.tf_interpolate.three_interpolate(torch.from_numpy(pts).to(dev),
                                                torch.from_numpy(ri).to(dev),
                                                torch.from_numpy(rw).to(dev))
-    assert np.array_equal(_bits(got.cpu().numpy()), _bits(O.three_interpolate(pts, ri, rw)))
+    assert np.array_equal(f32_bits(got.cpu().numpy()), f32_bits(O.three_interpolate(pts, ri, rw)))
 
 
 @pytest.mark.parametrize("n,m,C1,C2", [(64, 16, 256, 512), (256, 64, 128, 256),
@@ -480,7 +457,7 @@ def test_three_interpolate_and_idw(env, C):
                                        (1024, 256, 6, 64), (512, 64, 2, 52), (256, 64, 10, 128)])
 def test_fp_fused(env, n, m, C1, C2):
     pkg, O, torch, dev = env
-    x1 = _cloud(pkg, "scannet", 2, n, seed=11)
+    x1 = clouds(pkg, "scannet", 2, n, seed=11)
     x2 = O.gather_point(x1, O.fps(x1, m))
     p1 = pkg.synth.features_uniform(1, (2, n, C1)) if C1 else None
     p2 = pkg.synth.features_uniform(2, (2, m, C2))
@@ -489,7 +466,7 @@ def test_fp_fused(env, n, m, C1, C2):
     ref = O.fp_fused(x1, x2, p1, p2)
     np.testing.assert_allclose(got, ref, **TOL)
     if C1:
-        assert np.array_equal(_bits(got[..., C2:]), _bits(p1))  # the concat is a copy
+        assert np.array_equal(f32_bits(got[..., C2:]), f32_bits(p1))  # the concat is a copy
 
 
 @pytest.mark.parametrize("ns,C", [(32, 64), (32, 128), (32, 512), (16, 64), (64, 256),
@@ -555,7 +532,7 @@ def test_group_pool(env, mode):
 def test_gradients(env):
     pkg, O, torch, dev = env
     rng = np.random.default_rng(8)
-    x = _cloud(pkg, "scannet", 2, 1024)
+    x = clouds(pkg, "scannet", 2, 1024)
     idx = rng.integers(0, 1024, (2, 200)).astype(np.int32)
     og = rng.standard_normal((2, 200, 3)).astype(np.float32)
     g = pkg.tf_sampling.gather_point_grad(torch.from_numpy(x).to(dev),
@@ -567,7 +544,7 @@ def test_gradients(env):
     g = pkg.tf_grouping.group_point_grad(torch.from_numpy(pts).to(dev),
                                          torch.from_numpy(gi).to(dev), torch.from_numpy(go).to(dev))
     np.testing.assert_allclose(g.cpu().numpy(), O.group_point_grad(1024, gi, go), **TOL)
-    d, i = O.three_nn(_cloud(pkg, "scannet", 2, 512, 3), _cloud(pkg, "scannet", 2, 128, 4))
+    d, i = O.three_nn(clouds(pkg, "scannet", 2, 512, 3), clouds(pkg, "scannet", 2, 128, 4))
     w = O.idw_weights(d)
     go = rng.standard_normal((2, 512, 16)).astype(np.float32)
     g = pkg.tf_interpolate.three_interpolate_grad(torch.zeros((2, 128, 16), device=dev),
@@ -624,16 +601,16 @@ def test_hip_reproduces_golden(env, path):
             assert np.array_equal(cnt, d["pts_cnt"])
     elif op == "group_point(+grad)":
         out = pkg.tf_grouping.group_point(T(d["points"]), T(d["idx"])).cpu().numpy()
-        assert np.array_equal(_bits(out), _bits(d["out"]))
+        assert np.array_equal(f32_bits(out), f32_bits(d["out"]))
         g = pkg.tf_grouping.group_point_grad(T(d["points"]), T(d["idx"]), T(d["grad_out"]))
         np.testing.assert_allclose(g.cpu().numpy(), d["grad_points"], **TOL)
     elif op == "three_nn":
         dist, idx = pkg.tf_interpolate.three_nn(T(d["xyz1"]), T(d["xyz2"]))
         assert np.array_equal(idx.cpu().numpy(), d["idx"])
-        assert np.array_equal(_bits(dist.cpu().numpy()), _bits(d["dist"]))
+        assert np.array_equal(f32_bits(dist.cpu().numpy()), f32_bits(d["dist"]))
     elif op in ("three_interpolate", "three_interpolate(+grad)"):
         out = pkg.tf_interpolate.three_interpolate(T(d["points"]), T(d["idx"]), T(d["weight"]))
-        assert np.array_equal(_bits(out.cpu().numpy()), _bits(d["out"]))
+        assert np.array_equal(f32_bits(out.cpu().numpy()), f32_bits(d["out"]))
         if "grad_out" in d:
             g = pkg.tf_interpolate.three_interpolate_grad(T(d["points"]), T(d["idx"]),
                                                           T(d["weight"]), T(d["grad_out"]))
@@ -641,12 +618,12 @@ def test_hip_reproduces_golden(env, path):
     elif op == "selection_sort":
         oi, oo = pkg.tf_grouping.select_top_k(int(meta["k"]), T(d["dist"]))
         assert np.array_equal(oi.cpu().numpy(), d["outi"])
-        assert np.array_equal(_bits(oo.cpu().numpy()), _bits(d["out"]))
+        assert np.array_equal(f32_bits(oo.cpu().numpy()), f32_bits(d["out"]))
     elif op == "farthest_point_sample":
         idx, new_xyz = pkg.tf_sampling.farthest_point_sample_and_gather(int(meta["npoint"]),
                                                                         T(d["xyz"]))
         assert np.array_equal(idx.cpu().numpy(), d["idx"])
-        assert np.array_equal(_bits(new_xyz.cpu().numpy()), _bits(d["new_xyz"]))
+        assert np.array_equal(f32_bits(new_xyz.cpu().numpy()), f32_bits(d["new_xyz"]))
     elif op == "prob_sample":
         got = pkg.tf_sampling.prob_sample(T(d["inp"]), T(d["inpr"]))
         assert np.array_equal(got.cpu().numpy(), d["out"])
@@ -716,7 +693,7 @@ def test_select_top_k(env, kind, B, m, n, k):
     outi, out = pkg.tf_grouping.select_top_k(k, torch.from_numpy(d).to(dev))
     ri, ro = O.selection_sort(d, k)
     assert np.array_equal(outi.cpu().numpy(), ri)
-    assert np.array_equal(_bits(out.cpu().numpy()), _bits(ro))
+    assert np.array_equal(f32_bits(out.cpu().numpy()), f32_bits(ro))
     if O.have_ref_gpu():
         dt = torch.from_numpy(d).to(dev)
         gi = torch.zeros((B, m, n), dtype=torch.int32, device=dev)
@@ -732,19 +709,19 @@ def test_select_top_k(env, kind, B, m, n, k):
 def test_knn_point(env, kind, B, n, m, c, k):
     pkg, O, torch, dev = env
     if c == 3:
-        x = _cloud(pkg, kind, B, n)
+        x = clouds(pkg, kind, B, n)
     else:
         x = np.random.default_rng(c).random((B, n, c)).astype(np.float32)
     q = x[:, ::max(1, n // m)][:, :m].copy()
     val, idx = pkg.tf_grouping.knn_point(k, torch.from_numpy(x).to(dev), torch.from_numpy(q).to(dev))
     rv, ri = O.knn_point(k, x, q)
     assert np.array_equal(idx.cpu().numpy(), ri)
-    assert np.array_equal(_bits(val.cpu().numpy()), _bits(rv))
+    assert np.array_equal(f32_bits(val.cpu().numpy()), f32_bits(rv))
 
 
 def test_sample_and_group_knn(env):
     pkg, O, torch, dev = env
-    x = _cloud(pkg, "scannet", 2, 2048, seed=3)
+    x = clouds(pkg, "scannet", 2, 2048, seed=3)
     pts = pkg.synth.features_uniform(5, (2, 2048, 8))
     new_xyz, new_points, idx, grouped_xyz = pkg.pointnet_util.sample_and_group(
         128, 0.2, 16, torch.from_numpy(x).to(dev), torch.from_numpy(pts).to(dev), knn=True)
@@ -752,7 +729,7 @@ def test_sample_and_group_knn(env):
     _, ridx = O.knn_point(16, x, rnx)
     assert np.array_equal(idx.cpu().numpy(), ridx)
     rnp, rgx = O.group_concat(x, pts, rnx, ridx)
-    assert np.array_equal(_bits(new_points.cpu().numpy()), _bits(rnp))
+    assert np.array_equal(f32_bits(new_points.cpu().numpy()), f32_bits(rnp))
 
 
 @pytest.mark.parametrize("kind,B,N,npoints", [
@@ -765,7 +742,7 @@ def test_fps_chain(env, kind, B, N, npoints):
     """pn2_fps_chain (every SSG sampler of a cloud in one workgroup) gives exactly the
     per-stage farthest_point_sample_and_gather results, and the oracle's indices."""
     pkg, O, torch, dev = env
-    x = _cloud(pkg, kind, B, N)
+    x = clouds(pkg, kind, B, N)
     xt = torch.from_numpy(x).to(dev)
     outs = pkg.tf_sampling.farthest_point_sample_chain(npoints, xt)
     cur, cur_np = xt, x
@@ -810,7 +787,7 @@ def test_fps_chain_grid(env, kind, B, N, npoints):
     equals the fused scan bit for bit, and an explicit-edge known grid falls back to the
     in-workgroup build with the same result."""
     pkg, O, torch, dev = env
-    x = _cloud(pkg, kind, B, N)
+    x = clouds(pkg, kind, B, N)
     xt = torch.from_numpy(x).to(dev)
     ref = pkg.tf_sampling.farthest_point_sample_chain(npoints, xt)
     outs = [(torch.empty_like(i), torch.empty_like(n)) for i, n in ref]
@@ -861,7 +838,7 @@ def test_fps_chain_grid(env, kind, B, N, npoints):
                 B, N, m, out.data_ptr(), d.data_ptr(), i.data_ptr(), st.cuda_stream) == 0
             assert torch.equal(out, fused)
             assert np.array_equal(i.cpu().numpy(), ri)
-            assert np.array_equal(_bits(d.cpu().numpy()), _bits(rd))
+            assert np.array_equal(f32_bits(d.cpu().numpy()), f32_bits(rd))
     if pkg.tf_interpolate.use_grid(N, m):
         a = pkg.pointnet_util.fp_interpolate(xt, x2, p1, p2, known_grid=g0, unknown_grid=ug)
         assert torch.equal(a, fused)

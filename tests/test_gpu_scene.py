@@ -15,10 +15,10 @@ import os
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, gpu_available
+from conftest import PKG_NAME
+from support import gpu_marks
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 

@@ -6,6 +6,8 @@ gradient sums 1e-5 (north_star)."""
 import numpy as np
 import pytest
 
+from support import f32_bits
+
 pytestmark = pytest.mark.gpu
 TOL = dict(rtol=1e-5, atol=1e-5)
 
@@ -24,10 +26,6 @@ def _crops(pn2hip, ids, N):
     return pn2hip.synth.batch(ids, N, "scannet")[0]
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
-
-
 @pytest.mark.parametrize("N,M", [(1024, 256), (8192, 1024), (20000, 512)])
 def test_fps_gather(env, N, M):
     pn2hip, ops, O, torch, dev = env
@@ -38,9 +36,9 @@ def test_fps_gather(env, N, M):
     want = O.fps(x, M)
     assert np.array_equal(idx.cpu().numpy(), want)
     assert np.array_equal(i2.cpu().numpy(), want)
-    assert np.array_equal(_bits(nx.cpu().numpy()), _bits(O.gather_point(x, want)))
+    assert np.array_equal(f32_bits(nx.cpu().numpy()), f32_bits(O.gather_point(x, want)))
     g = ops.gather_point(xt, idx)
-    assert np.array_equal(_bits(g.cpu().numpy()), _bits(O.gather_point(x, want)))
+    assert np.array_equal(f32_bits(g.cpu().numpy()), f32_bits(O.gather_point(x, want)))
 
 
 @pytest.mark.parametrize("N,M,r,ns", [(8192, 1024, 0.1, 32), (1024, 256, 0.2, 32),
@@ -55,12 +53,12 @@ def test_ball_query_group(env, N, M, r, ns):
     assert np.array_equal(idx.cpu().numpy(), widx) and np.array_equal(cnt.cpu().numpy(), wcnt)
     pts = np.random.default_rng(0).standard_normal((2, N, 6)).astype(np.float32)
     pt = torch.from_numpy(pts).to(dev)
-    assert np.array_equal(_bits(ops.group_point(pt, idx).cpu().numpy()),
-                          _bits(O.group_point(pts, widx)))
+    assert np.array_equal(f32_bits(ops.group_point(pt, idx).cpu().numpy()),
+                          f32_bits(O.group_point(pts, widx)))
     gx, np_ = ops.group_concat(xt, pt, qt, idx)
     wnp, wgx = O.group_concat(x, pts, q, widx)
-    assert np.array_equal(_bits(np_.cpu().numpy()), _bits(wnp))
-    assert np.array_equal(_bits(gx.cpu().numpy()), _bits(wgx))
+    assert np.array_equal(f32_bits(np_.cpu().numpy()), f32_bits(wnp))
+    assert np.array_equal(f32_bits(gx.cpu().numpy()), f32_bits(wgx))
 
 
 @pytest.mark.parametrize("n,m,C", [(8192, 1024, 128), (256, 64, 256)])
@@ -71,13 +69,13 @@ def test_interp(env, n, m, C):
     xt, kt = torch.from_numpy(x).to(dev), torch.from_numpy(k).to(dev)
     d, i = ops.three_nn(xt, kt)
     wd, wi = O.three_nn(x, k)
-    assert np.array_equal(i.cpu().numpy(), wi) and np.array_equal(_bits(d.cpu().numpy()), _bits(wd))
+    assert np.array_equal(i.cpu().numpy(), wi) and np.array_equal(f32_bits(d.cpu().numpy()), f32_bits(wd))
     w = ops.idw_weights(d)
     np.testing.assert_allclose(w.cpu().numpy(), O.idw_weights(wd), **TOL)
     p2 = np.random.default_rng(1).uniform(-1, 1, (2, m, C)).astype(np.float32)
     ww = O.idw_weights(wd)
     out = ops.three_interpolate(torch.from_numpy(p2).to(dev), i, torch.from_numpy(ww).to(dev))
-    assert np.array_equal(_bits(out.cpu().numpy()), _bits(O.three_interpolate(p2, wi, ww)))
+    assert np.array_equal(f32_bits(out.cpu().numpy()), f32_bits(O.three_interpolate(p2, wi, ww)))
     p1 = np.random.default_rng(2).uniform(-1, 1, (2, n, 6)).astype(np.float32)
     fp = ops.fp_fused(xt, kt, torch.from_numpy(p1).to(dev), torch.from_numpy(p2).to(dev))
     np.testing.assert_allclose(fp.cpu().numpy(), O.fp_fused(x, k, p1, p2), **TOL)
@@ -90,7 +88,7 @@ def test_knn_select_attn_pool(env):
     q = O.gather_point(x, O.fps(x, 128))
     v, i = ops.knn_point(16, torch.from_numpy(x).to(dev), torch.from_numpy(q).to(dev))
     wv, wi = O.knn_point(16, x, q)
-    assert np.array_equal(i.cpu().numpy(), wi) and np.array_equal(_bits(v.cpu().numpy()), _bits(wv))
+    assert np.array_equal(i.cpu().numpy(), wi) and np.array_equal(f32_bits(v.cpu().numpy()), f32_bits(wv))
     dist = rng.integers(0, 50, (2, 64, 300)).astype(np.float32)  # many ties
     oi, oo = ops.select_top_k(10, torch.from_numpy(dist).to(dev))
     woi, woo = O.selection_sort(dist, 10)
@@ -208,7 +206,7 @@ def test_sa_layer_torch_compile(env):
     q = O.gather_point(x, fidx)
     widx, _ = O.ball_query(x, q, 0.2, 32)
     wnp, _ = O.group_concat(x, pts, q, widx)
-    assert np.array_equal(_bits(got[1].cpu().numpy()), _bits(wnp))
+    assert np.array_equal(f32_bits(got[1].cpu().numpy()), f32_bits(wnp))
 
 
 def test_reference_names_drop_in(env):

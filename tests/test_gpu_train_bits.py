@@ -26,10 +26,10 @@ import pytest
 
 if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from conftest import PKG_NAME, gpu_available  # noqa: E402
+from conftest import PKG_NAME  # noqa: E402
+from support import gpu_marks  # noqa: E402
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "train_bits.json")
 EPS = 1e-3

@@ -20,10 +20,10 @@ import os
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, ROOT, gpu_available
+from conftest import PKG_NAME, ROOT
+from support import gpu_marks
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
+pytestmark = gpu_marks
 
 
 def _time(torch, fn, reps=5):

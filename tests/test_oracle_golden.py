@@ -15,12 +15,10 @@ import os
 import numpy as np
 import pytest
 
+from support import f32_bits
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = sorted(glob.glob(os.path.join(HERE, "golden", "*.npz")))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 def _load(path):
@@ -56,32 +54,32 @@ def test_oracle_reproduces_golden(orc, path):
         assert (idx[~hit] == 0).all() and (d["idx"][~hit] == -1).all()
     elif op == "group_point(+grad)":
         assert np.array_equal(orc.ball_query(d["xyz1"], d["xyz2"], 0.3, 32)[0], d["idx"])
-        assert np.array_equal(_bits(orc.group_point(d["points"], d["idx"])), _bits(d["out"]))
+        assert np.array_equal(f32_bits(orc.group_point(d["points"], d["idx"])), f32_bits(d["out"]))
         g = orc.group_point_grad(d["points"].shape[1], d["idx"], d["grad_out"])
-        assert np.array_equal(_bits(g), _bits(d["grad_points"]))
+        assert np.array_equal(f32_bits(g), f32_bits(d["grad_points"]))
     elif op == "three_nn":
         dist, idx = orc.three_nn(d["xyz1"], d["xyz2"])
         assert np.array_equal(idx, d["idx"])
-        assert np.array_equal(_bits(dist), _bits(d["dist"]))
+        assert np.array_equal(f32_bits(dist), f32_bits(d["dist"]))
     elif op == "three_interpolate(+grad)":
         assert np.array_equal(orc.three_nn(d["xyz1"], d["xyz2"])[1], d["idx"])
         out = orc.three_interpolate(d["points"], d["idx"], d["weight"])
-        assert np.array_equal(_bits(out), _bits(d["out"]))
+        assert np.array_equal(f32_bits(out), f32_bits(d["out"]))
         g = orc.three_interpolate_grad(d["points"].shape[1], d["idx"], d["weight"], d["grad_out"])
-        assert np.array_equal(_bits(g), _bits(d["grad_points"]))
+        assert np.array_equal(f32_bits(g), f32_bits(d["grad_points"]))
     elif op == "three_interpolate":
         out = orc.three_interpolate(d["points"], d["idx"], d["weight"])
-        assert np.array_equal(_bits(out), _bits(d["out"]))
+        assert np.array_equal(f32_bits(out), f32_bits(d["out"]))
     elif op == "selection_sort":
         oi, oo = orc.selection_sort(d["dist"], int(meta["k"]))
         assert np.array_equal(oi, d["outi"])
-        assert np.array_equal(_bits(oo), _bits(d["out"]))
+        assert np.array_equal(f32_bits(oo), f32_bits(d["out"]))
     elif op == "prob_sample":
         assert np.array_equal(orc.prob_sample(d["inp"], d["inpr"]), d["out"])
     elif op == "farthest_point_sample":
         idx = orc.fps(d["xyz"], int(meta["npoint"]))
         assert np.array_equal(idx, d["idx"]), f"{(idx != d['idx']).sum()} FPS indices differ"
-        assert np.array_equal(_bits(orc.gather_point(d["xyz"], idx)), _bits(d["new_xyz"]))
+        assert np.array_equal(f32_bits(orc.gather_point(d["xyz"], idx)), f32_bits(d["new_xyz"]))
     else:
         pytest.fail(f"unknown golden op {op}")
 
@@ -112,12 +110,12 @@ def test_oracle_vs_reference_cpu_random(orc, pn2, seed):
         assert np.array_equal(got[hit], ref[hit])
     d_ref, i_ref = orc.ref_three_nn(q, x[:, :max(1, N // 4)])
     d, i = orc.three_nn(q, x[:, :max(1, N // 4)])
-    assert np.array_equal(i, i_ref) and np.array_equal(_bits(d), _bits(d_ref))
+    assert np.array_equal(i, i_ref) and np.array_equal(f32_bits(d), f32_bits(d_ref))
     C = int(rng.integers(1, 40))
     pts = rng.standard_normal((B, max(1, N // 4), C)).astype(np.float32)
     w = orc.idw_weights(d)
-    assert np.array_equal(_bits(orc.three_interpolate(pts, i, w)),
-                          _bits(orc.ref_three_interpolate(pts, i, w)))
+    assert np.array_equal(f32_bits(orc.three_interpolate(pts, i, w)),
+                          f32_bits(orc.ref_three_interpolate(pts, i, w)))
 
 
 def test_fps_restatement_known_answers(orc):

@@ -27,13 +27,13 @@ windows) and the bytes its algorithm has to move (computed from the shape) over 
 against the measured copy peak of 6.03 TB/s. The two GEMMs through pn2_shared_mlp
 include their pn2_mlp_pack.
 """
-import argparse
 import importlib
 import json
 import os
 import statistics
-import subprocess
 import sys
+
+from _timing import main, windows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -41,25 +41,6 @@ COPY_PEAK_TBS = 6.03
 SHAPES = {"SA1_conv1": (524288, 32, 32), "FP4_conv0": (131072, 128, 128),
           "SA4_conv1": (8192, 256, 512)}
 EPS = 1e-3
-
-
-def windows(torch, fns, repeats, iters):
-    """Median time per call (us) of each fn: `repeats` windows of `iters` calls, alternating."""
-    for fn in fns:
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    times = [[] for _ in fns]
-    for _ in range(repeats):
-        for k, fn in enumerate(fns):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(iters):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            times[k].append(e0.elapsed_time(e1) / iters * 1e3)
-    return [statistics.median(t) for t in times], [(min(t), max(t)) for t in times]
 
 
 def one(name, repeats, iters):
@@ -103,7 +84,9 @@ def one(name, repeats, iters):
     for nm, a, t in zip(("x", "w", "b", "gamma", "beta"), gh, leaves):
         scale = max(float(t.grad.abs().max()), 1e-6)
         diffs[nm] = float((a - t.grad).abs().max()) / scale
-    (t_hip, t_par), spread = windows(torch, [hip, parent], repeats, iters)
+    times = windows(torch, [hip, parent], repeats, iters)
+    t_hip, t_par = (statistics.median(t) for t in times)
+    spread = [(min(t), max(t)) for t in times]
 
     # the C entry points alone
     xd, wd, bd, gd, btd = (t.detach() for t in leaves)
@@ -145,7 +128,7 @@ def one(name, repeats, iters):
         fn()
     kern = {}
     for nm, (fn, nbytes) in calls.items():
-        (us,), _ = windows(torch, [fn], repeats, iters)
+        us = statistics.median(windows(torch, [fn], repeats, iters)[0])
         kern[nm] = {"us": round(us, 1), "bytes": nbytes, "GBps": round(nbytes / us / 1e3, 1),
                     "frac_copy_peak": round(nbytes / us / 1e6 / COPY_PEAK_TBS, 3)}
     print(json.dumps({
@@ -158,35 +141,5 @@ def one(name, repeats, iters):
         "entry_points": kern}))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--timeout", type=int, default=150, help="seconds per shape")
-    ap.add_argument("--out", default=None, help="write the results as one JSON file")
-    ap.add_argument("--one", choices=sorted(SHAPES), help=argparse.SUPPRESS)
-    args = ap.parse_args()
-    if args.repeats < 5:
-        ap.error("--repeats must be at least 5")
-    if args.one:
-        return one(args.one, args.repeats, args.iters)
-    results = []
-    for name in SHAPES:
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__),
-               "--one", name, "--repeats", str(args.repeats), "--iters", str(args.iters)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        sys.stderr.write(r.stderr[-2000:])
-        if r.returncode != 0:
-            sys.exit(f"{name}: exit status {r.returncode}; stopping")
-        line = r.stdout.strip().splitlines()[-1]
-        print(line, flush=True)
-        results.append(json.loads(line))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump({"copy_peak_TBps": COPY_PEAK_TBS, "shapes": results}, f, indent=1)
-            f.write("\n")
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, SHAPES, one, timeout=150, header={"copy_peak_TBps": COPY_PEAK_TBS})

@@ -24,38 +24,19 @@ pass, after reset_peak_memory_stats, less the memory held before the pass (the i
 `out_equal` and `max_rel_grad_diff` compare the two sides: the pooled outputs must be bit-equal;
 the gradients differ in the last bits of reordered fp32 sums.
 """
-import argparse
 import importlib
 import json
 import os
 import statistics
-import subprocess
 import sys
+
+from _timing import main, windows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 SHAPES = {"SA1_conv2": (16384, 32, 32, 64), "SA2_conv2": (4096, 32, 64, 128),
           "SA4_conv2": (256, 32, 256, 512)}
 EPS = 1e-3
-
-
-def windows(torch, fns, repeats, iters):
-    """Per fn the times per call (us) of `repeats` windows of `iters` calls, alternating."""
-    for fn in fns:
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    times = [[] for _ in fns]
-    for _ in range(repeats):
-        for k, fn in enumerate(fns):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(iters):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            times[k].append(e0.elapsed_time(e1) / iters * 1e3)
-    return times
 
 
 def one(name, repeats, iters):
@@ -124,35 +105,5 @@ def one(name, repeats, iters):
         "max_rel_grad_diff": {k: float(f"{v:.3g}") for k, v in diffs.items()}}))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--timeout", type=int, default=120, help="seconds per shape")
-    ap.add_argument("--out", default=None, help="write the results as one JSON file")
-    ap.add_argument("--one", choices=sorted(SHAPES), help=argparse.SUPPRESS)
-    args = ap.parse_args()
-    if args.repeats < 5:
-        ap.error("--repeats must be at least 5")
-    if args.one:
-        return one(args.one, args.repeats, args.iters)
-    results = []
-    for name in SHAPES:
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__),
-               "--one", name, "--repeats", str(args.repeats), "--iters", str(args.iters)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        sys.stderr.write(r.stderr[-2000:])
-        if r.returncode != 0:
-            sys.exit(f"{name}: exit status {r.returncode}; stopping")
-        line = r.stdout.strip().splitlines()[-1]
-        print(line, flush=True)
-        results.append(json.loads(line))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump({"shapes": results}, f, indent=1)
-            f.write("\n")
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, SHAPES, one)

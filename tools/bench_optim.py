@@ -18,26 +18,19 @@ stream (so a candidate bound by its host-side launches is charged for them); the
 and the range are reported. For `adam` the C entry point alone is timed too, with the bytes the
 update has to move (16 read and 12 written per element) over that time.
 """
-import argparse
 import importlib
 import json
 import os
 import statistics
-import subprocess
 import sys
+
+from _timing import main, summary, windows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from bench_head_train import windows  # noqa: E402
 
 ROWS, NCLASS = 16 * 8192, 21
 SHAPES = ("adam", "metrics")
-
-
-def summary(times):
-    return {"us": round(statistics.median(times), 1),
-            "min_max_us": [round(min(times), 1), round(max(times), 1)]}
 
 
 def one(name, repeats, iters):
@@ -121,35 +114,5 @@ def one(name, repeats, iters):
     print(json.dumps(res))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--timeout", type=int, default=120, help="seconds per shape")
-    ap.add_argument("--out", default=None, help="write the results as one JSON file")
-    ap.add_argument("--one", choices=SHAPES, help=argparse.SUPPRESS)
-    args = ap.parse_args()
-    if args.repeats < 5:
-        ap.error("--repeats must be at least 5")
-    if args.one:
-        return one(args.one, args.repeats, args.iters)
-    results = []
-    for name in SHAPES:
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__),
-               "--one", name, "--repeats", str(args.repeats), "--iters", str(args.iters)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        sys.stderr.write(r.stderr[-2000:])
-        if r.returncode != 0:
-            sys.exit(f"{name}: exit status {r.returncode}; stopping")
-        line = r.stdout.strip().splitlines()[-1]
-        print(line, flush=True)
-        results.append(json.loads(line))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump({"shapes": results}, f, indent=1)
-            f.write("\n")
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, SHAPES, one, iters=20)
