@@ -40,6 +40,7 @@
  *                        :57-60 (fc1, fc2)
  *   conv2d, is_training  tf_util.py:165-185, :512-531 (batch     → pn2_bn_stats, pn2_bn_act_fwd,
  *                        statistics) and its gradients             pn2_bn_act_bwd, pn2_mlp_wgrad
+ *                        (bf16 mode: the weight gradient)           pn2_mlp_wgrad_bf16
  *   conv2d, is_training, pointnet_util.py:106-136 (the last MLP  → pn2_bn_act_pool_fwd,
  *     + max pool         layer and reduce_max over nsample)        pn2_bn_act_pool_bwd
  *   AttentionLayer,      attention_layer.py:10-45, :256-259, :303 → pn2_attn_kv_reduce,
@@ -547,7 +548,26 @@ int pn2_mlp_pack(const float* weight, const float* bias, const float* bn_scale,
  * pn2_group_mlp, pn2_fp_mlp, pn2_shared_mlp, pn2_shared_mlp_plan and pn2_group_mlp_attention
  * honour the flag per layer; in pn2_group_mlp_attention qkv[1] and qkv[2] (key, value) may be
  * bf16, qkv[0] (the query, VALU work on the fp32 layout) may not: PN2_EINVAL before any
- * launch. The training entry points take no packed layers and stay fp32. */
+ * launch.
+ *
+ * Training in bf16 mode (also an opt-in; the training entry points take no packed layers, the
+ * caller packs per step). One tf_util.conv2d layer with is_training=True computes
+ *   forward          y[r][o]      = sum_f bf16(x[r][f]) * bf16(W[f][o]) + b[o]
+ *                    pn2_mlp_pack_bf16 of W, b (no batch norm, no activation), then
+ *                    pn2_shared_mlp with PN2_MLP_BF16: the layer contract above
+ *   input gradient   grad_x[r][f] = sum_o bf16(grad_y[r][o]) * bf16(W[f][o])
+ *                    the same kernel over a pn2_mlp_pack_bf16 of W^T
+ *   weight gradient  grad_w[f][o] = sum_r bf16(x[r][f]) * bf16(grad_y[r][o])
+ *                    pn2_mlp_wgrad_bf16
+ * - bf16(.) is round-to-nearest-even from fp32, the products are exact, the sums are fp32 on
+ *   the matrix cores, and the weight gradient adds its slabs in double as pn2_mlp_wgrad does;
+ * - everything else stays fp32 and unrounded: the batch statistics, the activation and its
+ *   backward (grad_y, grad_gamma, grad_beta, the bias gradient), the fused max pool and its
+ *   arg, the moving averages, Adam and the stored variables;
+ * - the variables are fp32 master copies, rounded per step when packed;
+ * - the backward treats the rounding as the identity (straight-through);
+ * - subnormal operands are out of contract, as above.
+ * Without the opt-in the training layers are the fp32 ones, unchanged. */
 size_t pn2_mlp_packed_size_bf16(int cin, int cout);
 int pn2_mlp_pack_bf16(const float* weight, const float* bias, const float* bn_scale,
                       const float* bn_shift, int cin, int cout, void* packed,
@@ -676,6 +696,16 @@ int pn2_bn_act_pool_bwd(const float* grad_out, const int* arg, const float* y, l
 size_t pn2_mlp_wgrad_workspace_size(long long rows, int cin, int cout);
 int pn2_mlp_wgrad(const float* x, const float* grad_y, long long rows, int cin, int cout,
                   float* grad_w, void* workspace, size_t workspace_bytes, pn2_stream_t stream);
+/* The weight gradient of a training layer in bf16 mode (the contract is at pn2_mlp_pack_bf16):
+ *   grad_w[f][o] = sum_r bf16(x[r][f]) * bf16(grad_y[r][o])
+ * on v_mfma_f32_32x32x16_bf16: x and grad_y are read as fp32, straight from the row-major
+ * tensors, and rounded on the way into the matrix cores (one MFMA covers 16 rows). Arguments,
+ * checks, slabs, parts, workspace (pn2_mlp_wgrad_workspace_size) and stage 2 are pn2_mlp_wgrad's:
+ * a slab's tile is four fp32 chains of 16 MFMAs from zero, added in wave order, slabs and parts
+ * in double. No atomics: two runs give equal bits. */
+int pn2_mlp_wgrad_bf16(const float* x, const float* grad_y, long long rows, int cin, int cout,
+                       float* grad_w, void* workspace, size_t workspace_bytes,
+                       pn2_stream_t stream);
 
 /* ---------------------------------------------------------------- attention, training --- */
 /* The AttentionLayer of the attention SA modules (attention_layer.py:10-45, :256-259) with

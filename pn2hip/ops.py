@@ -29,6 +29,13 @@ idw_weights, fp_fused, group_pool, *_grad), and the training-mode shared-MLP lay
                               need_grad_x)
                                        -> (grad_x, grad_w, grad_b, grad_gamma, grad_beta)
 
+The same four ops with the layer's three GEMMs on the bf16 matrix cores (an opt-in; the contract
+is at pn2_mlp_pack_bf16 in include/pn2hip.h: operands rounded to bf16, fp32 sums, everything
+after y and everything in the backward but the two GEMMs unchanged), listed in TRAIN_BF16_NAMES:
+
+    mlp_layer_train_bf16, mlp_layer_train_bf16_grad, mlp_layer_train_pool_bf16,
+    mlp_layer_train_pool_bf16_grad                     arguments and results as above
+
 and the training-mode AttentionLayer of the attention SA modules (csrc/attn_train.hip):
 
     attn_kv_train(x, wq, bq, wk, bk, wv, bv, add_max)   attention_layer.py:10-45, :256-259: x
@@ -119,7 +126,10 @@ NAMES = ("farthest_point_sample", "farthest_point_sample_and_gather", "gather_po
 # three_interpolate ops excepted)
 HOST_NAMES = ("scene_vote", "scene_labels", "map_back_rows", "label_lut")
 FEED_NAMES = ("feed_batch", "val_select", "val_chunks")
-for _n in NAMES + HOST_NAMES + FEED_NAMES:
+# the training layer's opt-in bf16 matrix-core mode (device-only, like NAMES)
+TRAIN_BF16_NAMES = ("mlp_layer_train_bf16", "mlp_layer_train_bf16_grad",
+                    "mlp_layer_train_pool_bf16", "mlp_layer_train_pool_bf16_grad")
+for _n in NAMES + HOST_NAMES + FEED_NAMES + TRAIN_BF16_NAMES:
     globals()[_n] = getattr(_ops, _n)
 
-__all__ = list(NAMES + HOST_NAMES + FEED_NAMES)
+__all__ = list(NAMES + HOST_NAMES + FEED_NAMES + TRAIN_BF16_NAMES)

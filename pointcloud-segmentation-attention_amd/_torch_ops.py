@@ -6,7 +6,8 @@ reference registers gradients for, w.r.t. the points only (tf_sampling.py:44-48 
 tf_grouping.py:42-46 GroupPoint, tf_interpolate.py:29-34 ThreeInterpolate), plus the attention
 reduction (TF autodiff through attention_layer.py:35-42, all of Q, K, V) and the training-mode
 shared-MLP layer (mlp_layer_train, and mlp_layer_train_pool for the layer fused with the max
-pool over nsample: x, weight, bias, gamma, beta; csrc/mlp_train.hip), the training-mode attention
+pool over nsample: x, weight, bias, gamma, beta; csrc/mlp_train.hip; their _bf16 namesakes, the
+layer's opt-in bf16 matrix-core mode, use the _bf16 grad ops), the training-mode attention
 layer (attn_kv_train: x and the three Dense layers' variables; csrc/attn_train.hip) and the
 stand-alone batch-statistics batch norm (bn_train: x, gamma, beta). The training head's ops
 (csrc/head_train.hip: dropout, the same op on the gradient with the same seed; softmax_xent,
@@ -81,21 +82,28 @@ def _register_autograd():
         Q, K, V = ctx.saved_tensors
         return tuple(torch.ops.pn2.attn_reduce_grad(Q, K, V, grad.contiguous()))
 
-    def mlp_setup(ctx, inputs, output):
+    def mlp_setup(ctx, inputs, output, bf16=False):
         # mlp_layer_train returns (out, y, mean, var), mlp_layer_train_pool the pool's arg too
         x, weight, bias, gamma, beta, eps, relu = inputs
         out, y, mean, var, *arg = output
         ctx.mark_non_differentiable(y, mean, var, *arg)
         ctx.save_for_backward(x, weight, y, mean, var, gamma, beta, *arg)
-        ctx.eps, ctx.relu, ctx.has_bias = eps, relu, bias is not None
+        ctx.eps, ctx.relu, ctx.has_bias, ctx.bf16 = eps, relu, bias is not None, bf16
+
+    def mlp_setup_bf16(ctx, inputs, output):
+        mlp_setup(ctx, inputs, output, bf16=True)
 
     def mlp_bwd(ctx, grad_out, *_):
         x, weight, y, mean, var, gamma, beta, *arg = ctx.saved_tensors
         # pooled, grad_out is (..., cout): the (..., ns, cout) gradient of the activation never
         # exists. The input gradient is one more GEMM: skipped when nothing upstream needs it
-        # (SA1's first layer reads coordinates)
+        # (SA1's first layer reads coordinates). A _bf16 forward gets the _bf16 grad op: its two
+        # GEMMs run on the bf16 matrix cores too (the rounding is straight-through)
         pn2 = torch.ops.pn2
-        grad = pn2.mlp_layer_train_pool_grad if arg else pn2.mlp_layer_train_grad
+        if ctx.bf16:
+            grad = pn2.mlp_layer_train_pool_bf16_grad if arg else pn2.mlp_layer_train_bf16_grad
+        else:
+            grad = pn2.mlp_layer_train_pool_grad if arg else pn2.mlp_layer_train_grad
         gx, gw, gb, gg, gbeta = grad(grad_out.contiguous(), *arg, x, weight, y, mean, var, gamma,
                                      beta, ctx.eps, ctx.relu, ctx.needs_input_grad[0])
         bn = gamma is not None
@@ -135,6 +143,8 @@ def _register_autograd():
     reg("pn2::bn_train", bn_bwd, setup_context=bn_setup)
     reg("pn2::mlp_layer_train", mlp_bwd, setup_context=mlp_setup)
     reg("pn2::mlp_layer_train_pool", mlp_bwd, setup_context=mlp_setup)
+    reg("pn2::mlp_layer_train_bf16", mlp_bwd, setup_context=mlp_setup_bf16)
+    reg("pn2::mlp_layer_train_pool_bf16", mlp_bwd, setup_context=mlp_setup_bf16)
     reg("pn2::gather_point", gather_bwd, setup_context=save_all)
     reg("pn2::group_point", group_bwd, setup_context=save_all)
     reg("pn2::three_interpolate", interp_bwd, setup_context=save_all)

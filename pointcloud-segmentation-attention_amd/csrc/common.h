@@ -117,6 +117,13 @@ PN2_DEV uint64_t uniform_u64(uint64_t v) {
 
 PN2_DEV int lane_id() { return (int)__lane_id(); }
 
+// Two fp32 to one packed bf16 pair (lo in bits 0..15), round to nearest even; no builtin.
+PN2_DEV uint32_t cvt_pk_bf16(float lo, float hi) {
+  uint32_t r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  return r;
+}
+
 // Sum / max over aligned segments of SEG lanes (SEG a power of two <= 64) using xor shuffles.
 template <int SEG>
 PN2_DEV float seg_sum(float v) {

@@ -208,13 +208,6 @@ PN2_DEV void mma_item(const float4* __restrict__ wp, const float* ap, int rstrid
   }
 }
 
-// Two fp32 to one packed bf16 pair (lo in bits 0..15), round to nearest even; no builtin.
-PN2_DEV uint32_t cvt_pk_bf16(float lo, float hi) {
-  uint32_t r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
 // mma_item for a bf16 layer: kch chunks of 16 input features, one MFMA per chunk and row tile
 // (k = 16c + 8h + j, j = 0..7). wp = the tile's packed weights at this lane (16 bytes = the
 // lane's 8 bf16), ap = this lane's activation row (+8h) in the first row tile: two 16-byte

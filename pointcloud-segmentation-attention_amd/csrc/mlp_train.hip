@@ -7,6 +7,9 @@
 //   backward   grad_y, grad_gamma, grad_beta = pn2_bn_act_bwd(grad_out, y, ...)
 //              grad_w = x^T grad_y    pn2_mlp_wgrad    (fp32 matrix cores)
 //              grad_x = grad_y W^T    pn2_shared_mlp over a pn2_mlp_pack of W^T
+//   bf16 mode (opt-in, the contract is at pn2_mlp_pack_bf16 in include/pn2hip.h): the three GEMMs
+//              on the bf16 matrix cores, pn2_shared_mlp with PN2_MLP_BF16 over a
+//              pn2_mlp_pack_bf16 of W, b / of W^T, and pn2_mlp_wgrad_bf16; all else as above
 //   last layer of a set-abstraction MLP, fused with the max pool over the ns samples of a group
 //   (y is (groups, ns, C)):
 //              out, arg = max_j act(bn(y))                        pn2_bn_act_pool_fwd
@@ -26,7 +29,8 @@
 // wave that owns a 32x32 (cin, cout) tile loads x[r + (lane >> 5)][ci0 + (lane & 31)] and
 // grad_y[r + (lane >> 5)][co0 + (lane & 31)]: two row segments straight from the row-major
 // tensors, no transpose. The four waves of a workgroup interleave the row pairs of a slab and
-// their accumulators are added through LDS in wave order.
+// their accumulators are added through LDS in wave order. pn2_mlp_wgrad_bf16 is the same kernel
+// on v_mfma_f32_32x32x16_bf16 (wgrad_partial_bf16), 16 rows per MFMA.
 #include "chan_rows.h"
 #include "common.h"
 
@@ -34,6 +38,8 @@ namespace pn2 {
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 using namespace chan_rows;
 
@@ -426,6 +432,16 @@ __global__ __launch_bounds__(kBlock) void bn_pool_bwd_apply_split(
 }
 
 // ---------------------------------------------------------------- weight gradient -------
+// eight fp32 to one bf16 MFMA operand (element j in bits 16 j ..), round to nearest even
+PN2_DEV bf16x8 pack_bf16x8(const float (&v)[8]) {
+  u32x4 p;
+  p.x = cvt_pk_bf16(v[0], v[1]);
+  p.y = cvt_pk_bf16(v[2], v[3]);
+  p.z = cvt_pk_bf16(v[4], v[5]);
+  p.w = cvt_pk_bf16(v[6], v[7]);
+  return __builtin_bit_cast(bf16x8, p);
+}
+
 // blockIdx.x = part p (slabs p, p + nparts, ...), blockIdx.y = (ti, tjg): input-channel tile
 // ti and output-channel tiles tjg * NJ .. + NJ - 1. Partial tiles are stored in accumulator
 // order e = reg * 64 + lane: ci = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5), co = lane & 31.
@@ -511,6 +527,101 @@ __global__ __launch_bounds__(kBlock) void wgrad_partial(const float* __restrict_
   }
 }
 
+// The same stage 1 on v_mfma_f32_32x32x16_bf16 (pn2_mlp_wgrad_bf16): lane (h = lane >> 5,
+// i = lane & 31) holds A[i][8h + j] and B[8h + j][i], j = 0..7, so one MFMA covers 16 rows and a
+// lane loads x[r + 8h + j][ci0 + i] and grad_y[r + 8h + j][co0 + i] for eight j: per j two
+// 128-byte row segments per wave, straight from the row-major tensors, rounded to bf16 pairs on
+// the way in. The four waves interleave the 16-row blocks of a slab (16 MFMAs per wave and tile
+// from zero); the accumulator layout, the LDS sum, the double slab sum and the partial tiles are
+// wgrad_partial's, so wgrad_final serves both.
+template <int NJ>
+__global__ __launch_bounds__(kBlock) void wgrad_partial_bf16(const float* __restrict__ x,
+                                                             const float* __restrict__ gy,
+                                                             long long rows, int cin, int cout,
+                                                             int cout32, int nslabs, int nparts,
+                                                             float* __restrict__ part) {
+  constexpr int U = NJ == 4 ? 2 : 4;  // 16-row blocks in flight per wave
+  __shared__ float sh[4][kTile];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int tjn = (cout32 + NJ - 1) / NJ;
+  const int ti = blockIdx.y / tjn, tjg = blockIdx.y % tjn;
+  const int p = blockIdx.x;
+  const int kh = lane >> 5;
+  const int ci = ti * 32 + (lane & 31);
+  const bool ci_ok = ci < cin;
+  int co[NJ];
+  bool co_ok[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    co[j] = (tjg * NJ + j) * 32 + (lane & 31);
+    co_ok[j] = co[j] < cout;
+  }
+  // output tiles of this group that exist (the last group may hold fewer than NJ): uniform
+  const int nj = min(NJ, cout32 - tjg * NJ);
+  double tot[NJ][4];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) tot[j][q] = 0.0;
+
+  for (int s = p; s < nslabs; s += nparts) {
+    const long long r0 = (long long)s * kSlab;
+    const int nr = block_rows(rows, r0, kSlab);
+    f32x16 acc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int k = 0; k < 16; ++k) acc[j][k] = 0.f;
+    // wave w takes 16-row blocks w, w + 4, ...: rows 16 (w + 4 t) + 8 kh + j
+    for (int t0 = 0; 64 * t0 < nr; t0 += U) {
+      float a[U][8], b[NJ][U][8];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const int r = 16 * (w + 4 * (t0 + u)) + 8 * kh + k;
+          const bool ok = r < nr;
+          const long long row = r0 + r;
+          a[u][k] = (ok && ci_ok) ? x[row * cin + ci] : 0.f;
+#pragma unroll
+          for (int j = 0; j < NJ; ++j)
+            b[j][u][k] = (j < nj && ok && co_ok[j]) ? gy[row * cout + co[j]] : 0.f;
+        }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const bf16x8 av = pack_bf16x8(a[u]);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          if (j < nj)
+            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, pack_bf16x8(b[j][u]), acc[j], 0,
+                                                             0, 0);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      if (j >= nj) break;  // uniform over the workgroup
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < 16; ++k) sh[w][k * 64 + lane] = acc[j][k];
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int e = threadIdx.x + kBlock * q;
+        tot[j][q] += (double)(((sh[0][e] + sh[1][e]) + sh[2][e]) + sh[3][e]);
+      }
+    }
+  }
+  const int ntiles = gridDim.y / tjn * cout32;  // cin32 * cout32
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int tj = tjg * NJ + j;
+    if (tj >= cout32) continue;
+    float* dst = part + ((size_t)p * ntiles + (size_t)ti * cout32 + tj) * kTile;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) dst[threadIdx.x + kBlock * q] = (float)tot[j][q];
+  }
+}
+
 // stage 2: grad_w[ci][co] = sum over parts (double, part order)
 __global__ __launch_bounds__(kBlock) void wgrad_final(const float* __restrict__ part, int cin,
                                                       int cout, int cout32, int ntiles,
@@ -558,6 +669,36 @@ int wgrad_parts(long long rows, int cin, int cout) {
 }
 
 int wgrad_nj(int cout32) { return cout32 >= 4 ? 4 : (cout32 >= 2 ? 2 : 1); }
+
+size_t wgrad_ws_bytes(long long rows, int cin, int cout) {
+  const size_t ntiles = (size_t)ceil_div(cin, 32) * (size_t)ceil_div(cout, 32);
+  return (size_t)wgrad_parts(rows, cin, cout) * ntiles * kTile * sizeof(float);
+}
+
+// pn2_mlp_wgrad and, with bf16, pn2_mlp_wgrad_bf16: the same checks, grid and stage 2
+int wgrad_launch(bool bf16, const float* x, const float* grad_y, long long rows, int cin, int cout,
+                 float* grad_w, void* workspace, size_t workspace_bytes, pn2_stream_t stream) {
+  if (rows <= 0 || cin <= 0 || cout <= 0 || rows > kMaxRows) return PN2_EINVAL;
+  if (!x || !grad_y || !grad_w || !workspace) return PN2_EINVAL;
+  if (workspace_bytes < wgrad_ws_bytes(rows, cin, cout)) return PN2_EINVAL;
+  const int cin32 = (int)ceil_div(cin, 32), cout32 = (int)ceil_div(cout, 32);
+  const int nj = wgrad_nj(cout32);
+  const long long gy = (long long)cin32 * ceil_div(cout32, nj);
+  const long long ntiles = (long long)cin32 * cout32;
+  if (gy > 65535 || ntiles * kTile / kBlock > 0x7fffffffLL) return PN2_EINVAL;
+  const int nslabs = (int)ceil_div(rows, kSlab), nparts = wgrad_parts(rows, cin, cout);
+  float* part = static_cast<float*>(workspace);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(nparts, (unsigned)gy);
+  auto* stage1 = nj == 4 ? (bf16 ? wgrad_partial_bf16<4> : wgrad_partial<4>)
+                 : nj == 2 ? (bf16 ? wgrad_partial_bf16<2> : wgrad_partial<2>)
+                           : (bf16 ? wgrad_partial_bf16<1> : wgrad_partial<1>);
+  hipLaunchKernelGGL(stage1, grid, dim3(kBlock), 0, s, x, grad_y, rows, cin, cout, cout32, nslabs,
+                     nparts, part);
+  hipLaunchKernelGGL(wgrad_final, dim3((unsigned)(ntiles * kTile / kBlock)), dim3(kBlock), 0, s,
+                     part, cin, cout, cout32, (int)ntiles, nparts, grad_w);
+  PN2_RETURN_LAUNCH();
+}
 
 // groups per thread of the pooled kernels' groups layout: about kActRows rows per workgroup
 int pool_gpt(int ns) {
@@ -716,37 +857,20 @@ int pn2_col_sum(const float* x, long long rows, int C, float* out, void* workspa
 
 size_t pn2_mlp_wgrad_workspace_size(long long rows, int cin, int cout) {
   if (rows <= 0 || cin <= 0 || cout <= 0) return 0;
-  const size_t ntiles = (size_t)pn2::ceil_div(cin, 32) * (size_t)pn2::ceil_div(cout, 32);
-  return (size_t)pn2::wgrad_parts(rows, cin, cout) * ntiles * pn2::kTile * sizeof(float);
+  return pn2::wgrad_ws_bytes(rows, cin, cout);
 }
 
 int pn2_mlp_wgrad(const float* x, const float* grad_y, long long rows, int cin, int cout,
                   float* grad_w, void* workspace, size_t workspace_bytes, pn2_stream_t stream) {
-  using namespace pn2;
-  if (rows <= 0 || cin <= 0 || cout <= 0 || rows > kMaxRows) return PN2_EINVAL;
-  if (!x || !grad_y || !grad_w || !workspace) return PN2_EINVAL;
-  if (workspace_bytes < pn2_mlp_wgrad_workspace_size(rows, cin, cout)) return PN2_EINVAL;
-  const int cin32 = (int)ceil_div(cin, 32), cout32 = (int)ceil_div(cout, 32);
-  const int nj = wgrad_nj(cout32);
-  const long long gy = (long long)cin32 * ceil_div(cout32, nj);
-  const long long ntiles = (long long)cin32 * cout32;
-  if (gy > 65535 || ntiles * kTile / kBlock > 0x7fffffffLL) return PN2_EINVAL;
-  const int nslabs = (int)ceil_div(rows, kSlab), nparts = wgrad_parts(rows, cin, cout);
-  float* part = static_cast<float*>(workspace);
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(nparts, (unsigned)gy);
-  if (nj == 4)
-    hipLaunchKernelGGL(wgrad_partial<4>, grid, dim3(kBlock), 0, s, x, grad_y, rows, cin, cout,
-                       cout32, nslabs, nparts, part);
-  else if (nj == 2)
-    hipLaunchKernelGGL(wgrad_partial<2>, grid, dim3(kBlock), 0, s, x, grad_y, rows, cin, cout,
-                       cout32, nslabs, nparts, part);
-  else
-    hipLaunchKernelGGL(wgrad_partial<1>, grid, dim3(kBlock), 0, s, x, grad_y, rows, cin, cout,
-                       cout32, nslabs, nparts, part);
-  hipLaunchKernelGGL(wgrad_final, dim3((unsigned)(ntiles * kTile / kBlock)), dim3(kBlock), 0, s,
-                     part, cin, cout, cout32, (int)ntiles, nparts, grad_w);
-  PN2_RETURN_LAUNCH();
+  return pn2::wgrad_launch(false, x, grad_y, rows, cin, cout, grad_w, workspace, workspace_bytes,
+                           stream);
+}
+
+int pn2_mlp_wgrad_bf16(const float* x, const float* grad_y, long long rows, int cin, int cout,
+                       float* grad_w, void* workspace, size_t workspace_bytes,
+                       pn2_stream_t stream) {
+  return pn2::wgrad_launch(true, x, grad_y, rows, cin, cout, grad_w, workspace, workspace_bytes,
+                           stream);
 }
 
 }  // extern "C"

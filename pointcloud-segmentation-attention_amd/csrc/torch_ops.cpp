@@ -546,15 +546,16 @@ Tensor workspace(const Tensor& like, size_t bytes) {
 }
 
 // out (rows, cout) = in (rows, cin) * w (cin, cout) + bias: pn2_mlp_pack + pn2_shared_mlp as one
-// layer with no batch norm and no activation
+// layer with no batch norm and no activation; bf16: pn2_mlp_pack_bf16 and PN2_MLP_BF16, so both
+// operands are rounded to bf16 (the training layer's bf16 mode, include/pn2hip.h)
 void linear_rows(const Tensor& in, const Tensor& w, const Tensor& bias, int64_t rows, Tensor& out,
-                 const char* op) {
+                 const char* op, bool bf16 = false) {
   const int cin = I(w.size(0)), cout = I(w.size(1));
-  const size_t bytes = pn2_mlp_packed_size(cin, cout);
+  const size_t bytes = bf16 ? pn2_mlp_packed_size_bf16(cin, cout) : pn2_mlp_packed_size(cin, cout);
   Tensor packed = workspace(in, bytes);
-  check_rc(pn2_mlp_pack(F(w), F(bias), nullptr, nullptr, cin, cout, P(packed), bytes,
-                        stream_of(in)), op);
-  const pn2_mlp_layer layer = {P(packed), cin, cout, 0};
+  check_rc((bf16 ? pn2_mlp_pack_bf16 : pn2_mlp_pack)(F(w), F(bias), nullptr, nullptr, cin, cout,
+                                                     P(packed), bytes, stream_of(in)), op);
+  const pn2_mlp_layer layer = {P(packed), cin, cout, bf16 ? PN2_MLP_BF16 : 0};
   check_rc(pn2_shared_mlp(F(in), rows, cin, 1, &layer, out.data_ptr<float>(), stream_of(in)), op);
 }
 
@@ -640,18 +641,21 @@ void bn_act_bwd(const Tensor& go, const Tensor* arg, const Tensor& y, int64_t ro
                                 ws, stream_of(y)), op);
 }
 void wgrad(const Tensor& x, const Tensor& grad_y, int64_t rows, int cin, int cout, Tensor& grad_w,
-           const char* op) {
+           const char* op, bool bf16 = false) {
   const size_t ws = pn2_mlp_wgrad_workspace_size(rows, cin, cout);
   Tensor w = workspace(x, ws);
-  check_rc(pn2_mlp_wgrad(F(x), F(grad_y), rows, cin, cout, grad_w.data_ptr<float>(), P(w), ws,
-                         stream_of(x)), op);
+  check_rc((bf16 ? pn2_mlp_wgrad_bf16 : pn2_mlp_wgrad)(F(x), F(grad_y), rows, cin, cout,
+                                                       grad_w.data_ptr<float>(), P(w), ws,
+                                                       stream_of(x)), op);
 }
 
-// mlp_layer_train and, pooled, mlp_layer_train_pool: out, y, mean, var and (pooled) arg
+// mlp_layer_train and, pooled, mlp_layer_train_pool: out, y, mean, var and (pooled) arg. bf16
+// (the _bf16 ops): the layer's GEMM runs on the bf16 matrix cores, everything after y is the
+// same fp32 code
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_train_fwd(
     const Tensor& x_, const Tensor& weight_, const std::optional<Tensor>& bias_,
     const std::optional<Tensor>& gamma_, const std::optional<Tensor>& beta_, double eps, bool relu,
-    bool pooled, const char* op) {
+    bool pooled, const char* op, bool bf16 = false) {
   (pooled ? chk_mlp_pool : chk_mlp_layer)(x_, weight_, bias_, gamma_, beta_, op);
   Tensor x = dev(x_, "x", at::kFloat), weight = dev(weight_, "weight", at::kFloat);
   Tensor bias = dev_opt(bias_, "bias"), gamma = dev_opt(gamma_, "gamma");
@@ -667,7 +671,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_train_fwd(
   if (fake(x)) return {out, y, mean, var, arg};
   c10::hip::HIPGuard g(x.device().index());
   if (no_rows(rows, {&mean, &var})) return {out, y, mean, var, arg};
-  linear_rows(x, weight, bias, rows, y, op);
+  linear_rows(x, weight, bias, rows, y, op, bf16);
   if (bn) bn_stats(y, rows, cout, mean, var, op);
   const float* m = bn ? F(mean) : nullptr;
   const float* v = bn ? F(var) : nullptr;
@@ -684,12 +688,13 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_train_fwd(
   return {out, y, mean, var, arg};
 }
 
-// mlp_layer_train_grad and, with arg, mlp_layer_train_pool_grad (grad_out is then (..., cout))
+// mlp_layer_train_grad and, with arg, mlp_layer_train_pool_grad (grad_out is then (..., cout)).
+// bf16 (the _bf16 ops): the two GEMMs on the fp32 grad_y run on the bf16 matrix cores
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_train_bwd(
     const Tensor& grad_out_, const Tensor* arg_, const Tensor& x_, const Tensor& weight_,
     const Tensor& y_, const std::optional<Tensor>& mean_, const std::optional<Tensor>& var_,
     const std::optional<Tensor>& gamma_, const std::optional<Tensor>& beta_, double eps, bool relu,
-    bool need_grad_x, const char* op) {
+    bool need_grad_x, const char* op, bool bf16 = false) {
   if (arg_) chk_mlp_pool_grad(grad_out_, *arg_, x_, weight_, y_, mean_, var_, gamma_, beta_, op);
   else chk_mlp_layer_grad(grad_out_, x_, weight_, y_, mean_, var_, gamma_, beta_, op);
   const bool bn = has(gamma_);
@@ -714,38 +719,47 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_train_bwd(
   Tensor grad_y = at::empty(y.sizes(), f32(x));
   bn_act_bwd(go, arg_ ? &arg : nullptr, y, rows, arg_ ? x.size(-2) : 1, cout, mean, var, gamma,
              beta, eps, relu, grad_y, bn ? grad_gamma : Tensor(), bn ? grad_beta : grad_b, op);
-  wgrad(x, grad_y, rows, cin, cout, grad_w, op);
-  if (need_grad_x) linear_rows(grad_y, weight.t().contiguous(), Tensor(), rows, grad_x, op);
+  wgrad(x, grad_y, rows, cin, cout, grad_w, op, bf16);
+  if (need_grad_x) linear_rows(grad_y, weight.t().contiguous(), Tensor(), rows, grad_x, op, bf16);
   return {grad_x, grad_w, grad_b, grad_gamma, grad_beta};
 }
 
+// the fp32 ops and their _bf16 namesakes (the training layer's bf16 mode): the same bodies
+template <bool BF16>
 std::tuple<Tensor, Tensor, Tensor, Tensor> mlp_layer_train_hip(
     const Tensor& x, const Tensor& weight, const std::optional<Tensor>& bias,
     const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta, double eps, bool relu) {
   auto [out, y, mean, var, arg] =
-      mlp_train_fwd(x, weight, bias, gamma, beta, eps, relu, false, "mlp_layer_train");
+      mlp_train_fwd(x, weight, bias, gamma, beta, eps, relu, false,
+                    BF16 ? "mlp_layer_train_bf16" : "mlp_layer_train", BF16);
   return {out, y, mean, var};
 }
+template <bool BF16>
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_pool_hip(
     const Tensor& x, const Tensor& weight, const std::optional<Tensor>& bias,
     const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta, double eps, bool relu) {
-  return mlp_train_fwd(x, weight, bias, gamma, beta, eps, relu, true, "mlp_layer_train_pool");
+  return mlp_train_fwd(x, weight, bias, gamma, beta, eps, relu, true,
+                       BF16 ? "mlp_layer_train_pool_bf16" : "mlp_layer_train_pool", BF16);
 }
+template <bool BF16>
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_grad_hip(
     const Tensor& grad_out, const Tensor& x, const Tensor& weight, const Tensor& y,
     const std::optional<Tensor>& mean, const std::optional<Tensor>& var,
     const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta, double eps, bool relu,
     bool need_grad_x) {
   return mlp_train_bwd(grad_out, nullptr, x, weight, y, mean, var, gamma, beta, eps, relu,
-                       need_grad_x, "mlp_layer_train_grad");
+                       need_grad_x, BF16 ? "mlp_layer_train_bf16_grad" : "mlp_layer_train_grad",
+                       BF16);
 }
+template <bool BF16>
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_layer_train_pool_grad_hip(
     const Tensor& grad_out, const Tensor& arg, const Tensor& x, const Tensor& weight,
     const Tensor& y, const std::optional<Tensor>& mean, const std::optional<Tensor>& var,
     const std::optional<Tensor>& gamma, const std::optional<Tensor>& beta, double eps, bool relu,
     bool need_grad_x) {
   return mlp_train_bwd(grad_out, &arg, x, weight, y, mean, var, gamma, beta, eps, relu,
-                       need_grad_x, "mlp_layer_train_pool_grad");
+                       need_grad_x,
+                       BF16 ? "mlp_layer_train_pool_bf16_grad" : "mlp_layer_train_pool_grad", BF16);
 }
 
 // ---- training-mode AttentionLayer of the attention SA modules (csrc/attn_train.hip;
@@ -1780,6 +1794,21 @@ TORCH_LIBRARY(pn2, m) {
         "Tensor? mean, Tensor? var, Tensor? gamma, Tensor? beta, float eps, bool relu, "
         "bool need_grad_x) -> "
         "(Tensor grad_x, Tensor grad_w, Tensor grad_b, Tensor grad_gamma, Tensor grad_beta)");
+  // the training layer's bf16 mode (include/pn2hip.h, at pn2_mlp_pack_bf16): the schemas of the
+  // four ops above, the GEMMs on the bf16 matrix cores
+  m.def("mlp_layer_train_bf16(Tensor x, Tensor weight, Tensor? bias, Tensor? gamma, Tensor? beta, "
+        "float eps, bool relu) -> (Tensor out, Tensor y, Tensor mean, Tensor var)");
+  m.def("mlp_layer_train_bf16_grad(Tensor grad_out, Tensor x, Tensor weight, Tensor y, "
+        "Tensor? mean, Tensor? var, Tensor? gamma, Tensor? beta, float eps, bool relu, "
+        "bool need_grad_x) -> "
+        "(Tensor grad_x, Tensor grad_w, Tensor grad_b, Tensor grad_gamma, Tensor grad_beta)");
+  m.def("mlp_layer_train_pool_bf16(Tensor x, Tensor weight, Tensor? bias, Tensor? gamma, "
+        "Tensor? beta, float eps, bool relu) -> "
+        "(Tensor out, Tensor y, Tensor mean, Tensor var, Tensor arg)");
+  m.def("mlp_layer_train_pool_bf16_grad(Tensor grad_out, Tensor arg, Tensor x, Tensor weight, "
+        "Tensor y, Tensor? mean, Tensor? var, Tensor? gamma, Tensor? beta, float eps, bool relu, "
+        "bool need_grad_x) -> "
+        "(Tensor grad_x, Tensor grad_w, Tensor grad_b, Tensor grad_gamma, Tensor grad_beta)");
   m.def("attn_kv_train(Tensor x, Tensor wq, Tensor bq, Tensor wk, Tensor bk, Tensor wv, Tensor bv, "
         "bool add_max) -> (Tensor att, Tensor pmax, Tensor arg, Tensor q, Tensor kv)");
   m.def("attn_kv_train_grad(Tensor grad_att, Tensor? grad_pmax, Tensor arg, Tensor x, Tensor wq, "
@@ -1844,10 +1873,14 @@ static void register_bodies(torch::Library& m) {
   m.impl("attn_reduce", &attn_reduce_hip);
   m.impl("attn_reduce_grad", &attn_reduce_grad_hip);
   m.impl("group_pool", &group_pool_hip);
-  m.impl("mlp_layer_train", &mlp_layer_train_hip);
-  m.impl("mlp_layer_train_grad", &mlp_layer_train_grad_hip);
-  m.impl("mlp_layer_train_pool", &mlp_layer_train_pool_hip);
-  m.impl("mlp_layer_train_pool_grad", &mlp_layer_train_pool_grad_hip);
+  m.impl("mlp_layer_train", &mlp_layer_train_hip<false>);
+  m.impl("mlp_layer_train_grad", &mlp_layer_train_grad_hip<false>);
+  m.impl("mlp_layer_train_pool", &mlp_layer_train_pool_hip<false>);
+  m.impl("mlp_layer_train_pool_grad", &mlp_layer_train_pool_grad_hip<false>);
+  m.impl("mlp_layer_train_bf16", &mlp_layer_train_hip<true>);
+  m.impl("mlp_layer_train_bf16_grad", &mlp_layer_train_grad_hip<true>);
+  m.impl("mlp_layer_train_pool_bf16", &mlp_layer_train_pool_hip<true>);
+  m.impl("mlp_layer_train_pool_bf16_grad", &mlp_layer_train_pool_grad_hip<true>);
   m.impl("attn_kv_train", &attn_kv_train_hip);
   m.impl("attn_kv_train_grad", &attn_kv_train_grad_hip);
   m.impl("bn_train", &bn_train_hip);

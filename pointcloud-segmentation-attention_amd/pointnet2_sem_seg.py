@@ -54,7 +54,8 @@ def model_body(point_cloud, l0_points, is_training, num_class, bn_decay=None, pa
     net = tf_util.dropout(net, is_training, "dp1", keep_prob=0.5, seed=seed)
     # the reference calls fc2 without is_training; here the flag selects the training layer, and
     # without it fc2's variables would never learn on a trainable store
-    # fc2 stays fp32 on a bf16 store: 21 logits, negligible work, and it decides the argmax
+    # fc2 stays fp32 on a bf16 store, in inference and in training (precision="fp32" holds for
+    # both): 21 logits, negligible work, and it decides the argmax
     net = tf_util.conv1d(net, num_class, 1, "fc2", padding="VALID", activation_fn=None,
                          is_training=is_training, params=store, precision="fp32")
     return net, end_points

@@ -28,8 +28,22 @@ packed_mlp / packed_dense of that store bf16 unless the call names a precision i
 models name "fp32" for fc2, whose 21 logits decide the argmax, and for the attention's query
 Dense, which is not matrix-core work). The numerical contract of a bf16 layer is written at
 pn2_mlp_pack_bf16 in include/pn2hip.h: operands rounded to bf16 (nearest even), exact products,
-fp32 sums and fp32 everything else. Training is untouched: is_training=True on a trainable
-store ignores the precision and runs the fp32 training layers.
+fp32 sums and fp32 everything else. The inference precision never reaches training:
+is_training=True on a trainable store ignores it.
+
+Training precision. The HIP training layers are fp32 by default and have a bf16 matrix-core mode
+of their own, also an opt-in: ParamStore(train_precision="bf16") or
+store.set_train_precision("bf16") makes every layer that mlp_train runs for that store (the SA,
+MSG and FP modules' MLPs, the attention SA modules' MLP and mlp2, conv2d / conv1d with
+is_training=True) run its three GEMMs, the forward product, the input gradient and the weight
+gradient, on the bf16 matrix cores (torch.ops.pn2.mlp_layer_train_bf16 and its namesakes) unless
+the call names precision="fp32" itself (the models do for fc2). The contract is written beside
+the inference one in include/pn2hip.h: operands rounded to bf16 per step, exact products, fp32
+sums; the variables stay fp32 master copies, and the batch statistics, the activation and its
+backward, the fused max pool, the moving averages, Adam, the attention's projections
+(attn_kv_train), bn_train, the head's dropout and loss and the geometry stay fp32. The two
+settings are independent: a store with only precision="bf16" still trains in fp32. What bf16
+training does to a converged mIoU has not been measured (there is no dataset here).
 """
 import math
 
@@ -46,7 +60,8 @@ CONV_SUFFIXES = ("weights", "biases", "bn/gamma", "bn/beta", "bn/moving_mean",
                  "bn/moving_variance")
 DENSE_SUFFIXES = ("kernel", "bias")
 BN_SUFFIXES = ("gamma", "beta", "moving_mean", "moving_variance")
-PRECISIONS = ("fp32", "bf16")  # of a packed inference layer (pn2_mlp_pack / pn2_mlp_pack_bf16)
+# of a packed inference layer (pn2_mlp_pack / pn2_mlp_pack_bf16) and of a HIP training layer
+PRECISIONS = ("fp32", "bf16")
 
 
 def check_precision(precision):
@@ -58,11 +73,13 @@ def check_precision(precision):
 class ParamStore(dict):
     """TF variable name -> float32 tensor, with the reference's initialisers for misses."""
 
-    def __init__(self, *args, seed=0, device="cuda", precision="fp32", **kw):
+    def __init__(self, *args, seed=0, device="cuda", precision="fp32", train_precision="fp32",
+                 **kw):
         super().__init__()
         self.seed = seed
         self.device = device
         self.precision = check_precision(precision)
+        self.train_precision = check_precision(train_precision)
         self.is_trainable = False
         self._packed = {}
         self._stamps = {}
@@ -103,6 +120,14 @@ class ParamStore(dict):
         Returns the store."""
         self.precision = check_precision(precision)
         self.invalidate()
+        return self
+
+    def set_train_precision(self, precision):
+        """The precision of the store's HIP training layers from now on: "fp32" (the default) or
+        "bf16" (the opt-in matrix-core mode of mlp_train; see the module docstring). Independent
+        of set_precision. The training layers pack per step, so nothing is dropped. Returns the
+        store."""
+        self.train_precision = check_precision(precision)
         return self
 
     def parameters(self):
@@ -327,7 +352,8 @@ def conv2d(inputs, num_output_channels, kernel_size, scope, stride=[1, 1], paddi
     Extra keyword `params`: the ParamStore (default: default_store()). is_training=True needs a
     trainable store (ParamStore.trainable()) and runs mlp_train: batch-statistics batch norm,
     gradients for the input and every variable. Extra keyword `precision`: of the packed
-    inference layer ("fp32" / "bf16"; None: the store's); the training layer is fp32."""
+    inference layer ("fp32" / "bf16"; None: the store's). The training layer follows the store's
+    train_precision, except that precision="fp32" on the call keeps it fp32 in training too."""
     if list(kernel_size) != [1, 1] or list(stride) != [1, 1] or data_format != 'NHWC':
         raise NotImplementedError("pn2hip's conv2d is the 1x1 NHWC shared MLP of PointNet++")
     store = params if params is not None else default_store()
@@ -340,7 +366,11 @@ def conv2d(inputs, num_output_channels, kernel_size, scope, stride=[1, 1], paddi
     if is_training:
         layers = torch_layers(store, [scope], int(inputs.shape[-1]), [num_output_channels],
                               bn=bn, relu=activation_fn is not None)
-        return mlp_train(inputs, layers, bn_decay)
+        if precision is not None:
+            check_precision(precision)
+        # "bf16" on the call names the inference pack: training follows the store's own setting
+        return mlp_train(inputs, layers, bn_decay,
+                         precision="fp32" if precision == "fp32" else None)
     mlp = packed_mlp(store, [scope], int(inputs.shape[-1]), [num_output_channels], bn=bn,
                      relu=activation_fn is not None, precision=precision)
     return mlp(inputs)
@@ -385,7 +415,7 @@ def mlp_torch(x, layers, is_training=False, bn_decay=None):
     return x
 
 
-def mlp_train(x, layers, bn_decay=None, pool=None):
+def mlp_train(x, layers, bn_decay=None, pool=None, precision=None):
     """The layers of mlp_torch(x, layers, is_training=True) on the HIP training kernels
     (torch.ops.pn2.mlp_layer_train: conv + bias + batch-statistics batch norm + ReLU, with
     autograd for x and every variable), for the variables of a trainable ParamStore. The moving
@@ -395,7 +425,13 @@ def mlp_train(x, layers, bn_decay=None, pool=None):
     pool="max": x is (..., ns, cin) and the last layer runs fused with the max over the ns
     axis (torch.ops.pn2.mlp_layer_train_pool): the result, (..., cout), has the bits of
     mlp_train(x, layers).max(dim=-2).values, and neither the last activation nor its gradient is
-    materialised."""
+    materialised.
+
+    precision: "fp32", "bf16" (the layers' GEMMs on the bf16 matrix cores:
+    torch.ops.pn2.mlp_layer_train_bf16 / _pool_bf16; see the module docstring) or None: each
+    layer's own train_precision, which torch_layers takes from the store."""
+    if precision is not None:
+        check_precision(precision)
     if pool not in (None, "max"):
         raise InvalidArgumentError(f"mlp_train fuses max pooling only, got pool={pool!r}")
     if pool and not layers:
@@ -407,6 +443,8 @@ def mlp_train(x, layers, bn_decay=None, pool=None):
         bn = p.get("gamma") is not None
         rows = x.numel()
         op = "mlp_layer_train_pool" if pool and i == len(layers) - 1 else "mlp_layer_train"
+        if (precision or getattr(L, "train_precision", "fp32")) == "bf16":
+            op += "_bf16"
         x, _, mean, var = _torch_ops.call(
             op, x, p["weights"], p.get("biases"), p.get("gamma") if bn else None,
             p.get("beta") if bn else None, BN_EPSILON, bool(L.relu))[:4]
@@ -476,15 +514,18 @@ def sparse_softmax_cross_entropy(labels, logits, weights=1.0):
 
 
 class TorchLayer:
-    """A conv layer's raw variables for mlp_torch."""
+    """A conv layer's raw variables for mlp_torch and mlp_train; train_precision: of the HIP
+    training layer mlp_train runs for it."""
 
-    def __init__(self, params, relu=True):
+    def __init__(self, params, relu=True, train_precision="fp32"):
         self.params, self.relu = params, relu
+        self.train_precision = check_precision(train_precision)
 
 
 def torch_layers(store, scopes, cin, widths, bn=True, relu=True):
     layers, c = [], cin
     for scope, w in zip(scopes, widths):
-        layers.append(TorchLayer(store.conv(scope, c, w, bn=bn), relu=relu))
+        layers.append(TorchLayer(store.conv(scope, c, w, bn=bn), relu=relu,
+                                 train_precision=store.train_precision))
         c = w
     return layers

@@ -44,11 +44,16 @@ def peak_delta(torch, fn):
     return int(torch.cuda.max_memory_allocated() - before)
 
 
-def main(script, shapes, one, iters=10, timeout=120, header=None):
+def main(script, shapes, one, iters=10, timeout=120, header=None, options=()):
     """The command line of a benchmark over `shapes`: each shape runs `one(name, repeats, iters)`
     in a child process of its own under `timeout` and prints one JSON line; a shape that fails
-    stops the run. --out writes {**header, "shapes": [the lines]} as one JSON file."""
+    stops the run. --out writes {**header, "shapes": [the lines]} as one JSON file. `options`:
+    (flag, add_argument keywords) of the tool's own string options; a given one reaches the
+    child's command line and `one` as a keyword (--precision bf16: one(..., precision="bf16"))
+    and the header."""
     ap = argparse.ArgumentParser()
+    for flag, kw in options:
+        ap.add_argument(flag, **kw)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--iters", type=int, default=iters)
     ap.add_argument("--timeout", type=int, default=timeout, help="seconds per shape")
@@ -58,14 +63,18 @@ def main(script, shapes, one, iters=10, timeout=120, header=None):
     args = ap.parse_args()
     if args.repeats < 5:
         ap.error("--repeats must be at least 5")
+    extra = {flag.lstrip("-").replace("-", "_"): flag for flag, _ in options}
+    given = {k: getattr(args, k) for k in extra if getattr(args, k) is not None}
     if args.one:
-        return one(args.one, args.repeats, args.iters)
+        return one(args.one, args.repeats, args.iters, **given)
     results = []
     for name in args.shapes.split(","):
         if name not in shapes:
             ap.error(f"unknown shape {name!r}")
         cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(script),
                "--one", name, "--repeats", str(args.repeats), "--iters", str(args.iters)]
+        for k, v in given.items():
+            cmd += [extra[k], str(v)]
         r = subprocess.run(cmd, capture_output=True, text=True)
         sys.stderr.write(r.stderr[-2000:])
         if r.returncode != 0:
@@ -76,5 +85,5 @@ def main(script, shapes, one, iters=10, timeout=120, header=None):
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
-            json.dump({**(header or {}), "shapes": results}, f, indent=1)
+            json.dump({**(header or {}), **given, "shapes": results}, f, indent=1)
             f.write("\n")

@@ -8,6 +8,7 @@
     SA4 conv1     8,192 rows  256 -> 512
 
     python tools/bench_mlp_train.py [--repeats 7] [--iters 10] [--out summary.json]
+                                    [--precision bf16]
 
 Each shape runs in a child process of its own under `timeout`; a shape that fails stops the
 run. Per shape: warm-up, then `repeats` timed windows of `iters` forward+backward passes per
@@ -26,6 +27,13 @@ Then, per C entry point of the layer, the time of the call alone (events, median
 windows) and the bytes its algorithm has to move (computed from the shape) over that time,
 against the measured copy peak of 6.03 TB/s. The two GEMMs through pn2_shared_mlp
 include their pn2_mlp_pack.
+
+--precision bf16 adds the layer's opt-in bf16 matrix-core mode (torch.ops.pn2.mlp_layer_train_bf16)
+as a third side in the same alternating windows of the same child process, and
+pn2_mlp_wgrad_bf16 and the two bf16 GEMMs (pn2_mlp_pack_bf16 included) to the entry-point table.
+`bf16_checks` holds what the issue of that mode asks of the times: the bf16 layer's median window
+below the fp32 layer's fastest one (FP4 conv0, SA4 conv1: matrix-core bound in fp32), not above
+its slowest one (SA1 conv1: load bound), and pn2_mlp_wgrad_bf16 no slower than pn2_mlp_wgrad.
 """
 import importlib
 import json
@@ -43,7 +51,7 @@ SHAPES = {"SA1_conv1": (524288, 32, 32), "FP4_conv0": (131072, 128, 128),
 EPS = 1e-3
 
 
-def one(name, repeats, iters):
+def one(name, repeats, iters, precision="fp32"):
     import torch
     pkg = importlib.import_module("pointcloud-segmentation-attention_amd")
     import pn2hip
@@ -76,6 +84,12 @@ def one(name, repeats, iters):
         clear()
         tu.mlp_torch(x, [layer], True, None).backward(go)
 
+    def hip_bf16():
+        clear()
+        ops.mlp_layer_train_bf16(x, w, b, gamma, beta, EPS, True)[0].backward(go)
+
+    bf16 = precision == "bf16"
+
     # same gradients on both sides (reordered fp32 sums differ in the last bits)
     hip()
     gh = [t.grad.clone() for t in leaves]
@@ -84,8 +98,14 @@ def one(name, repeats, iters):
     for nm, a, t in zip(("x", "w", "b", "gamma", "beta"), gh, leaves):
         scale = max(float(t.grad.abs().max()), 1e-6)
         diffs[nm] = float((a - t.grad).abs().max()) / scale
-    times = windows(torch, [hip, parent], repeats, iters)
-    t_hip, t_par = (statistics.median(t) for t in times)
+    bf16_diffs = {}
+    if bf16:  # against the fp32 HIP layer: the rounding of the operands, about 2^-8 relative
+        hip_bf16()
+        for nm, a, t in zip(("x", "w", "b", "gamma", "beta"), gh, leaves):
+            scale = max(float(a.abs().max()), 1e-6)
+            bf16_diffs[nm] = float((a - t.grad).abs().max()) / scale
+    times = windows(torch, [hip, parent] + ([hip_bf16] if bf16 else []), repeats, iters)
+    t_hip, t_par = (statistics.median(t) for t in times[:2])
     spread = [(min(t), max(t)) for t in times]
 
     # the C entry points alone
@@ -99,12 +119,13 @@ def one(name, repeats, iters):
     wsb, wsw = f32(max(ws_bn // 4, 4)), f32(max(ws_wg // 4, 4))
     wt = wd.t().contiguous()
 
-    def gemm(inp, weight, bias, ci, co, dst):
-        nb = int(lib.pn2_mlp_packed_size(ci, co))
+    def gemm(inp, weight, bias, ci, co, dst, bf=False):
+        size, pack = ((lib.pn2_mlp_packed_size_bf16, lib.pn2_mlp_pack_bf16) if bf else
+                      (lib.pn2_mlp_packed_size, lib.pn2_mlp_pack))
+        nb = int(size(ci, co))
         packed = f32((nb + 3) // 4)
-        L.check(lib.pn2_mlp_pack(ptr(weight), ptr(bias), None, None, ci, co, ptr(packed), nb, st),
-                "mlp_pack")
-        tab = (L.MlpLayer * 1)(L.MlpLayer(packed.data_ptr(), ci, co, 0))
+        L.check(pack(ptr(weight), ptr(bias), None, None, ci, co, ptr(packed), nb, st), "mlp_pack")
+        tab = (L.MlpLayer * 1)(L.MlpLayer(packed.data_ptr(), ci, co, L.PN2_MLP_BF16 if bf else 0))
         L.check(lib.pn2_shared_mlp(ptr(inp), rows, ci, 1, tab, ptr(dst), st), "shared_mlp")
 
     R, F = rows * 4, 4
@@ -124,22 +145,58 @@ def one(name, repeats, iters):
         "pn2_shared_mlp grad_x=grad_y W^T": (lambda: gemm(gy, wt, None, cout, cin, gx),
                                              R * (cin + cout)),
     }
+    if bf16:
+        calls.update({
+            "pn2_shared_mlp y=xW+b bf16": (lambda: gemm(xd, wd, bd, cin, cout, y, True),
+                                           R * (cin + cout)),
+            "pn2_mlp_wgrad_bf16": (lambda: L.check(lib.pn2_mlp_wgrad_bf16(
+                ptr(xd), ptr(gy), rows, cin, cout, ptr(gw), ptr(wsw), ws_wg, st), "mlp_wgrad_bf16"),
+                R * (cin + cout) + ws_wg * 2 + F * cin * cout),
+            "pn2_shared_mlp grad_x=grad_y W^T bf16": (lambda: gemm(gy, wt, None, cout, cin, gx, True),
+                                                      R * (cin + cout)),
+        })
     for fn, _ in calls.values():  # in order: each call's inputs exist
         fn()
     kern = {}
+    # a bf16 entry point alternates with its fp32 twin in the same windows
+    twins = {nm: nm[:-5] for nm in calls if nm.endswith("bf16")}  # " bf16" / "_bf16"
+    timed = {}
     for nm, (fn, nbytes) in calls.items():
-        us = statistics.median(windows(torch, [fn], repeats, iters)[0])
-        kern[nm] = {"us": round(us, 1), "bytes": nbytes, "GBps": round(nbytes / us / 1e3, 1),
+        if nm in twins:
+            continue
+        pair = [nm] + [b for b, a in twins.items() if a == nm]
+        for k, t in zip(pair, windows(torch, [calls[k][0] for k in pair], repeats, iters)):
+            timed[k] = t
+    for nm, (fn, nbytes) in calls.items():
+        t = timed[nm]
+        us = statistics.median(t)
+        kern[nm] = {"us": round(us, 1), "min_max_us": [round(min(t), 1), round(max(t), 1)],
+                    "bytes": nbytes, "GBps": round(nbytes / us / 1e3, 1),
                     "frac_copy_peak": round(nbytes / us / 1e6 / COPY_PEAK_TBS, 3)}
+    extra = {}
+    if bf16:
+        t_bf = statistics.median(times[2])
+        extra = {"bf16_fwd_bwd_us": round(t_bf, 1),
+                 "bf16_min_max_us": [round(min(times[2]), 1), round(max(times[2]), 1)],
+                 "hip_over_bf16": round(t_hip / t_bf, 2),
+                 "bf16_max_rel_grad_diff_vs_hip": {k: float(f"{v:.3g}")
+                                                   for k, v in bf16_diffs.items()},
+                 "bf16_checks": {
+                     "layer_median_below_fp32_fastest": bool(t_bf < min(times[0])),
+                     "layer_median_not_above_fp32_slowest": bool(t_bf <= max(times[0])),
+                     "wgrad_bf16_no_slower": bool(kern["pn2_mlp_wgrad_bf16"]["us"]
+                                                  <= kern["pn2_mlp_wgrad"]["us"])}}
     print(json.dumps({
         "shape": name, "rows": rows, "cin": cin, "cout": cout, "repeats": repeats, "iters": iters,
         "hip_fwd_bwd_us": round(t_hip, 1), "parent_fwd_bwd_us": round(t_par, 1),
         "hip_min_max_us": [round(v, 1) for v in spread[0]],
         "parent_min_max_us": [round(v, 1) for v in spread[1]],
         "parent_over_hip": round(t_par / t_hip, 2), "no_slower": bool(t_hip <= t_par),
-        "max_rel_grad_diff": {k: float(f"{v:.3g}") for k, v in diffs.items()},
+        "max_rel_grad_diff": {k: float(f"{v:.3g}") for k, v in diffs.items()}, **extra,
         "entry_points": kern}))
 
 
 if __name__ == "__main__":
-    main(__file__, SHAPES, one, timeout=150, header={"copy_peak_TBps": COPY_PEAK_TBS})
+    main(__file__, SHAPES, one, timeout=150, header={"copy_peak_TBps": COPY_PEAK_TBS},
+         options=[("--precision", {"choices": ("fp32", "bf16"), "default": None,
+                                   "help": "bf16: time the layer's bf16 mode as a further side"})])
