@@ -22,6 +22,12 @@
 // Exactness does not depend on the sort: any cell layout gives the same picks; the sort only
 // decides how much the box test skips (tools/model_fps_cull.py models it on the SA1 crops:
 // ~34 refreshes for 1,023 picks at K = 128; 25 measured at K = 256, ~93 % of (cell, centre) pairs skipped).
+//  * DISTINCT POINTS. Crops are drawn with replacement (a quarter of an SA1 cloud is copies).
+//    Points with the same coordinate bits have the same running min at every step, so the
+//    points holding the maximum are whole groups and the reference's pick (the smallest tie
+//    key among them) is the group member with the smallest key: only that representative is
+//    sorted, held and sampled. A copy is dropped only when an identical point with a smaller
+//    key was seen, so a copy the bounded search misses is simply handled as before.
 #pragma once
 #include "fps_kernels.h"
 #include "grid.h"
@@ -98,6 +104,26 @@ PN2_DEV int wave_max_i32_l63(int v) {
 
 // tie key: smaller = earlier in the reference's order (k mod 512, k div 512); N < 2^25
 PN2_DEV uint32_t cull_key(int k) { return ((uint32_t)(k & 511) << 16) | ((uint32_t)k >> 9); }
+
+// hash of a point's coordinate bits (the search for copies: per round a table slot and 18
+// check bits from it). The words are folded by rotation and mixed by two multiplies (the
+// 32-bit finalizer of MurmurHash3): the 32-bit multiply is the slow instruction here, 8 to 16
+// points a thread
+PN2_DEV uint32_t point_hash(uint32_t x, uint32_t y, uint32_t z) {
+  uint32_t h = x ^ __builtin_rotateleft32(y, 11) ^ __builtin_rotateleft32(z, 22);
+  h = (h ^ (h >> 16)) * 0x85EBCA6Bu;
+  h = (h ^ (h >> 13)) * 0xC2B2AE35u;
+  return h ^ (h >> 16);
+}
+// rounds of the search for copies: a group whose slot another group's smaller key takes in
+// every round stays unmerged (~29 % of the groups after one round on an SA1 crop, ~3 % after two)
+// (-DPN2_FPS_DEDUP_ROUNDS=0: no search, every point is sorted and sampled, for A/B builds)
+#ifndef PN2_FPS_DEDUP_ROUNDS
+#define PN2_FPS_DEDUP_ROUNDS 2
+#endif
+constexpr int kDedupRounds = PN2_FPS_DEDUP_ROUNDS;
+
+__device__ unsigned long long g_cull_dedup[16 * 4];  // STAMP: per cloud N', search cycles, tie-path picks
 
 // exclusive prefix sum over the wave (Hillis-Steele on ds_swizzle-free shuffles)
 PN2_DEV uint32_t wave_excl_scan(uint32_t v, int lane) {
@@ -334,7 +360,7 @@ __device__ __attribute__((always_inline)) inline void hotcull_body(
   static_assert(!LEAN || (PPC == 1 && NPTS <= 8192), "LEAN: one point per lane per cell");
   constexpr bool XYZ_LDS = NPTS <= 8192 && !LEAN;
   __shared__ __attribute__((aligned(16))) float sxyz[XYZ_LDS ? 3 * NPTS : 4];
-  __shared__ int sperm[NPTS];         // sorted position -> point index
+  __shared__ __attribute__((aligned(16))) int sperm[NPTS];  // sorted position -> point index
   // bucket counts, then offsets; LEAN: then the batch buffer and the hot set (below)
   constexpr int kLeanWords = (K + 1) * 4 + K * 4 + K;
   __shared__ __attribute__((aligned(16))) uint32_t shist[LEAN && kLeanWords > NBK ? kLeanWords : NBK];
@@ -366,7 +392,7 @@ __device__ __attribute__((always_inline)) inline void hotcull_body(
   float* __restrict__ NX = new_xyz ? new_xyz + (size_t)b * M * 3 : nullptr;
   unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev = 0;
   unsigned long long n_refresh = 0, n_stall = 0, n_pairs = 0, n_hot = 0, clk0 = 0;
-  unsigned long long n_tail_grp = 0;
+  unsigned long long n_tail_grp = 0, n_tie = 0;
   unsigned long long ev[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // STAMP: this round's events
   unsigned long long n_grp = 0, n_grp_cyc = 0, n_poll = 0;
   if constexpr (STAMP) {
@@ -387,6 +413,19 @@ __device__ __attribute__((always_inline)) inline void hotcull_body(
   }
   const float* __restrict__ X = XYZ_LDS ? (const float*)sxyz : P;  // coordinates
   for (int e = t; e < NBK; e += BLOCK) shist[e] = 0u;
+  // the search for copies keeps its table in sperm, which the sort fills only afterwards
+  static_assert((NPTS & (NPTS - 1)) == 0 && NPTS <= 16384, "table slots from hash bits; 14-bit keys");
+  static_assert(SPT <= 16, "one flag bit per setup point");
+  uint32_t* const stab = reinterpret_cast<uint32_t*>(sperm);
+  auto dedup_clear = [&] {
+    for (int e = t; e < NPTS / 4; e += BLOCK)
+      reinterpret_cast<uint4*>(stab)[e] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+  };
+  __shared__ int s_anydup;  // the first round found a copy somewhere in the cloud
+  if constexpr (kDedupRounds > 0) {
+    dedup_clear();
+    if (t == 0) s_anydup = 0;
+  }
   // the batch slots start untagged (LEAN: they alias shist, whose counts / offsets < 65536
   // carry tag 0 too)
   if constexpr (!LEAN)
@@ -397,13 +436,42 @@ __device__ __attribute__((always_inline)) inline void hotcull_body(
   __shared__ char* s_kgrid;
   if (KG && t == 0) s_kgrid = NX && M <= NBK ? kgrid + (size_t)b * grid_stride(M) : nullptr;
   __syncthreads();
+  // ---- distinct points: point t + i BLOCK is bit i of `open` while undecided, of `dup`
+  // once an identical point with a smaller tie key was found (a copy: left out of the sort).
+  // Round r: every open point puts (its tie key in 14 bits, 18 more hash bits) into slot (hash
+  // bits of round r) by atomic min: the slot's winner has the smallest key in it and is a
+  // representative. An open point whose 18 bits match the winner's compares coordinate bits
+  // with it and is a copy if they are equal; any other stays open (on a cloud without copies
+  // no coordinate is read). All members of a group share a slot, so they are decided
+  // together, and the work per point is bounded: an atomic, a read and at most one compare per
+  // round (thousands of copies of one point only serialize on their slot). The second round
+  // runs only if the first found a copy anywhere in the cloud.
+  uint32_t hsh[SPT], open = 0, dup = 0;
+  auto dedup_slot = [&](int i, int r) { return (hsh[i] >> (16 * r)) & (uint32_t)(NPTS - 1); };
+  // (the slot takes hash bits 16 r ... 16 r + 13 at most: the 18 check bits are others)
+  auto dedup_word = [&](int i, int r) {  // order = tie order: (k mod 512, k div 512), then the check bits
+    const int k = t + i * BLOCK;
+    const uint32_t chk = r == 0 ? hsh[i] >> 14 : (hsh[i] & 0xFFFFu) | ((hsh[i] >> 30) << 16);
+    return ((uint32_t)(((k & 511) << 5) | (k >> 9)) << 18) | chk;
+  };
+  static_assert(kDedupRounds <= 2, "16 hash bits per round");
   {
     float mx[3] = {-INFINITY, -INFINITY, -INFINITY}, mn[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int k = t; k < N; k += BLOCK) {
 #pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        mx[a] = fmaxf(mx[a], X[3 * k + a]);
-        mn[a] = fmaxf(mn[a], -X[3 * k + a]);
+    for (int i = 0; i < SPT; ++i) {
+      const int k = t + i * BLOCK;
+      hsh[i] = 0u;
+      if (k < N) {
+        float c[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          c[a] = X[3 * k + a];
+          mx[a] = fmaxf(mx[a], c[a]);
+          mn[a] = fmaxf(mn[a], -c[a]);
+        }
+        hsh[i] = point_hash(__float_as_uint(c[0]), __float_as_uint(c[1]), __float_as_uint(c[2]));
+        if constexpr (kDedupRounds > 0) atomicMin(&stab[dedup_slot(i, 0)], dedup_word(i, 0));
+        open |= 1u << i;
       }
     }
 #pragma unroll
@@ -420,6 +488,46 @@ __device__ __attribute__((always_inline)) inline void hotcull_body(
     }
   }
   __syncthreads();
+  unsigned long long dd_clk = 0;
+  if constexpr (STAMP) dd_clk = __builtin_amdgcn_s_memtime();
+  const uint32_t valid = open;
+#pragma unroll
+  for (int r = 0; r < kDedupRounds; ++r) {
+    if (r > 0) {
+      if (dup) s_anydup = 1;
+      __syncthreads();  // every read of the round before is done
+      if (!s_anydup) break;
+      dedup_clear();
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < SPT; ++i)
+        if ((open >> i) & 1u) atomicMin(&stab[dedup_slot(i, r)], dedup_word(i, r));
+      __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < SPT; ++i) {
+      if ((open >> i) & 1u) {
+        const int k = t + i * BLOCK;
+        const uint32_t mine = dedup_word(i, r), win = stab[dedup_slot(i, r)];
+        if (win == mine) {
+          open &= ~(1u << i);
+        } else if (((win ^ mine) & 0x3FFFFu) == 0u) {
+          // the winner's point (smaller key, same hash bits): clamped, so that no table
+          // content can send the read outside the cloud
+          const int o = min((int)(((win >> 18) & 31u) << 9 | (win >> 23)), N - 1);
+          const bool same = __float_as_uint(X[3 * o]) == __float_as_uint(X[3 * k]) &&
+                            __float_as_uint(X[3 * o + 1]) == __float_as_uint(X[3 * k + 1]) &&
+                            __float_as_uint(X[3 * o + 2]) == __float_as_uint(X[3 * k + 2]);
+          if (same) {
+            dup |= 1u << i;
+            open &= ~(1u << i);
+          }
+        }
+      }
+    }
+  }
+  const uint32_t keep = valid & ~dup;
+  if constexpr (STAMP) dd_clk = __builtin_amdgcn_s_memtime() - dd_clk;
   float blo[3], bsc[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -436,7 +544,7 @@ __device__ __attribute__((always_inline)) inline void hotcull_body(
 #pragma unroll
   for (int i = 0; i < SPT; ++i) {
     const int k = t + i * BLOCK;
-    if (k < N) {
+    if ((keep >> i) & 1u) {
       uint32_t c = 0;
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
@@ -452,6 +560,7 @@ __device__ __attribute__((always_inline)) inline void hotcull_body(
     }
   }
   __syncthreads();
+  int Np;  // N': the points that are sorted and sampled (the representatives)
   {
     constexpr int PB = (NBK + BLOCK - 1) / BLOCK;
     uint32_t c[PB], s = 0;
@@ -463,8 +572,12 @@ __device__ __attribute__((always_inline)) inline void hotcull_body(
     const uint32_t ex = wave_excl_scan(s, lane);
     if (lane == kWave - 1) swmax[w] = (int)(ex + s);
     __syncthreads();
-    uint32_t base = 0;
-    for (int v = 0; v < w; ++v) base += (uint32_t)swmax[v];
+    uint32_t base = 0, total = 0;
+    for (int v = 0; v < NW; ++v) {
+      base += v < w ? (uint32_t)swmax[v] : 0u;
+      total += (uint32_t)swmax[v];
+    }
+    Np = __builtin_amdgcn_readfirstlane((int)total);
     uint32_t run = base + ex;
 #pragma unroll
     for (int i = 0; i < PB; ++i) {
@@ -476,7 +589,7 @@ __device__ __attribute__((always_inline)) inline void hotcull_body(
 #pragma unroll
   for (int i = 0; i < SPT; ++i) {
     const int k = t + i * BLOCK;
-    if (k < N) sperm[shist[code[i]] + rank[i]] = k;
+    if ((keep >> i) & 1u) sperm[shist[code[i]] + rank[i]] = k;
   }
   __syncthreads();
   // cell boxes: 8 lanes per cell, each folds 8 consecutive sorted points, then DPP within 8
@@ -486,7 +599,7 @@ __device__ __attribute__((always_inline)) inline void hotcull_body(
 #pragma unroll
     for (int i = 0; i < 8 * PPC; ++i) {
       const int pos = base + i;
-      if (pos < N) {
+      if (pos < Np) {
         const int k = sperm[pos];
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -584,7 +697,7 @@ __device__ __attribute__((always_inline)) inline void hotcull_body(
 #pragma unroll
       for (int h = 0; h < PPC; ++h) {
         const int pos = spos(s, h);
-        const bool in = pos < N;
+        const bool in = pos < Np;
         const int k = in ? sperm[pos] : 0;
         px[s * PPC + h] = X[3 * k];
         py[s * PPC + h] = X[3 * k + 1];
@@ -874,6 +987,7 @@ __device__ __attribute__((always_inline)) inline void hotcull_body(
             if (__builtin_popcountll(hold) == 1) {
               L = (int)__builtin_ctzll(hold);
             } else {  // equal values: the smallest tie key among the holders
+              if constexpr (STAMP) ++n_tie;
               uint32_t ck;
               if constexpr (HQ == 4) {  // the same selects as the lane's best entry
                 uint32_t k23;
@@ -1052,6 +1166,9 @@ __device__ __attribute__((always_inline)) inline void hotcull_body(
         g_cull_stats[b * 8 + 1] = n_refresh;
         g_cull_stats[b * 8 + 2] = n_stall;
         g_cull_stats[b * 8 + 4] = n_hot;
+        g_cull_dedup[b * 4 + 0] = (unsigned long long)Np;
+        g_cull_dedup[b * 4 + 1] = dd_clk;
+        g_cull_dedup[b * 4 + 2] = n_tie;
       }
       if (w == 1) {
         g_cull_stats[b * 8 + 3] = n_pairs;

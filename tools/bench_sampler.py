@@ -6,6 +6,10 @@ its picks: fps_hotcull_grid_kernel) and without the grid (pn2_fps_gather: fps_ho
 grid form's outputs are checked equal to the plain form's (the parity tests pin both).
 
     [PN2HIP_LIB=<variant .so>] python tools/bench_sampler.py [--reps 15] [--inner 10]
+                                                             [--msg] [--kind uniform]
+
+--msg: the MSG SA1 size instead (B = 8, 16384 -> 512; it has no grid form). --kind: the clouds
+(synth.batch kinds: scannet crops drawn with replacement, or duplicate-free uniform ones).
 """
 import argparse
 import importlib
@@ -22,13 +26,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--inner", type=int, default=10)
+    ap.add_argument("--msg", action="store_true")
+    ap.add_argument("--kind", default="scannet")
     args = ap.parse_args()
     import torch
     pkg = importlib.import_module("pointcloud-segmentation-attention_amd")
     ts = pkg.tf_sampling
     dev = torch.device("cuda:0")
-    B, N, M = 16, 8192, 1024
-    x = torch.from_numpy(pkg.synth.batch(range(B), N, "scannet")[0]).to(dev)
+    B, N, M = (8, 16384, 512) if args.msg else (16, 8192, 1024)
+    x = torch.from_numpy(pkg.synth.batch(range(B), N, args.kind)[0]).to(dev)
     st = torch.cuda.Stream()
     st.wait_stream(torch.cuda.current_stream())
     out = [(torch.empty((B, M), dtype=torch.int32, device=dev),
@@ -56,11 +62,15 @@ def main():
                 t.append(a.elapsed_time(b) * 1e3 / args.inner)
         return statistics.median(t)
 
-    res = {"lib": os.environ.get("PN2HIP_LIB") or "product",
-           "grid_us": timeit(lambda: ts.farthest_point_sample_chain([M], x, out=out, grid0=kgrid)),
-           "plain_us": timeit(lambda: ts.farthest_point_sample_and_gather(M, x))}
+    res = {"lib": os.environ.get("PN2HIP_LIB") or "product", "kind": args.kind,
+           "shape": [B, N, M]}
+    if not args.msg:
+        res["grid_us"] = timeit(
+            lambda: ts.farthest_point_sample_chain([M], x, out=out, grid0=kgrid))
+    res["plain_us"] = timeit(lambda: ts.farthest_point_sample_and_gather(M, x))
     ri, rx = ts.farthest_point_sample_and_gather(M, x)
-    res["exact"] = bool(torch.equal(out[0][0], ri) and torch.equal(out[0][1], rx))
+    if not args.msg:
+        res["exact"] = bool(torch.equal(out[0][0], ri) and torch.equal(out[0][1], rx))
     print(json.dumps({k: round(v, 2) if isinstance(v, float) else v for k, v in res.items()}))
 
 

@@ -7,6 +7,10 @@
 //   pn2_fps_cull_stamp_msg  the same at the MSG SA1 size (N <= 16384)
 //   pn2_fps_cull_waves   per wave: groups, group cycles, pairs, idle polls (g_cull_wave)
 //   pn2_fps_cull_events  cloud 0, rounds < 64: per wave the round's event stamps (g_cull_ev)
+//   pn2_fps_cull_dedup   per cloud: [0] N' (the distinct points the search kept), [1] cycles
+//                        of the search for copies (wave 0: the table reads and the second
+//                        round; the first round's atomics ride in the bounding-box pass),
+//                        [2] picks decided by the tie path (g_cull_dedup)
 #include "../../pointcloud-segmentation-attention_amd/csrc/fps_cull.h"
 
 extern "C" {
@@ -48,6 +52,11 @@ int pn2_fps_cull_waves(unsigned long long* out_host) {
 int pn2_fps_cull_events(unsigned long long* out_host) {
   return (int)hipMemcpyFromSymbol(out_host, HIP_SYMBOL(pn2::g_cull_ev),
                                   sizeof(unsigned long long) * 64 * 16 * 8);
+}
+
+int pn2_fps_cull_dedup(unsigned long long* out_host) {
+  return (int)hipMemcpyFromSymbol(out_host, HIP_SYMBOL(pn2::g_cull_dedup),
+                                  sizeof(unsigned long long) * 16 * 4);
 }
 
 }  // extern "C"

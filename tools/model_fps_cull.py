@@ -5,7 +5,11 @@ of the (cell, centre) distance updates a box test skips when the cold points are
 into cells of C points. The picks are checked against a brute-force exact FPS (same fp32
 arithmetic and tie order as tf_sampling_g.cu:105-170).
 
-    python tools/model_fps_cull.py [--clouds 2] [--K 128] [--cells 64,256,512]
+    python tools/model_fps_cull.py [--clouds 2] [--K 128] [--cells 64,256,512] [--dedup]
+
+--dedup: the schedule runs over the cloud's distinct points only (representatives(): of the
+points with the same coordinate bits, the one with the smallest tie key); the picks must still
+be the brute-force sampler's over the whole cloud.
 """
 import argparse
 import importlib
@@ -42,6 +46,21 @@ def fps_exact(x, M):
     return np.array(out)
 
 
+def representatives(x):
+    """Indices (ascending) of the points that stand for their group of bit-identical points:
+    the member with the smallest tie key. Two points with the same coordinate bits have the same
+    running minimum at every step, so the set holding the maximum is made of whole groups and
+    its smallest key is a representative's: the argmax over representatives is the reference's
+    pick. Bits, not float equality: +0.0 / -0.0 and different NaNs are not merged."""
+    bits = np.ascontiguousarray(x, np.float32).view(np.uint32).reshape(len(x), 3)
+    _, inv = np.unique(bits, axis=0, return_inverse=True)
+    inv = inv.reshape(-1)
+    k = key(np.arange(len(x)))
+    best = np.full(inv.max() + 1, np.iinfo(np.int64).max, np.int64)
+    np.minimum.at(best, inv, k)
+    return np.flatnonzero(k == best[inv])
+
+
 def morton(x, bits=10):
     lo, hi = x.min(0), x.max(0)
     q = np.clip(((x - lo) / np.maximum(hi - lo, 1e-12) * (2 ** bits - 1)).astype(np.int64), 0,
@@ -60,9 +79,13 @@ def box_lb(lo, hi, c):
         np.float32)
 
 
-def simulate(x, M, K, C, fracs, ref_prev=False):
+def simulate(x, M, K, C, fracs, ref_prev=False, dedup=False):
     """ref_prev: thresholds are fractions of the previous round's threshold (or of the stall's
-    value) instead of the exact maximum, so each cold wave can count before the round's barrier"""
+    value) instead of the exact maximum, so each cold wave can count before the round's barrier.
+    dedup: sort, cells, hot set and picks over the representatives only (their tie keys are
+    those of their indices in the whole cloud; point 0 is always one)"""
+    own = representatives(x) if dedup else np.arange(len(x))
+    x = x[own]
     n = len(x)
     order = np.argsort(morton(x), kind="stable")
     ncell = (n + C - 1) // C
@@ -71,7 +94,7 @@ def simulate(x, M, K, C, fracs, ref_prev=False):
     lo = np.stack([x[cell_of == c].min(0) for c in range(ncell)])
     hi = np.stack([x[cell_of == c].max(0) for c in range(ncell)])
     members = [np.flatnonzero(cell_of == c) for c in range(ncell)]
-    keys = key(np.arange(n))
+    keys = key(own)
     t = np.full(n, INIT, np.float32)
     tmax = np.full(ncell, INIT, np.float32)
     picks, pending = [0], [0]
@@ -118,7 +141,8 @@ def simulate(x, M, K, C, fracs, ref_prev=False):
             st["hot_picks"] += 1
             hv = np.minimum(hv, d2(x[H], x[p]))
     st["culled_frac"] = 1 - st["pairs"] / max(st["pairs_full"], 1)
-    return np.array(picks), st
+    st["points"] = n
+    return own[np.array(picks)], st
 
 
 def main():
@@ -130,6 +154,7 @@ def main():
     ap.add_argument("--cells", default="64,256,512")
     ap.add_argument("--kind", default="scannet")
     ap.add_argument("--ref-prev", action="store_true")
+    ap.add_argument("--dedup", action="store_true")
     ap.add_argument("--fracs", default="0.5,0.7,0.8,0.85,0.9,0.93,0.95,0.97,0.98,0.99,0.995")
     a = ap.parse_args()
     pkg = importlib.import_module("pointcloud-segmentation-attention_amd")
@@ -139,8 +164,8 @@ def main():
         ref = fps_exact(x, a.M)
         for K in [int(v) for v in a.K.split(",")]:
             for C in [int(v) for v in a.cells.split(",")]:
-                p, st = simulate(x, a.M, K, C, fr, a.ref_prev)
-                st.update(cloud=cid, K=K, C=C, exact=bool(np.array_equal(p, ref)))
+                p, st = simulate(x, a.M, K, C, fr, a.ref_prev, a.dedup)
+                st.update(cloud=cid, dedup=a.dedup, K=K, C=C, exact=bool(np.array_equal(p, ref)))
                 print(json.dumps(st), flush=True)
 
 

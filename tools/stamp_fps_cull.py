@@ -52,6 +52,18 @@ for kind in ("scannet", "uniform"):
                       "per_wave_cyc_per_group": [round(v) for v in (wv[:, :, 1] / np.maximum(wv[:, :, 0], 1)).mean(0)],
                       "per_wave_pairs": [round(v) for v in wv[:, :, 2].mean(0)],
                       "per_wave_polls": [round(v) for v in wv[:, :, 3].mean(0)]}), flush=True)
+    # the distinct-points search (builds that have it): N', its cycles, tie-path picks
+    dd = None
+    if hasattr(L, "pn2_fps_cull_dedup"):
+        L.pn2_fps_cull_dedup.argtypes = [ctypes.c_void_p]
+        ddb = np.zeros(16 * 4, np.uint64)
+        assert L.pn2_fps_cull_dedup(ddb.ctypes.data) == 0
+        dd = ddb.reshape(16, 4)[:B].astype(np.int64)
+        bits = x.cpu().numpy().view(np.uint32)
+        print(json.dumps({"kind": kind, "per_cloud_kept_points": dd[:, 0].tolist(),
+                          "per_cloud_distinct_points": [len(np.unique(c, axis=0)) for c in bits],
+                          "per_cloud_dedup_cycles": dd[:, 1].tolist(),
+                          "per_cloud_tie_path_picks": dd[:, 2].tolist()}), flush=True)
     a = buf.reshape(16, 16, 8)[:B].astype(np.float64)
     st = stats.reshape(16, 8)[:B].astype(np.float64)
     print(json.dumps({
@@ -106,6 +118,10 @@ for kind in ("scannet", "uniform"):
             "rounds": float(st[:, 1].mean()), "stalls": float(st[:, 2].mean()),
             "round_cycles": (float(st[:, 0].mean()) - setup - hot_total) / float(st[:, 1].mean()),
             "median_round_events": med})
+        if dd is not None:
+            SUMMARY.update({"kept_points": float(dd[:, 0].mean()),
+                            "dedup_cycles": float(dd[:, 1].mean()),
+                            "tie_path_picks": float(dd[:, 2].mean())})
 
 if ARGS.json:
     with open(ARGS.json, "w") as f:
