@@ -327,7 +327,7 @@ int pn2_attn_reduce(const float* Q, const float* K, const float* V, int B, int M
   const long long G = (long long)B * M;
   if (G == 0 || C == 0) return PN2_OK;
   if (!Q || !K || !V || !out || G > INT32_MAX) return PN2_EINVAL;
-  if ((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)out) & 15) != 0) return PN2_EINVAL;
+  if (!pn2::aligned16(Q, K, V, out)) return PN2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   pn2::AttnLayers a{};
   a.l[0] = pn2::AttnLayer{Q, K, V, out, (int)G, C, 0, {}};
@@ -353,8 +353,7 @@ int pn2_attn_reduce_layers(const pn2_attn_layer* layers, int nlayers, int B,
     const long long G = (long long)B * l.M;
     if (G == 0 || l.C == 0) continue;
     if (!l.Q || !l.K || !l.V || !l.out || G > INT32_MAX) return PN2_EINVAL;
-    if ((((uintptr_t)l.Q | (uintptr_t)l.K | (uintptr_t)l.V | (uintptr_t)l.out) & 15) != 0)
-      return PN2_EINVAL;
+    if (!pn2::aligned16(l.Q, l.K, l.V, l.out)) return PN2_EINVAL;
     // a layer too large for the FastDiv task arithmetic: its own generic launch, as
     // pn2_attn_reduce runs it (the same results)
     pn2::AttnLayers& dst = pn2::attn_small_tasks(G, l.C) ? a : big;
@@ -381,9 +380,7 @@ int pn2_attn_reduce_grad(const float* Q, const float* K, const float* V, const f
   if (G == 0 || C == 0) return PN2_OK;
   if (!Q || !K || !V || !grad_out || !grad_Q || !grad_K || !grad_V || G > INT32_MAX)
     return PN2_EINVAL;
-  if ((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)grad_out | (uintptr_t)grad_Q |
-        (uintptr_t)grad_K | (uintptr_t)grad_V) & 15) != 0)
-    return PN2_EINVAL;
+  if (!pn2::aligned16(Q, K, V, grad_out, grad_Q, grad_K, grad_V)) return PN2_EINVAL;
   hipLaunchKernelGGL(pn2::attn_reduce_grad_kernel, dim3(pn2::grid_for(G * (C / 4))),
                      dim3(pn2::kBlock), 0, (hipStream_t)stream, Q, K, V, grad_out, (int)G, ns, C,
                      grad_Q, grad_K, grad_V);

@@ -398,15 +398,6 @@ int kv_shape(long long G, int ns, int C) {
   return 0;
 }
 
-bool aligned16(std::initializer_list<const void*> ps) {
-  uintptr_t m = 0;
-  for (const void* p : ps) {
-    if (!p) return false;
-    m |= (uintptr_t)p;
-  }
-  return (m & 15) == 0;
-}
-
 }  // namespace
 }  // namespace pn2
 
@@ -417,7 +408,7 @@ int pn2_attn_kv_reduce(const float* Q, const float* KV, long long G, int ns, int
   using namespace pn2;
   const int sh = kv_shape(G, ns, C);
   if (sh) return sh < 0 ? sh : PN2_OK;
-  if (!aligned16({Q, KV, out})) return PN2_EINVAL;
+  if (!Q || !KV || !out || !aligned16(Q, KV, out)) return PN2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   if (small_tasks(G, C) && specialised(ns)) {
     if (ns == 8) launch_fwd<8>(Q, KV, G, C, out, s);
@@ -438,7 +429,8 @@ int pn2_attn_kv_reduce_grad(const float* Q, const float* KV, const float* grad_o
   using namespace pn2;
   const int sh = kv_shape(G, ns, C);
   if (sh) return sh < 0 ? sh : PN2_OK;
-  if (!aligned16({Q, KV, grad_out, grad_Q, grad_KV})) return PN2_EINVAL;
+  if (!Q || !KV || !grad_out || !grad_Q || !grad_KV) return PN2_EINVAL;
+  if (!aligned16(Q, KV, grad_out, grad_Q, grad_KV)) return PN2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   if (small_tasks(G, C) && specialised(ns)) {
     if (ns == 8) launch_bwd<8>(Q, KV, grad_out, G, C, grad_Q, grad_KV, s);

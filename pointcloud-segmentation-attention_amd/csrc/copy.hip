@@ -33,7 +33,7 @@ __global__ __launch_bounds__(kCopyBlock) void copy_f4_kernel(const v4f* __restri
 extern "C" int pn2_copy_f4(const void* src, void* dst, size_t bytes, int cus,
                            pn2_stream_t stream) {
   if (bytes == 0) return PN2_OK;
-  if (!src || !dst || cus <= 0 || (bytes & 15) || ((((uintptr_t)src) | ((uintptr_t)dst)) & 15))
+  if (!src || !dst || cus <= 0 || (bytes & 15) || !pn2::aligned16(src, dst))
     return PN2_EINVAL;
   const size_t n4 = bytes / 16;
   const size_t tiles = (n4 + pn2::kCopyBlock * pn2::kCopyUnroll - 1) /

@@ -847,7 +847,7 @@ int fps_impl(const float* xyz, int B, int N, int M, int32_t* idx, float* nx, voi
              size_t ws_bytes, hipStream_t s, int sched = PN2_FPS_AUTO, bool take = true,
              char* kgrid = nullptr, size_t kgrid_bytes = 0) {
   if (B < 0 || N < 0 || M <= 0 || (B > 0 && (!xyz || !idx))) return PN2_EINVAL;
-  if (kgrid && (!nx || kgrid_bytes < pn2_grid_size(B, M) || ((uintptr_t)kgrid & 15)))
+  if (kgrid && (!nx || kgrid_bytes < pn2_grid_size(B, M) || !aligned16(kgrid)))
     return PN2_EINVAL;
   // the block-scan schedule exists only where the culled sampler runs (4096 < N <= 16384)
   if (sched != PN2_FPS_AUTO && sched != PN2_FPS_BLOCKSCAN) return PN2_EINVAL;
@@ -945,7 +945,7 @@ int fps_chain_launch(const float* xyz, int B, int N, int nstages, const int* npo
                      void* grid0, size_t grid0_bytes) {
   const int rc0 = fps_chain_check(xyz, B, N, nstages, npoint, idx, new_xyz);
   if (rc0 != PN2_OK || B == 0) return rc0;
-  if (grid0 && (grid0_bytes < pn2_grid_size(B, npoint[0]) || ((uintptr_t)grid0 & 15)))
+  if (grid0 && (grid0_bytes < pn2_grid_size(B, npoint[0]) || !aligned16(grid0)))
     return PN2_EINVAL;
   int first = 0;  // first stage of the fused tail
   if (N > kChainNext) {  // the big first stage as its own sampler launch (+ its picks' grid)

@@ -39,47 +39,6 @@ __device__ unsigned long long g_cull_stats[16 * 8];  // STAMP builds: per-cloud 
 __device__ unsigned long long g_cull_wave[16 * 16 * 4];  // STAMP: per wave groups, group cycles, pairs, polls
 __device__ unsigned long long g_cull_ev[64 * 16 * 8];   // STAMP: cloud 0, rounds < 64: per wave events
 
-// float max over the wave (every lane gets it); DPP rows, then the gfx950 permlane swaps
-PN2_DEV float wave_max_f32(float v) {
-#define PN2_FMAX_DPP(C) v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp( \
-                              __float_as_int(v), __float_as_int(v), C, 0xF, 0xF, false)))
-  PN2_FMAX_DPP(kDppXor1);
-  PN2_FMAX_DPP(kDppXor2);
-  PN2_FMAX_DPP(kDppHalfMirror);
-  PN2_FMAX_DPP(kDppMirror);
-#undef PN2_FMAX_DPP
-  {
-    auto x = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(x[0]), __uint_as_float(x[1]));
-  }
-  {
-    auto x = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(x[0]), __uint_as_float(x[1]));
-  }
-  return v;
-}
-
-// signed 32-bit max over the wave (every lane gets it): v_max_i32_dpp rows, permlane swaps
-PN2_DEV int wave_max_i32(int v) {
-// (old = 0: every lane has a valid source in these patterns, so the old value is never used,
-// and the move folds into v_max_i32_dpp)
-#define PN2_IMAX_DPP(C) v = max(v, __builtin_amdgcn_update_dpp(0, v, C, 0xF, 0xF, false))
-  PN2_IMAX_DPP(kDppXor1);
-  PN2_IMAX_DPP(kDppXor2);
-  PN2_IMAX_DPP(kDppHalfMirror);
-  PN2_IMAX_DPP(kDppMirror);
-#undef PN2_IMAX_DPP
-  {
-    auto x = __builtin_amdgcn_permlane16_swap((uint32_t)v, (uint32_t)v, false, false);
-    v = max((int)x[0], (int)x[1]);
-  }
-  {
-    auto x = __builtin_amdgcn_permlane32_swap((uint32_t)v, (uint32_t)v, false, false);
-    v = max((int)x[0], (int)x[1]);
-  }
-  return v;
-}
-
 // signed 32-bit max over the wave, valid in lane 63 only: the DPP row reduction, then the
 // row broadcasts (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3)
 PN2_DEV int wave_max_i32_l63(int v) {
@@ -402,7 +361,7 @@ __device__ __attribute__((always_inline)) inline void hotcull_body(
 
   // ---- setup: LDS copy, bounding box, counting sort by Morton bucket, cells -------------
   if constexpr (XYZ_LDS) {
-    if ((((uintptr_t)P) & 15) == 0) {  // 16 B per lane: one pass of wide coalesced loads
+    if (aligned16(P)) {  // 16 B per lane: one pass of wide coalesced loads
       const int n4 = (3 * N) >> 2;
       const float4* __restrict__ P4 = reinterpret_cast<const float4*>(P);
       for (int e = t; e < n4; e += BLOCK) reinterpret_cast<float4*>(sxyz)[e] = P4[e];
@@ -476,8 +435,8 @@ __device__ __attribute__((always_inline)) inline void hotcull_body(
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      mx[a] = wave_max_f32(mx[a]);
-      mn[a] = wave_max_f32(mn[a]);
+      mx[a] = wave_max_f(mx[a]);
+      mn[a] = wave_max_f(mn[a]);
     }
     if (lane == 0) {
 #pragma unroll

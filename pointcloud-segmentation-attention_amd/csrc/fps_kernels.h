@@ -231,9 +231,7 @@ PN2_DEV void fps_v9_body(const float* P, int N, int M, const float* CXYZ, int32_
       __syncthreads();
       PN2_STAMP(3)
       const uint2 r = (lane & 7) < NW ? red[j & 1][lane & 7] : make_uint2(0u, 0u);
-      uint32_t bm = max_dpp_u32<kDppXor1>(r.x);
-      bm = max_dpp_u32<kDppXor2>(bm);
-      bm = max_dpp_u32<kDppHalfMirror>(bm);
+      const uint32_t bm = seg_max_u32<8>(r.x);
       const uint64_t wins = __builtin_amdgcn_ballot_w64(r.x == bm) & 0xFFull;
       const int wi = (int)__builtin_amdgcn_readfirstlane((int)__builtin_ctzll(wins));
       old = __builtin_amdgcn_readlane((int)r.y, wi);

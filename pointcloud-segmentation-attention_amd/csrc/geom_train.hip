@@ -248,7 +248,7 @@ int grad_ordered(const float* grad_out, int ld, int col0, const void* inv, const
   if ((long long)B * K * C == 0) return PN2_OK;
   if (!grad_points) return PN2_EINVAL;
   if (S > 0 && (!grad_out || !inv || (weighted && !weight))) return PN2_EINVAL;
-  if ((uintptr_t)inv % 16) return PN2_EINVAL;
+  if (!aligned16(inv)) return PN2_EINVAL;
   const int32_t* offsets = S > 0 ? (const int32_t*)inv : nullptr;
   const int32_t* slots = S > 0 ? (const int32_t*)inv + inv_slot_base(B, K) : nullptr;
   int cpl_log2 = 0;
@@ -279,7 +279,7 @@ int pn2_inverse_index_build(const int32_t* keys, int B, int S, int K, void* inv,
   if (B < 0 || S < 0 || K < 0) return PN2_EINVAL;
   if (B > pn2::kMaxBatch || K > PN2_INV_MAX_KEYS || S > PN2_INV_MAX_SLOTS) return PN2_EINVAL;
   if (B == 0 || S == 0) return PN2_OK;
-  if (!keys || !inv || (uintptr_t)inv % 16) return PN2_EINVAL;
+  if (!keys || !inv || !pn2::aligned16(inv)) return PN2_EINVAL;
   if (inv_bytes < pn2_inverse_index_size(B, S, K)) return PN2_EINVAL;
   constexpr int kLdsMax = (PN2_INV_MAX_KEYS + pn2::kInvWaves) * 4;
   static const hipError_t attr = hipFuncSetAttribute(

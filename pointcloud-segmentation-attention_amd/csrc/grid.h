@@ -49,45 +49,6 @@ PN2_DEV int cell_coord(float v, float o, float inv, int n) {
 
 constexpr float kAutoPointsPerCell = 2.0f;
 
-// min / max over the wave (every lane gets it): DPP within rows of 16, then the gfx950
-// permlane swaps across rows -- no LDS crossbar round trip per step (ds_bpermute shuffles)
-template <bool MAX>
-PN2_DEV float wave_minmax_f(float v) {
-  auto op = [](float a, float b) { return MAX ? fmaxf(a, b) : fminf(a, b); };
-#define PN2_MM_DPP(C) v = op(v, __int_as_float(__builtin_amdgcn_update_dpp( \
-                             __float_as_int(v), __float_as_int(v), C, 0xF, 0xF, false)))
-  PN2_MM_DPP(kDppXor1);
-  PN2_MM_DPP(kDppXor2);
-  PN2_MM_DPP(kDppHalfMirror);
-  PN2_MM_DPP(kDppMirror);
-#undef PN2_MM_DPP
-  {
-    auto x = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = op(__uint_as_float(x[0]), __uint_as_float(x[1]));
-  }
-  {
-    auto x = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = op(__uint_as_float(x[0]), __uint_as_float(x[1]));
-  }
-  return v;
-}
-PN2_DEV float wave_min_f(float v) { return wave_minmax_f<false>(v); }
-PN2_DEV float wave_max_f(float v) { return wave_minmax_f<true>(v); }
-// inclusive prefix sum over the wave: DPP row shifts (1, 2, 4, 8 within each 16-lane row; a
-// lane without a source adds 0), then row_bcast:15 / :31 carry each row's total into the rows
-// above -- six VALU steps, where the __shfl_up form was six dependent LDS-crossbar round trips
-// (every lane of the wave active; SA1's grid query 22.0 -> 21.0 us, tools/bench_side.py)
-PN2_DEV int wave_incl_scan(int v, int lane) {
-  (void)lane;
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);  // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);  // row_shr:2
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);  // row_shr:4
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);  // row_shr:8
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);  // row_bcast:15, rows 1, 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);  // row_bcast:31, rows 2, 3
-  return v;
-}
-
 // The grid's header for bbox [lo, hi] of N points (an empty / NaN-only axis as lo = hi = 0).
 // One thread computes it: pn2_grid_build's workgroup, or each workgroup of the fused FP
 // search (interp.hip), which builds a cloud's grid of known points in its own LDS.

@@ -610,7 +610,7 @@ int pn2_grid_build(const float* xyz, int B, int N, float cell_edge, void* grid,
   if (B < 0 || N < 0 || cell_edge != cell_edge) return PN2_EINVAL;
   if (B == 0) return PN2_OK;
   if (!grid || grid_bytes < pn2_grid_size(B, N) || (N > 0 && !xyz)) return PN2_EINVAL;
-  if ((uintptr_t)grid % 16 || B > 65535) return PN2_EINVAL;
+  if (!pn2::aligned16(grid) || B > 65535) return PN2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   char* g = (char*)grid;
   const dim3 grd(B);

@@ -42,8 +42,6 @@ constexpr int kXentBwdThreads = 256;
 constexpr long long kXentMaxRows = 0x7fffffffLL;
 constexpr int kXentMaxC = 65535;
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 // ---------------------------------------------------------------- dropout ---------------
 template <bool VEC>
 __global__ __launch_bounds__(kDropBlock) void dropout_kernel(const float* x, uint64_t n,

@@ -148,17 +148,6 @@ PN2_DEV void scan_known(const float* __restrict__ K, int m, float x1, float y1, 
   best3_merge_xor(best, 2);
 }
 
-// weight = (1/d)/sum(1/d), d = max(dist, 1e-10)  (pointnet_util.py:219-222)
-PN2_DEV void idw(float d1, float d2, float d3, float& w1, float& w2, float& w3) {
-  const float r1 = 1.0f / fmaxf(d1, 1e-10f);
-  const float r2 = 1.0f / fmaxf(d2, 1e-10f);
-  const float r3 = 1.0f / fmaxf(d3, 1e-10f);
-  const float norm = (r1 + r2) + r3;
-  w1 = r1 / norm;
-  w2 = r2 / norm;
-  w3 = r3 / norm;
-}
-
 __global__ __launch_bounds__(kNNBlock) void three_nn_kernel(const float* __restrict__ xyz1,
                                                             const float* __restrict__ xyz2, int n,
                                                             int m, float* __restrict__ dist,
@@ -970,12 +959,12 @@ int fp_plan(const float* xyz1, const float* xyz2, const float* pdist, const int3
   const bool pre = pdist != nullptr;
   // interpolated columns of 4 floats when C2 % 4 == 0 (16 B aligned loads and, on rows that
   // start 16 B aligned, stores); concat columns of 4 when C1 % 4 == 0 as well
-  const bool v2 = C2 % 4 == 0 && ((((uintptr_t)points2 | (uintptr_t)out) & 15) == 0);
+  const bool v2 = C2 % 4 == 0 && aligned16(points2, out);
   // concat columns of 4 floats when C1 % 4 == 0 (16 B aligned), of 2 when C1 is even
   // (cfg3's C1 = 6: rows of C2 + 6 floats start 8 B aligned; float2 loads and stores instead
   // of dwords), else 1
   const int v1 = !v2 ? 1
-                 : C1 % 4 == 0 && (((uintptr_t)points1 & 15) == 0) ? 4
+                 : C1 % 4 == 0 && aligned16(points1) ? 4
                  : C1 % 2 == 0 && (((uintptr_t)points1 & 7) == 0) ? 2 : 1;
   const int coutv = C2 / (v2 ? 4 : 1) + C1 / v1;
   const int row_blocks = (n + kNNRows - 1) / kNNRows;
@@ -1233,7 +1222,7 @@ int pn2_fp_grid_fused_known(const void* known_grid, const float* xyz1, const flo
                             const void* unknown_grid, const float* points1, int C1,
                             const float* points2, int C2, int B, int n, int m, float* out,
                             float* dist, int32_t* idx, pn2_stream_t stream) {
-  if (!known_grid || ((uintptr_t)known_grid & 15)) return PN2_EINVAL;
+  if (!known_grid || !pn2::aligned16(known_grid)) return PN2_EINVAL;
   if (B < 0 || n < 0 || m < 1 || m > pn2::kFpGridMaxKnown || C1 < 0 || C2 < 0 || B > 65535)
     return PN2_EINVAL;
   if (!points1 && C1 != 0) return PN2_EINVAL;

@@ -43,10 +43,6 @@
 namespace pn2 {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / kWave;
 constexpr int kMaxGroupsPerWG = 16;  // P / ns_pad with P <= 128, ns_pad >= 8
@@ -124,19 +120,6 @@ unsigned long long* g_stamp = nullptr;
 #endif
 
 PN2_DEV float act(float v, int relu) { return relu ? fmaxf(v, 0.f) : v; }
-
-// weight = (1/d)/sum(1/d), d = max(dist, 1e-10)  (pointnet_util.py:219-222); same fp32 order
-// as interp.hip's idw(), so the interpolated features are bit-identical to pn2_fp_apply's.
-PN2_DEV void idw3(float d1, float d2, float d3, float& w1, float& w2, float& w3) {
-  const float r1 = 1.0f / fmaxf(d1, 1e-10f);
-  const float r2 = 1.0f / fmaxf(d2, 1e-10f);
-  const float r3 = 1.0f / fmaxf(d3, 1e-10f);
-  const float norm = (r1 + r2) + r3;
-  w1 = r1 / norm;
-  w2 = r2 / norm;
-  w3 = r3 / norm;
-}
-
 
 // One output tile over RG row tiles: cin8 chunks of 8 input features, 4 MFMAs per chunk and
 // row tile (k = 8c + 4h + s, s = 0..3); every weight fragment serves the RG row tiles'
@@ -227,12 +210,8 @@ PN2_DEV void mma_item_bf16(const u32x4* __restrict__ wp, const float* ap, int rs
     float4 lo, hi;
   };
   auto mma1 = [&](const u32x4& w, const Act& a, f32x16& c) {
-    u32x4 p;
-    p.x = cvt_pk_bf16(a.lo.x, a.lo.y);
-    p.y = cvt_pk_bf16(a.lo.z, a.lo.w);
-    p.z = cvt_pk_bf16(a.hi.x, a.hi.y);
-    p.w = cvt_pk_bf16(a.hi.z, a.hi.w);
-    const bf16x8 av = __builtin_bit_cast(bf16x8, p), wv = __builtin_bit_cast(bf16x8, w);
+    const float v[8] = {a.lo.x, a.lo.y, a.lo.z, a.lo.w, a.hi.x, a.hi.y, a.hi.z, a.hi.w};
+    const bf16x8 av = pack_bf16x8(v), wv = __builtin_bit_cast(bf16x8, w);
     if (LAST) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, wv, c, 0, 0, 0);
     else c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv, av, c, 0, 0, 0);
   };
@@ -473,15 +452,6 @@ PN2_DEV void dense_item(const LayerDev& D, const float* X, int Sx, int xrow, int
   }
 }
 
-// (1x4)·(4x1) of tf.matmul, summed left to right (as attn.hip)
-PN2_DEV float dot4q(float4 q, float4 k) {
-  float s = q.x * k.x;
-  s = s + q.y * k.y;
-  s = s + q.z * k.z;
-  s = s + q.w * k.w;
-  return s;
-}
-
 // The query of every group, Dense_q(X[first neighbour]) (attention_layer.py:31, :259), on the
 // VALU: only G rows are needed, so a 32-row MFMA tile would waste (32 - G)/32 of its work
 // (31/32 at SA3/SA4, where one group fills the workgroup). Thread -> (group, output feature);
@@ -510,19 +480,6 @@ PN2_DEV void attn_query(const LayerDev& D, const float* X, int Sx, int G, int ns
     }
     Qb[gi * Sq + f] = ((a0 + a1) + (a2 + a3)) * D.scale[f] + D.shift[f];
   }
-}
-
-template <int L>
-PN2_DEV float lane_sum(float v) {
-#pragma unroll
-  for (int o = L / 2; o > 0; o >>= 1) v = v + __shfl_xor(v, o, kWave);
-  return v;
-}
-template <int L>
-PN2_DEV float lane_max(float v) {
-#pragma unroll
-  for (int o = L / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
-  return v;
 }
 
 // Scores, softmax over the ns pseudo-keys and the weighted V of every (group, head) unit of
@@ -560,12 +517,12 @@ PN2_DEV void attn_scores(const Params& prm, const float* X, int Sx, const float*
       return *reinterpret_cast<const float4*>(B + (r0 + row) * Skv + c);
     };
     float mx = -__builtin_inff();
-    for (int j = sub; j < ns; j += L) mx = fmaxf(mx, dot4q(q, key_at(j, Kb)) / 2.0f);
-    mx = lane_max<L>(mx);  // softmax (:39)
+    for (int j = sub; j < ns; j += L) mx = fmaxf(mx, dot4(q, key_at(j, Kb)) / 2.0f);
+    mx = seg_max<L>(mx);  // softmax (:39)
     float sum = 0.f;
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int j = sub; j < ns; j += L) {
-      const float e = expf(dot4q(q, key_at(j, Kb)) / 2.0f - mx);
+      const float e = expf(dot4(q, key_at(j, Kb)) / 2.0f - mx);
       sum = sum + e;
       const float4 v = key_at(j, Vb);
       o.x = o.x + e * v.x;
@@ -573,11 +530,11 @@ PN2_DEV void attn_scores(const Params& prm, const float* X, int Sx, const float*
       o.z = o.z + e * v.z;
       o.w = o.w + e * v.w;
     }
-    sum = lane_sum<L>(sum);
-    o.x = lane_sum<L>(o.x) / sum;  // aᵀ·V_h (:40), a = e / sum
-    o.y = lane_sum<L>(o.y) / sum;
-    o.z = lane_sum<L>(o.z) / sum;
-    o.w = lane_sum<L>(o.w) / sum;
+    sum = seg_sum<L>(sum);
+    o.x = seg_sum<L>(o.x) / sum;  // aᵀ·V_h (:40), a = e / sum
+    o.y = seg_sum<L>(o.y) / sum;
+    o.z = seg_sum<L>(o.z) / sum;
+    o.w = seg_sum<L>(o.w) / sum;
     float4 pm = make_float4(0.f, 0.f, 0.f, 0.f);
     if (prm.att_add_max) {  // + reduce_max over ns of X (:296-303)
       float4 m4 = make_float4(-__builtin_inff(), -__builtin_inff(), -__builtin_inff(),
@@ -589,8 +546,8 @@ PN2_DEV void attn_scores(const Params& prm, const float* X, int Sx, const float*
         m4.z = fmaxf(m4.z, x.z);
         m4.w = fmaxf(m4.w, x.w);
       }
-      pm = make_float4(lane_max<L>(m4.x), lane_max<L>(m4.y), lane_max<L>(m4.z),
-                       lane_max<L>(m4.w));
+      pm = make_float4(seg_max<L>(m4.x), seg_max<L>(m4.y), seg_max<L>(m4.z),
+                       seg_max<L>(m4.w));
     }
     if (sub == 0 && g < prm.ngroups) {
       float4 y = o;
@@ -885,7 +842,7 @@ PN2_DEV void commit_meta(const Params& prm, int tile, int pass, int p, const Met
       if (SRC == kSrcFP) {
         const int b = (int)(row / prm.n);
         float w1, w2, w3;
-        idw3(f.d0, f.d1, f.d2, w1, w2, w3);
+        idw(f.d0, f.d1, f.d2, w1, w2, w3);
         s_fw[3 * p] = w1;
         s_fw[3 * p + 1] = w2;
         s_fw[3 * p + 2] = w3;
@@ -1085,87 +1042,95 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   PN2_STAMP(15);
 }
 
-// Packed layer: Wp [cout32][cin8][2][32][4] then scale [cout32*32] then shift [cout32*32].
-// scale = bn_scale (1 without BN), shift = bias*scale + bn_shift; padded rows/columns are 0.
+// Packed layer: Wp [cout32][kch][2][32][J] (Wp[to][c][h][i][j] = W[2J c + J h + j][32 to + i]),
+// then scale [cout32*32], then shift [cout32*32]. fp32: J = 4, chunks of 8 input features;
+// BF: J = 8 elements rounded to bf16, chunks of 16. scale = bn_scale (1 without BN),
+// shift = bias*scale + bn_shift, both fp32; padded rows/columns are 0.
+template <bool BF>
 __global__ void mlp_pack_kernel(const float* __restrict__ W, const float* __restrict__ bias,
                                 const float* __restrict__ bn_scale,
-                                const float* __restrict__ bn_shift, int cin, int cout, int cin8,
-                                int cout32, float* __restrict__ packed) {
-  const long long nw = (long long)cout32 * cin8 * 256;
+                                const float* __restrict__ bn_shift, int cin, int cout, int kch,
+                                int cout32, void* __restrict__ packed) {
+  constexpr int LJ = BF ? 3 : 2, J = 1 << LJ;
+  const long long nw = (long long)cout32 * kch * (64 * J);  // weight elements
   const long long total = nw + 2LL * cout32 * 32;
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
+  // BF: nw bf16 elements, then the floats
+  [[maybe_unused]] uint16_t* wp = static_cast<uint16_t*>(packed);
+  [[maybe_unused]] float* sp = static_cast<float*>(packed) + nw / 2;
+  struct At {
+    int f, o;  // W's row (input feature) and column of a packed weight element
+  };
+  auto at = [&](long long e) {
+    const int j = (int)(e & (J - 1));
+    const int i = (int)((e >> LJ) & 31);
+    const int hh = (int)((e >> (LJ + 5)) & 1);
+    const long long tc = e >> (LJ + 6);
+    const int c = (int)(tc % kch);
+    const int to = (int)(tc / kch);
+    return At{2 * J * c + J * hh + j, 32 * to + i};
+  };
+  auto scale_shift = [&](long long r) {
+    const int which = (int)(r / (cout32 * 32));
+    const int o = (int)(r % (cout32 * 32));
     float v = 0.f;
-    if (e < nw) {
-      const int s = (int)(e & 3);
-      const int i = (int)((e >> 2) & 31);
-      const int hh = (int)((e >> 7) & 1);
-      const long long tc = e >> 8;
-      const int c = (int)(tc % cin8);
-      const int to = (int)(tc / cin8);
-      const int f = 8 * c + 4 * hh + s, o = 32 * to + i;
-      if (f < cin && o < cout) v = W[(size_t)f * cout + o];
-    } else {
-      const long long r = e - nw;
-      const int which = (int)(r / (cout32 * 32));
-      const int o = (int)(r % (cout32 * 32));
-      if (o < cout) {
-        const float sc = bn_scale ? bn_scale[o] : 1.f;
-        if (which == 0) v = sc;
-        else v = (bias ? bias[o] : 0.f) * sc + (bn_shift ? bn_shift[o] : 0.f);
-      }
+    if (o < cout) {
+      const float sc = bn_scale ? bn_scale[o] : 1.f;
+      if (which == 0) v = sc;
+      else v = (bias ? bias[o] : 0.f) * sc + (bn_shift ? bn_shift[o] : 0.f);
     }
-    packed[e] = v;
-  }
-}
-
-// fp32 to bf16, round to nearest even (the rounding of v_cvt_pk_bf16_f32)
-PN2_DEV uint16_t bf16_rne(float v) {
-  uint32_t u = __float_as_uint(v);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);  // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
-// Packed bf16 layer: Wp [cout32][cin16][2][32][8] bf16 (Wp[to][c][h][i][j] =
-// bf16(W[16c + 8h + j][32to + i])), then scale and shift as mlp_pack_kernel (fp32).
-__global__ void mlp_pack_bf16_kernel(const float* __restrict__ W, const float* __restrict__ bias,
-                                     const float* __restrict__ bn_scale,
-                                     const float* __restrict__ bn_shift, int cin, int cout,
-                                     int cin16, int cout32, void* __restrict__ packed) {
-  const long long nw = (long long)cout32 * cin16 * 512;  // bf16 elements
-  const long long total = nw + 2LL * cout32 * 32;
-  uint16_t* wp = static_cast<uint16_t*>(packed);
-  float* sp = static_cast<float*>(packed) + nw / 2;
+    return v;
+  };
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (long long)gridDim.x * blockDim.x) {
-    if (e < nw) {
-      const int j = (int)(e & 7);
-      const int i = (int)((e >> 3) & 31);
-      const int hh = (int)((e >> 8) & 1);
-      const long long tc = e >> 9;
-      const int c = (int)(tc % cin16);
-      const int to = (int)(tc / cin16);
-      const int f = 16 * c + 8 * hh + j, o = 32 * to + i;
-      wp[e] = (f < cin && o < cout) ? bf16_rne(W[(size_t)f * cout + o]) : (uint16_t)0;
-    } else {
-      const long long r = e - nw;
-      const int which = (int)(r / (cout32 * 32));
-      const int o = (int)(r % (cout32 * 32));
-      float v = 0.f;
-      if (o < cout) {
-        const float sc = bn_scale ? bn_scale[o] : 1.f;
-        if (which == 0) v = sc;
-        else v = (bias ? bias[o] : 0.f) * sc + (bn_shift ? bn_shift[o] : 0.f);
+    if constexpr (BF) {
+      if (e < nw) {
+        const At w = at(e);
+        wp[e] = (w.f < cin && w.o < cout) ? bf16_rne(W[(size_t)w.f * cout + w.o]) : (uint16_t)0;
+      } else {
+        sp[e - nw] = scale_shift(e - nw);
       }
-      sp[r] = v;
+    } else {
+      float v = 0.f;
+      if (e < nw) {
+        const At w = at(e);
+        if (w.f < cin && w.o < cout) v = W[(size_t)w.f * cout + w.o];
+      } else {
+        v = scale_shift(e - nw);
+      }
+      static_cast<float*>(packed)[e] = v;
     }
   }
 }
 
-// K chunks of a layer in its packed format: 8 input features per chunk (fp32), 16 (bf16)
-int k_chunks(const pn2_mlp_layer& L) {
-  return (L.flags & PN2_MLP_BF16) ? (L.cin + 15) / 16 : (L.cin + 7) / 8;
+// K chunks of a layer in its packed format: 8 input features per chunk (fp32), 16 (bf16).
+// Either chunk of a 32-column tile is 1024 bytes, 256 floats.
+int k_chunks(int cin, bool bf) { return bf ? (cin + 15) / 16 : (cin + 7) / 8; }
+int k_chunks(const pn2_mlp_layer& L) { return k_chunks(L.cin, (L.flags & PN2_MLP_BF16) != 0); }
+
+// pn2_mlp_packed_size and pn2_mlp_packed_size_bf16
+size_t packed_size(bool bf, int cin, int cout) {
+  if (cin <= 0 || cout <= 0) return 0;
+  const size_t kch = (size_t)k_chunks(cin, bf), cout32 = (size_t)(cout + 31) / 32;
+  return (cout32 * kch * 256 + 2 * cout32 * 32) * sizeof(float);
+}
+
+// pn2_mlp_pack and pn2_mlp_pack_bf16
+int pack(bool bf, const float* weight, const float* bias, const float* bn_scale,
+         const float* bn_shift, int cin, int cout, void* packed, size_t packed_bytes,
+         pn2_stream_t stream) {
+  if (cin <= 0 || cout <= 0 || !weight || !packed) return PN2_EINVAL;
+  if (packed_bytes < packed_size(bf, cin, cout)) return PN2_EINVAL;
+  if ((!bn_scale) != (!bn_shift)) return PN2_EINVAL;
+  if (!aligned16(packed)) return PN2_EINVAL;
+  const int kch = k_chunks(cin, bf), cout32 = (cout + 31) / 32;
+  // one thread per weight element (4 or 8 per lane of a chunk) and per scale / shift
+  const long long total = (long long)cout32 * kch * (bf ? 512 : 256) + 2LL * cout32 * 32;
+  long long blocks = (total + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(!bf ? mlp_pack_kernel<false> : mlp_pack_kernel<true>, dim3((unsigned)blocks),
+                     dim3(256), 0, (hipStream_t)stream, weight, bias, bn_scale, bn_shift, cin,
+                     cout, kch, cout32, packed);
+  PN2_RETURN_LAUNCH();
 }
 
 int next_pow2(int v) {
@@ -1248,7 +1213,9 @@ size_t plan(Params& prm, int nl, const pn2_mlp_layer* layers, int cin0, int R, b
   return off * sizeof(float);
 }
 
-// Input segments of the three sources (see Params).
+// Input segments of the three sources (see Params). A source is read as float4 (vecA / vecB)
+// only from a 16-byte aligned base (its row width, a multiple of 4, then keeps every row
+// aligned); any other pointer takes the per-float gather.
 void set_segments(Params& prm, int nA, bool vecA, int offA, int nB, bool vecB, int offB,
                   int cin_total) {
   prm.vecA = vecA;
@@ -1264,16 +1231,12 @@ void set_segments(Params& prm, int nA, bool vecA, int offA, int nB, bool vecB, i
   prm.div_pad = make_fastdiv((uint32_t)(npad > 0 ? npad : 1));
 }
 
-// A source is read as float4 only from a 16-byte aligned base (its row width, a multiple of 4,
-// then keeps every row aligned); any other pointer takes the per-float gather.
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int check_layers(int nl, const pn2_mlp_layer* layers, int cin0) {
   if (nl < 1 || nl > PN2_MLP_MAX_LAYERS || !layers) return PN2_EINVAL;
   int cin = cin0;
   for (int l = 0; l < nl; ++l) {
     if (!layers[l].packed || layers[l].cin != cin || layers[l].cout <= 0) return PN2_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(layers[l].packed) & 15) != 0) return PN2_EINVAL;
+    if (!aligned16(layers[l].packed)) return PN2_EINVAL;
     cin = layers[l].cout;
   }
   return PN2_OK;
@@ -1406,7 +1369,7 @@ int choose_R_staged(Params& prm, int nl, const pn2_mlp_layer* layers, int cin0, 
     const int occ = lds * 2 <= kLdsLimit ? 2 : 1, occ_plain = lds_plain * 2 <= kLdsLimit ? 2 : 1;
     if (R && (!R_plain || (R == R_plain && occ == occ_plain))) {
       const int cout = layers[nl - 1].cout;
-      staged.out_vec = (cout % 4 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
+      staged.out_vec = (cout % 4 == 0) && aligned16(out);
       prm = staged;
       *lds_out = lds;
       return R;
@@ -1427,50 +1390,18 @@ extern "C" {
 void pn2_mlp_set_stamp(void* buf) { pn2::g_stamp = static_cast<unsigned long long*>(buf); }
 #endif
 
-size_t pn2_mlp_packed_size(int cin, int cout) {
-  if (cin <= 0 || cout <= 0) return 0;
-  const size_t cin8 = (size_t)(cin + 7) / 8, cout32 = (size_t)(cout + 31) / 32;
-  return (cout32 * cin8 * 256 + 2 * cout32 * 32) * sizeof(float);
-}
+size_t pn2_mlp_packed_size(int cin, int cout) { return pn2::packed_size(false, cin, cout); }
+size_t pn2_mlp_packed_size_bf16(int cin, int cout) { return pn2::packed_size(true, cin, cout); }
 
 int pn2_mlp_pack(const float* weight, const float* bias, const float* bn_scale,
                  const float* bn_shift, int cin, int cout, void* packed, size_t packed_bytes,
                  pn2_stream_t stream) {
-  if (cin <= 0 || cout <= 0 || !weight || !packed) return PN2_EINVAL;
-  if (packed_bytes < pn2_mlp_packed_size(cin, cout)) return PN2_EINVAL;
-  if ((!bn_scale) != (!bn_shift)) return PN2_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0) return PN2_EINVAL;
-  const int cin8 = (cin + 7) / 8, cout32 = (cout + 31) / 32;
-  const long long total = (long long)cout32 * cin8 * 256 + 2LL * cout32 * 32;
-  long long blocks = (total + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(pn2::mlp_pack_kernel, dim3((unsigned)blocks), dim3(256), 0,
-                     (hipStream_t)stream, weight, bias, bn_scale, bn_shift, cin, cout, cin8,
-                     cout32, static_cast<float*>(packed));
-  PN2_RETURN_LAUNCH();
+  return pn2::pack(false, weight, bias, bn_scale, bn_shift, cin, cout, packed, packed_bytes, stream);
 }
-
-size_t pn2_mlp_packed_size_bf16(int cin, int cout) {
-  if (cin <= 0 || cout <= 0) return 0;
-  const size_t cin16 = (size_t)(cin + 15) / 16, cout32 = (size_t)(cout + 31) / 32;
-  return cout32 * cin16 * 512 * sizeof(uint16_t) + 2 * cout32 * 32 * sizeof(float);
-}
-
 int pn2_mlp_pack_bf16(const float* weight, const float* bias, const float* bn_scale,
                       const float* bn_shift, int cin, int cout, void* packed,
                       size_t packed_bytes, pn2_stream_t stream) {
-  if (cin <= 0 || cout <= 0 || !weight || !packed) return PN2_EINVAL;
-  if (packed_bytes < pn2_mlp_packed_size_bf16(cin, cout)) return PN2_EINVAL;
-  if ((!bn_scale) != (!bn_shift)) return PN2_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0) return PN2_EINVAL;
-  const int cin16 = (cin + 15) / 16, cout32 = (cout + 31) / 32;
-  const long long total = (long long)cout32 * cin16 * 512 + 2LL * cout32 * 32;
-  long long blocks = (total + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(pn2::mlp_pack_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0,
-                     (hipStream_t)stream, weight, bias, bn_scale, bn_shift, cin, cout, cin16,
-                     cout32, packed);
-  PN2_RETURN_LAUNCH();
+  return pn2::pack(true, weight, bias, bn_scale, bn_shift, cin, cout, packed, packed_bytes, stream);
 }
 
 static int group_mlp_impl(const float* xyz, const float* points, const float* new_xyz,
@@ -1497,7 +1428,7 @@ static int group_mlp_impl(const float* xyz, const float* points, const float* ne
     for (int i = 0; i < 3; ++i) {
       if (!qkv[i].packed || qkv[i].cin != Ca || qkv[i].cout != Ca || (qkv[i].flags & PN2_MLP_RELU))
         return PN2_EINVAL;
-      if ((reinterpret_cast<uintptr_t>(qkv[i].packed) & 15) != 0) return PN2_EINVAL;
+      if (!aligned16(qkv[i].packed)) return PN2_EINVAL;
     }
     // the query runs on the VALU from the fp32 layout (attn_query): it has no bf16 form
     if (qkv[0].flags & PN2_MLP_BF16) return PN2_EINVAL;
@@ -1518,7 +1449,7 @@ static int group_mlp_impl(const float* xyz, const float* points, const float* ne
   if (ngroups == 0) return PN2_OK;
   if (!xyz || !new_xyz || !idx || !out || ngroups > 0x7fffffffLL) return PN2_EINVAL;
   // the attention tail loads bn_scale / bn_shift and stores out in float4 units (attn_scores)
-  if (qkv && !(aligned16(out) && aligned16(bn_scale) && aligned16(bn_shift))) return PN2_EINVAL;
+  if (qkv && !aligned16(out, bn_scale, bn_shift)) return PN2_EINVAL;
   if ((long long)B * N > 0x7fffffffLL || ngroups * nsample > 0x7fffffffLL) return PN2_EINVAL;
   const bool pooled = pool >= 0;
   size_t lds = 0;

@@ -30,16 +30,12 @@
 // grad_y[r + (lane >> 5)][co0 + (lane & 31)]: two row segments straight from the row-major
 // tensors, no transpose. The four waves of a workgroup interleave the row pairs of a slab and
 // their accumulators are added through LDS in wave order. pn2_mlp_wgrad_bf16 is the same kernel
-// on v_mfma_f32_32x32x16_bf16 (wgrad_partial_bf16), 16 rows per MFMA.
+// on v_mfma_f32_32x32x16_bf16 (wgrad_partial<NJ, true>), 16 rows per MFMA.
 #include "chan_rows.h"
 #include "common.h"
 
 namespace pn2 {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 using namespace chan_rows;
 
@@ -432,26 +428,25 @@ __global__ __launch_bounds__(kBlock) void bn_pool_bwd_apply_split(
 }
 
 // ---------------------------------------------------------------- weight gradient -------
-// eight fp32 to one bf16 MFMA operand (element j in bits 16 j ..), round to nearest even
-PN2_DEV bf16x8 pack_bf16x8(const float (&v)[8]) {
-  u32x4 p;
-  p.x = cvt_pk_bf16(v[0], v[1]);
-  p.y = cvt_pk_bf16(v[2], v[3]);
-  p.z = cvt_pk_bf16(v[4], v[5]);
-  p.w = cvt_pk_bf16(v[6], v[7]);
-  return __builtin_bit_cast(bf16x8, p);
-}
-
 // blockIdx.x = part p (slabs p, p + nparts, ...), blockIdx.y = (ti, tjg): input-channel tile
 // ti and output-channel tiles tjg * NJ .. + NJ - 1. Partial tiles are stored in accumulator
 // order e = reg * 64 + lane: ci = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5), co = lane & 31.
-template <int NJ>
+//
+// BF: the same stage 1 on v_mfma_f32_32x32x16_bf16 (pn2_mlp_wgrad_bf16): lane (h = lane >> 5,
+// i = lane & 31) holds A[i][8h + j] and B[8h + j][i], j = 0..7, so one MFMA covers 16 rows and a
+// lane loads x[r + 8h + j][ci0 + i] and grad_y[r + 8h + j][co0 + i] for eight j: per j two
+// 128-byte row segments per wave, straight from the row-major tensors, rounded to bf16 pairs on
+// the way in. The four waves interleave the 16-row blocks of a slab (16 MFMAs per wave and tile
+// from zero). Only the operand loads and the MFMA differ: the accumulator layout, the LDS sum,
+// the double slab sum and the partial tiles are one text, so wgrad_final serves both.
+template <int NJ, bool BF>
 __global__ __launch_bounds__(kBlock) void wgrad_partial(const float* __restrict__ x,
                                                         const float* __restrict__ gy,
                                                         long long rows, int cin, int cout,
                                                         int cout32, int nslabs, int nparts,
                                                         float* __restrict__ part) {
-  constexpr int U = 8;
+  // in flight per wave: row pairs (fp32), 16-row blocks (bf16)
+  constexpr int U = BF ? (NJ == 4 ? 2 : 4) : 8;
   __shared__ float sh[4][kTile];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int tjn = (cout32 + NJ - 1) / NJ;
@@ -483,118 +478,52 @@ __global__ __launch_bounds__(kBlock) void wgrad_partial(const float* __restrict_
     for (int j = 0; j < NJ; ++j)
 #pragma unroll
       for (int k = 0; k < 16; ++k) acc[j][k] = 0.f;
-    // wave w takes row pairs w, w + 4, ...: rows 2 (w + 4 t) + kh
-    for (int t0 = 0; 8 * t0 < nr; t0 += U) {
-      float a[U], b[NJ][U];
+    if constexpr (BF) {
+      // wave w takes 16-row blocks w, w + 4, ...: rows 16 (w + 4 t) + 8 kh + j
+      for (int t0 = 0; 64 * t0 < nr; t0 += U) {
+        float a[U][8], b[NJ][U][8];
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int r = 2 * (w + 4 * (t0 + u)) + kh;
-        const bool ok = r < nr;
-        const long long row = r0 + r;
-        a[u] = (ok && ci_ok) ? x[row * cin + ci] : 0.f;
+        for (int u = 0; u < U; ++u)
 #pragma unroll
-        for (int j = 0; j < NJ; ++j)
-          b[j][u] = (j < nj && ok && co_ok[j]) ? gy[row * cout + co[j]] : 0.f;
-      }
+          for (int k = 0; k < 8; ++k) {
+            const int r = 16 * (w + 4 * (t0 + u)) + 8 * kh + k;
+            const bool ok = r < nr;
+            const long long row = r0 + r;
+            a[u][k] = (ok && ci_ok) ? x[row * cin + ci] : 0.f;
 #pragma unroll
-      for (int u = 0; u < U; ++u)
+            for (int j = 0; j < NJ; ++j)
+              b[j][u][k] = (j < nj && ok && co_ok[j]) ? gy[row * cout + co[j]] : 0.f;
+          }
 #pragma unroll
-        for (int j = 0; j < NJ; ++j)
-          if (j < nj) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[j][u], acc[j], 0, 0, 0);
-    }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      if (j >= nj) break;  // uniform over the workgroup
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < 16; ++k) sh[w][k * 64 + lane] = acc[j][k];
-      __syncthreads();
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int e = threadIdx.x + kBlock * q;
-        tot[j][q] += (double)(((sh[0][e] + sh[1][e]) + sh[2][e]) + sh[3][e]);
-      }
-    }
-  }
-  const int ntiles = gridDim.y / tjn * cout32;  // cin32 * cout32
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int tj = tjg * NJ + j;
-    if (tj >= cout32) continue;
-    float* dst = part + ((size_t)p * ntiles + (size_t)ti * cout32 + tj) * kTile;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) dst[threadIdx.x + kBlock * q] = (float)tot[j][q];
-  }
-}
-
-// The same stage 1 on v_mfma_f32_32x32x16_bf16 (pn2_mlp_wgrad_bf16): lane (h = lane >> 5,
-// i = lane & 31) holds A[i][8h + j] and B[8h + j][i], j = 0..7, so one MFMA covers 16 rows and a
-// lane loads x[r + 8h + j][ci0 + i] and grad_y[r + 8h + j][co0 + i] for eight j: per j two
-// 128-byte row segments per wave, straight from the row-major tensors, rounded to bf16 pairs on
-// the way in. The four waves interleave the 16-row blocks of a slab (16 MFMAs per wave and tile
-// from zero); the accumulator layout, the LDS sum, the double slab sum and the partial tiles are
-// wgrad_partial's, so wgrad_final serves both.
-template <int NJ>
-__global__ __launch_bounds__(kBlock) void wgrad_partial_bf16(const float* __restrict__ x,
-                                                             const float* __restrict__ gy,
-                                                             long long rows, int cin, int cout,
-                                                             int cout32, int nslabs, int nparts,
-                                                             float* __restrict__ part) {
-  constexpr int U = NJ == 4 ? 2 : 4;  // 16-row blocks in flight per wave
-  __shared__ float sh[4][kTile];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int tjn = (cout32 + NJ - 1) / NJ;
-  const int ti = blockIdx.y / tjn, tjg = blockIdx.y % tjn;
-  const int p = blockIdx.x;
-  const int kh = lane >> 5;
-  const int ci = ti * 32 + (lane & 31);
-  const bool ci_ok = ci < cin;
-  int co[NJ];
-  bool co_ok[NJ];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    co[j] = (tjg * NJ + j) * 32 + (lane & 31);
-    co_ok[j] = co[j] < cout;
-  }
-  // output tiles of this group that exist (the last group may hold fewer than NJ): uniform
-  const int nj = min(NJ, cout32 - tjg * NJ);
-  double tot[NJ][4];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) tot[j][q] = 0.0;
-
-  for (int s = p; s < nslabs; s += nparts) {
-    const long long r0 = (long long)s * kSlab;
-    const int nr = block_rows(rows, r0, kSlab);
-    f32x16 acc[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int k = 0; k < 16; ++k) acc[j][k] = 0.f;
-    // wave w takes 16-row blocks w, w + 4, ...: rows 16 (w + 4 t) + 8 kh + j
-    for (int t0 = 0; 64 * t0 < nr; t0 += U) {
-      float a[U][8], b[NJ][U][8];
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const int r = 16 * (w + 4 * (t0 + u)) + 8 * kh + k;
-          const bool ok = r < nr;
-          const long long row = r0 + r;
-          a[u][k] = (ok && ci_ok) ? x[row * cin + ci] : 0.f;
+        for (int u = 0; u < U; ++u) {
+          const bf16x8 av = pack_bf16x8(a[u]);
 #pragma unroll
           for (int j = 0; j < NJ; ++j)
-            b[j][u][k] = (j < nj && ok && co_ok[j]) ? gy[row * cout + co[j]] : 0.f;
+            if (j < nj)
+              acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, pack_bf16x8(b[j][u]), acc[j],
+                                                               0, 0, 0);
+        }
+      }
+    } else {
+      // wave w takes row pairs w, w + 4, ...: rows 2 (w + 4 t) + kh
+      for (int t0 = 0; 8 * t0 < nr; t0 += U) {
+        float a[U], b[NJ][U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int r = 2 * (w + 4 * (t0 + u)) + kh;
+          const bool ok = r < nr;
+          const long long row = r0 + r;
+          a[u] = (ok && ci_ok) ? x[row * cin + ci] : 0.f;
+#pragma unroll
+          for (int j = 0; j < NJ; ++j)
+            b[j][u] = (j < nj && ok && co_ok[j]) ? gy[row * cout + co[j]] : 0.f;
         }
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const bf16x8 av = pack_bf16x8(a[u]);
+        for (int u = 0; u < U; ++u)
 #pragma unroll
-        for (int j = 0; j < NJ; ++j)
-          if (j < nj)
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, pack_bf16x8(b[j][u]), acc[j], 0,
-                                                             0, 0);
+          for (int j = 0; j < NJ; ++j)
+            if (j < nj)
+              acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[j][u], acc[j], 0, 0, 0);
       }
     }
 #pragma unroll
@@ -690,9 +619,9 @@ int wgrad_launch(bool bf16, const float* x, const float* grad_y, long long rows,
   float* part = static_cast<float*>(workspace);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(nparts, (unsigned)gy);
-  auto* stage1 = nj == 4 ? (bf16 ? wgrad_partial_bf16<4> : wgrad_partial<4>)
-                 : nj == 2 ? (bf16 ? wgrad_partial_bf16<2> : wgrad_partial<2>)
-                           : (bf16 ? wgrad_partial_bf16<1> : wgrad_partial<1>);
+  auto* stage1 = nj == 4 ? (bf16 ? wgrad_partial<4, true> : wgrad_partial<4, false>)
+                 : nj == 2 ? (bf16 ? wgrad_partial<2, true> : wgrad_partial<2, false>)
+                           : (bf16 ? wgrad_partial<1, true> : wgrad_partial<1, false>);
   hipLaunchKernelGGL(stage1, grid, dim3(kBlock), 0, s, x, grad_y, rows, cin, cout, cout32, nslabs,
                      nparts, part);
   hipLaunchKernelGGL(wgrad_final, dim3((unsigned)(ntiles * kTile / kBlock)), dim3(kBlock), 0, s,

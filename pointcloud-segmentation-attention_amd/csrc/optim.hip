@@ -68,7 +68,7 @@ __global__ __launch_bounds__(kAdamThreads) void adam_kernel(const AdamArgs a) {
   float* m = s.m + e0;
   float* v = s.v + e0;
   const float alpha = a.alpha, omb1 = a.omb1, omb2 = a.omb2, eps = a.epsilon;
-  const bool vec = ((((uintptr_t)s.p | (uintptr_t)s.g | (uintptr_t)s.m | (uintptr_t)s.v) & 15u) == 0);
+  const bool vec = aligned16(s.p, s.g, s.m, s.v);
   int done = 0;
   if (vec) {  // uniform over the workgroup
     const int len4 = len >> 2;

@@ -148,7 +148,7 @@ int pn2_plan_fps_chain_grid(pn2_plan* plan, const float* xyz, int B, int N, int 
   const int rc = pn2::fps_chain_check(xyz, B, N, nstages, npoint, idx, new_xyz);
   if (rc != PN2_OK) return rc;
   if (grid0 && (!new_xyz[0] || grid0_bytes < pn2_grid_size(B, npoint[0]) ||
-                ((uintptr_t)grid0 & 15)))
+                !pn2::aligned16(grid0)))
     return PN2_EINVAL;
   Op o = blank(kFpsChain, (hipStream_t)stream, nullptr);
   o.xyz = xyz;

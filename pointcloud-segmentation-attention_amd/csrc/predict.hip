@@ -126,7 +126,7 @@ __global__ __launch_bounds__(kBlock) void scene_labels_kernel(
 __global__ __launch_bounds__(kBlock) void map_back_rows_kernel(
     const uint8_t* __restrict__ values, int row_bytes, long long row0, long long rows,
     const unsigned long long* __restrict__ keys, int n_scene, uint8_t* __restrict__ out) {
-  const bool v16 = (row_bytes & 15) == 0 && ((uintptr_t)values & 15) == 0 && ((uintptr_t)out & 15) == 0;
+  const bool v16 = (row_bytes & 15) == 0 && aligned16(values, out);
   const int units = v16 ? row_bytes / 16 : row_bytes / 4;
   const long long total = (long long)n_scene * units;
   for (long long e = (long long)blockIdx.x * kBlock + threadIdx.x; e < total;

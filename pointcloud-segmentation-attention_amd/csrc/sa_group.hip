@@ -347,7 +347,7 @@ int pn2_ball_group_layers(const pn2_sa_layer* layers, int nlayers, int B, pn2_st
     g.div_c4 = pn2::make_fastdiv((uint32_t)(s.C / 4 > 0 ? s.C / 4 : 1));
     g.vec = layout != PN2_SG_XYZ_ONLY && s.C % 4 == 0 && s.nsample % 4 == 0 &&
             !s.grouped_xyz && 4 * Cout <= pn2::kSgVecFloats &&
-            (((uintptr_t)s.points | (uintptr_t)s.new_points) & 15) == 0;
+            aligned16(s.points, s.new_points);
     a.first[i] = (int)blocks;
     blocks += (long long)g.tiles * g.parts;  // per cloud
     if (blocks * B >= (1LL << 31) - 8) return PN2_EINVAL;

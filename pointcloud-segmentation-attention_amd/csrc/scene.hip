@@ -282,7 +282,7 @@ __global__ __launch_bounds__(kBlock) void gather_rows_kernel(const uint8_t* __re
                                                              long long nsrc, int row_bytes,
                                                              const int32_t* __restrict__ idx,
                                                              long long n, uint8_t* __restrict__ dst) {
-  const bool v16 = (row_bytes & 15) == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0;
+  const bool v16 = (row_bytes & 15) == 0 && aligned16(src, dst);
   const int units = v16 ? row_bytes / 16 : row_bytes / 4;
   const long long total = n * units;
   for (long long e = (long long)blockIdx.x * kBlock + threadIdx.x; e < total;
