@@ -479,8 +479,9 @@ int pn2_three_interpolate_grad_ordered(const float* grad_out, int ld, int col0, 
 
 /* ---------------------------------------------------------------- attention / pooling --- */
 
-/* AttentionLayer reduction core (attention_layer.py:35-42) with key_dim = output_dim = 4,
- * heads H = C/4. Q (B,M,C), K,V (B,M,ns,C) → out (B,M,C). Head h reads the CONTIGUOUS
+/* AttentionLayer reduction core (attention_layer.py:35-42) with key_dim = output_dim = 4 (the
+ * SA attention modules; any other key_dim: pn2_attn_reduce_kd), heads H = C/4. Q (B,M,C),
+ * K,V (B,M,ns,C) → out (B,M,C). Head h reads the CONTIGUOUS
  * block [4*ns*h, 4*ns*(h+1)) of each group's flattened ns*C K/V values as ns rows of 4
  * (the reference's tf.reshape reinterpretation), s = (K_h·q_h)/2, a = softmax(s),
  * out[4h:4h+4] = aᵀ V_h. C must be a multiple of 4; Q, K, V and out 16-byte aligned
@@ -508,6 +509,36 @@ int pn2_attn_reduce_layers(const pn2_attn_layer* layers, int nlayers, int B,
 int pn2_attn_reduce_grad(const float* Q, const float* K, const float* V, const float* grad_out,
                          int B, int M, int ns, int C, float* grad_Q, float* grad_K,
                          float* grad_V, pn2_stream_t stream);
+/* The same reduction for any key_dim (csrc/attn_net.hip): the attention networks build
+ * AttentionLayer(out_dim, key_dim=out_dim) with 16 heads, key_dim 8 .. 512 (attention_layer.py
+ * :142, :185, pooling_attention_layer.py:17). C = H * key_dim. Head h reads the CONTIGUOUS block
+ * [h*ns*kd, (h+1)*ns*kd) of each group's flattened ns*C K / V values as ns rows of kd,
+ * s = (K_h q_h) / sqrtf(kd), a = softmax(s), out[h*kd : (h+1)*kd] = aᵀ V_h, fp32 throughout.
+ * key_dim % 4 == 0, 4 <= key_dim <= 512, C % key_dim == 0, ns >= 1, every pointer 16-byte
+ * aligned: PN2_EINVAL otherwise, before any launch. No groups: PN2_OK. key_dim == 4 IS
+ * pn2_attn_reduce / pn2_attn_reduce_grad (the same bits). The backward writes every element of
+ * grad_Q (B,M,C) and grad_K / grad_V (B,M,ns,C) exactly once (no atomics: two runs, equal bits).
+ * Beyond PN2_ATTN_NET_MAX_BLOCKS blocks of four (group, head) waves the grid strides. */
+#define PN2_ATTN_NET_MAX_BLOCKS 4096
+int pn2_attn_reduce_kd(const float* Q, const float* K, const float* V, int B, int M, int ns,
+                       int C, int key_dim, float* out, pn2_stream_t stream);
+int pn2_attn_reduce_kd_grad(const float* Q, const float* K, const float* V,
+                            const float* grad_out, int B, int M, int ns, int C, int key_dim,
+                            float* grad_Q, float* grad_K, float* grad_V, pn2_stream_t stream);
+/* InnerAttentionLayer.call (attention_layer.py:61-78): attention among the heads of ONE point,
+ * never across the group. qkv (rows, 3*H*kd) holds [Q | K | V] per row, each H vectors of kd
+ * (one GEMM over [Wq | Wk | Wv] writes it). S[i][j] = (Q_i . K_j) / sqrtf(kd), A = softmax over
+ * j, out (rows, H*kd) row = [sum_j A[0][j] V_j | .. | sum_j A[H-1][j] V_j]. pn2_head_mix_grad:
+ * grad_qkv (rows, 3*H*kd) from grad_out (rows, H*kd), every element written once.
+ * 1 <= heads <= PN2_HEAD_MIX_MAX_HEADS, key_dim % 4 == 0, 4 <= key_dim <= 256, 16-byte aligned
+ * pointers (PN2_EINVAL otherwise, before any launch); no rows: PN2_OK. 64 / (key_dim / 4 rounded
+ * up to a power of two) rows share a wave; beyond PN2_ATTN_NET_MAX_BLOCKS blocks the grid
+ * strides. */
+#define PN2_HEAD_MIX_MAX_HEADS 8
+int pn2_head_mix(const float* qkv, long long rows, int heads, int key_dim, float* out,
+                 pn2_stream_t stream);
+int pn2_head_mix_grad(const float* qkv, const float* grad_out, long long rows, int heads,
+                      int key_dim, float* grad_qkv, pn2_stream_t stream);
 /* Per-group pooling over nsample (pointnet_util.py:130-145): x (B,M,ns,C) → out (B,M,C),
  * or (B,M,2C) = [avg, max] for PN2_POOL_MAX_AND_AVG. grouped_xyz (B,M,ns,3) is read only
  * by PN2_POOL_WEIGHTED_AVG (w = exp(-5|xyz|)/sum). */

@@ -50,6 +50,18 @@ and the training-mode AttentionLayer of the attention SA modules (csrc/attn_trai
     bn_train_grad(grad_out, x, mean, var, gamma, beta, eps, relu)
                                                          -> (grad_x, grad_gamma, grad_beta)
 
+and the reductions of the reference's attention networks (attention_scannet's AttentionNetLayer,
+AttentionNetMLPLayer, PoolingAttentionNetLayer; csrc/attn_net.hip), listed in ATTN_NET_NAMES,
+with autograd for attn_reduce_kd (Q, K, V) and head_mix (qkv):
+
+    attn_reduce_kd(Q, K, V, key_dim)                    attention_layer.py:29-45 for any key_dim
+                         % 4 == 0 up to 512, C = heads * key_dim; key_dim 4 is attn_reduce
+    attn_reduce_kd_grad(Q, K, V, grad_out, key_dim)     -> (grad_Q, grad_K, grad_V)
+    head_mix(qkv, heads, key_dim)                       InnerAttentionLayer.call (:61-78): qkv
+                         (..., 3 * heads * key_dim) = [Q | K | V] per point, softmax((Q_i . K_j) /
+                         sqrt(key_dim)) over the point's own heads -> (..., heads * key_dim)
+    head_mix_grad(qkv, grad_out, heads, key_dim)        -> grad_qkv
+
 and the training-mode segmentation head (csrc/head_train.hip):
 
     dropout(x, keep_prob, seed)                         tf_util.py:594-612 with is_training: the
@@ -129,7 +141,9 @@ FEED_NAMES = ("feed_batch", "val_select", "val_chunks")
 # the training layer's opt-in bf16 matrix-core mode (device-only, like NAMES)
 TRAIN_BF16_NAMES = ("mlp_layer_train_bf16", "mlp_layer_train_bf16_grad",
                     "mlp_layer_train_pool_bf16", "mlp_layer_train_pool_bf16_grad")
-for _n in NAMES + HOST_NAMES + FEED_NAMES + TRAIN_BF16_NAMES:
+# the attention networks' reductions (csrc/attn_net.hip; device-only, like NAMES)
+ATTN_NET_NAMES = ("attn_reduce_kd", "attn_reduce_kd_grad", "head_mix", "head_mix_grad")
+for _n in NAMES + HOST_NAMES + FEED_NAMES + TRAIN_BF16_NAMES + ATTN_NET_NAMES:
     globals()[_n] = getattr(_ops, _n)
 
-__all__ = list(NAMES + HOST_NAMES + FEED_NAMES + TRAIN_BF16_NAMES)
+__all__ = list(NAMES + HOST_NAMES + FEED_NAMES + TRAIN_BF16_NAMES + ATTN_NET_NAMES)

@@ -27,16 +27,21 @@ Drop-in modules (reference names, argument order, shapes, dtypes, error messages
   evaluate               evaluate_scan, get_iou, evaluate, write_result_file (the ScanNet
                          benchmark score)
   complete_scene_loader  the whole-scene chunker (selection + gathers on the GPU)
-  attention_layer attention_reduce, AttentionLayer
+  attention_layer attention_reduce, AttentionLayer (any key_dim % 4 == 0), and the attention
+                  networks' layers: InnerAttentionLayer, FeedForwardLayer, InnerAttentionBlock,
+                  AttentionNetLayer, AttentionNetMLPLayer
+  pooling_attention_layer  PoolingAttentionNetLayer
+  attention_models         AttentionNetModel, AttentionNetFeatureModel, AttentionNetMLPModel
+  pooling_attention_model  PoolingAttentionNetModel
 Everything runs the gfx950 kernels of libpn2hip.so (C ABI: include/pn2hip.h).
 
 The directory name has hyphens, so import it with importlib:
     pn2 = importlib.import_module("pointcloud-segmentation-attention_amd")
 """
-from . import attention_layer, complete_scene_loader, compute_class_weights, data_transformation, evaluate, \
+from . import attention_layer, attention_models, complete_scene_loader, compute_class_weights, data_transformation, evaluate, \
     generate_predictions, grid, plan, pointnet2_sem_seg, pointnet2_sem_seg_attention, \
     pointnet2_sem_seg_attention_and_pooling, pointnet2_sem_seg_attention_single_layer, \
-    pointnet2_sem_seg_features, pointnet_util, shard, stack, synth, tf_grouping, tf_interpolate, tf_sampling, \
+    pointnet2_sem_seg_features, pointnet_util, pooling_attention_layer, pooling_attention_model, shard, stack, synth, tf_grouping, tf_interpolate, tf_sampling, \
     tf_util, train
 from .data_transformation import random_rotate, rotation_cs, scene_val_chunks
 from .generate_predictions import predict_scene
@@ -48,6 +53,7 @@ __all__ = ["tf_sampling", "tf_grouping", "tf_interpolate", "pointnet_util", "att
            "synth", "stack", "shard", "plan", "pointnet2_sem_seg", "pointnet2_sem_seg_features", "train",
            "generate_predictions", "evaluate", "predict_scene", "eval_step",
            "pointnet2_sem_seg_attention", "pointnet2_sem_seg_attention_and_pooling",
-           "pointnet2_sem_seg_attention_single_layer", "compute_class_weights", "random_rotate", "rotation_cs",
+           "pointnet2_sem_seg_attention_single_layer", "attention_models", "pooling_attention_layer",
+           "pooling_attention_model", "compute_class_weights", "random_rotate", "rotation_cs",
            "scene_val_chunks", "CLASS_WEIGHTS", "get_data_tensors", "eval_model", "train_step_with",
            "AdamOptimizer", "SegMetrics", "get_learning_rate", "get_bn_decay", "train_step", "lib", "LIB_PATH", "InvalidArgumentError", "Pn2RuntimeError"]

@@ -4,7 +4,8 @@ argument order, one body per op that launches on the current HIP stream and, reg
 Meta as well, gives fake tensors / torch.compile the same checks and output shapes. This module loads the library and registers autograd for the ops the
 reference registers gradients for, w.r.t. the points only (tf_sampling.py:44-48 GatherPoint,
 tf_grouping.py:42-46 GroupPoint, tf_interpolate.py:29-34 ThreeInterpolate), plus the attention
-reduction (TF autodiff through attention_layer.py:35-42, all of Q, K, V) and the training-mode
+reduction (TF autodiff through attention_layer.py:35-42, all of Q, K, V; attn_reduce_kd for any
+key_dim, and head_mix, the attention among one point's heads of :61-78: csrc/attn_net.hip) and the training-mode
 shared-MLP layer (mlp_layer_train, and mlp_layer_train_pool for the layer fused with the max
 pool over nsample: x, weight, bias, gamma, beta; csrc/mlp_train.hip; their _bf16 namesakes, the
 layer's opt-in bf16 matrix-core mode, use the _bf16 grad ops), the training-mode attention
@@ -82,6 +83,24 @@ def _register_autograd():
         Q, K, V = ctx.saved_tensors
         return tuple(torch.ops.pn2.attn_reduce_grad(Q, K, V, grad.contiguous()))
 
+    def attn_kd_setup(ctx, inputs, output):
+        *qkv, ctx.key_dim = inputs
+        ctx.save_for_backward(*qkv)
+
+    def attn_kd_bwd(ctx, grad):
+        Q, K, V = ctx.saved_tensors
+        return tuple(torch.ops.pn2.attn_reduce_kd_grad(Q, K, V, grad.contiguous(),
+                                                       ctx.key_dim)) + (None,)
+
+    def head_mix_setup(ctx, inputs, output):
+        qkv, ctx.heads, ctx.key_dim = inputs
+        ctx.save_for_backward(qkv)
+
+    def head_mix_bwd(ctx, grad):
+        qkv, = ctx.saved_tensors
+        return torch.ops.pn2.head_mix_grad(qkv, grad.contiguous(), ctx.heads,
+                                           ctx.key_dim), None, None
+
     def mlp_setup(ctx, inputs, output, bf16=False):
         # mlp_layer_train returns (out, y, mean, var), mlp_layer_train_pool the pool's arg too
         x, weight, bias, gamma, beta, eps, relu = inputs
@@ -149,3 +168,5 @@ def _register_autograd():
     reg("pn2::group_point", group_bwd, setup_context=save_all)
     reg("pn2::three_interpolate", interp_bwd, setup_context=save_all)
     reg("pn2::attn_reduce", attn_bwd, setup_context=save_all)
+    reg("pn2::attn_reduce_kd", attn_kd_bwd, setup_context=attn_kd_setup)
+    reg("pn2::head_mix", head_mix_bwd, setup_context=head_mix_setup)

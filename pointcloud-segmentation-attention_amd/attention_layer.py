@@ -3,37 +3,49 @@
 attention_reduce is the reduction core of AttentionLayer.call (:35-42) as one gfx950 kernel.
 AttentionLayer mirrors the reference layer (:10-45): its Dense query/key/value projections
 (:24-26) are plain torch Linear layers (dense contractions are outside the hot path), the
-reduction is the kernel. The reference instantiates it with key_dim = output_dim = 4 and
-num_heads = C/4 (:256-258, :313-315); that is the configuration the kernel implements.
+reduction is the kernel. The SA attention modules instantiate it with key_dim = output_dim = 4
+and num_heads = C/4 (:256-258, :313-315): csrc/attn.hip. The attention networks (:128-210,
+pooling_attention_layer.py) instantiate it with key_dim = output_dim = out_dim, 8 to 512, and 16
+heads: csrc/attn_net.hip, which also holds the head mixing of InnerAttentionLayer (:48-78). The
+networks' layers are at the end of this module.
 """
 import ctypes
+import functools
 
 import torch
 
 from . import pointnet_util, tf_grouping, tf_sampling, tf_util
-from ._lib import (PN2_ATTN_MAX_LAYERS, AttnLayer, InvalidArgumentError, aligned_device_tensor,
-                   check, device_tensor, lib, ptr, stream_of)
+from ._lib import (PN2_ATTN_MAX_LAYERS, PN2_MLP_MAX_LAYERS, AttnLayer, InvalidArgumentError,
+                   MlpLayer, aligned_device_tensor, check, device_tensor, lib, ptr, stream_of)
 from ._torch_ops import call
 
 
-def attention_reduce(Q, K, V):
-    """Q (B,M,C), K,V (B,M,ns,C) -> (B,M,C), C = 4*heads.
+def attention_reduce(Q, K, V, key_dim=4):
+    """Q (B,M,C), K,V (B,M,ns,C) -> (B,M,C), C = key_dim*heads.
 
-    Per group and head h: K_h = the contiguous block [4*ns*h, 4*ns*(h+1)) of the group's
-    flattened K (the tf.reshape reinterpretation of :35-36), s = K_h q_h / 2 (:37-38),
-    a = softmax(s) (:39), out[4h:4h+4] = a^T V_h (:40-42).
+    Per group and head h, with kd = key_dim: K_h = the contiguous block [kd*ns*h, kd*ns*(h+1)) of
+    the group's flattened K (the tf.reshape reinterpretation of :35-36), s = K_h q_h / sqrt(kd)
+    (:37-38), a = softmax(s) (:39), out[kd*h : kd*(h+1)] = a^T V_h (:40-42). key_dim = 4 (the SA
+    attention modules) is torch.ops.pn2.attn_reduce; any other multiple of 4 up to 512 (the
+    attention networks, key_dim = out_dim) is torch.ops.pn2.attn_reduce_kd (csrc/attn_net.hip).
     """
     if Q.dim() == 4 and Q.shape[2] == 1:  # the reference's (B,M,1,C) query vectors (:259)
         Q = Q.squeeze(2)
     if Q.dim() != 3 or K.dim() != 4 or tuple(V.shape) != tuple(K.shape):
         raise InvalidArgumentError("attention_reduce expects Q (B,M,C), K and V (B,M,ns,C)")
     B, M, ns, C = (int(s) for s in K.shape)
-    if tuple(Q.shape) != (B, M, C) or C % 4 != 0:
-        raise InvalidArgumentError("attention_reduce expects Q (B,M,C) with C a multiple of 4")
+    key_dim = int(key_dim)
+    if key_dim < 4 or key_dim > 512 or key_dim % 4 != 0:
+        raise InvalidArgumentError("attention_reduce expects key_dim % 4 == 0, 4 <= key_dim <= 512")
+    if tuple(Q.shape) != (B, M, C) or C % key_dim != 0:
+        raise InvalidArgumentError("attention_reduce expects Q (B,M,C) with C a multiple of "
+                                   f"{key_dim}")
+    tensors = (device_tensor(Q, "Q", torch.float32), device_tensor(K, "K", torch.float32),
+               device_tensor(V, "V", torch.float32))
     # torch.ops.pn2.attn_reduce (autograd: pn2_attn_reduce_grad, _torch_ops.py)
-    return call("attn_reduce", device_tensor(Q, "Q", torch.float32),
-                             device_tensor(K, "K", torch.float32),
-                             device_tensor(V, "V", torch.float32))
+    if key_dim == 4:
+        return call("attn_reduce", *tensors)
+    return call("attn_reduce_kd", *tensors, key_dim)
 
 
 def attention_reduce_layers(qkvs):
@@ -79,28 +91,41 @@ def attention_reduce_grad(Q, K, V, grad_out):
 
 
 class AttentionLayer(torch.nn.Module):
-    """attention_layer.py:10-45 with output_dim = key_dim = 4 (the reference's only use).
+    """attention_layer.py:10-45 with output_dim = key_dim: 4 in the SA attention modules
+    (:256-258, :313-315), out_dim = 8 .. 512 with the default 16 heads in the attention networks
+    (:142, :185, pooling_attention_layer.py:17).
 
-    forward([input, query]): input (B,M,ns,Cin), query (B,M,1,Cin) -> (B,M,num_heads*4).
+    forward([input, query]): input (B,M,ns,in_dim), query (B,M,1,query_dim) or (B,M,query_dim)
+    -> (B,M,num_heads*key_dim). in_dim defaults to num_heads*key_dim, query_dim to in_dim (the
+    pooling layer's query is new_xyz: query_dim = 3).
     """
 
-    def __init__(self, output_dim, key_dim, num_heads=16, in_dim=None):
+    def __init__(self, output_dim, key_dim, num_heads=16, in_dim=None, query_dim=None):
         super().__init__()
-        if output_dim != 4 or key_dim != 4:
-            raise NotImplementedError("the reference uses AttentionLayer(4, 4, heads) only")
+        if output_dim != key_dim:
+            # (:35-36) reshapes V, whose width is output_dim * num_heads, with key_dim: the
+            # reference's own graph is ill-formed unless the two agree
+            raise NotImplementedError(
+                f"AttentionLayer(output_dim={output_dim}, key_dim={key_dim}): the reference "
+                "reshapes the values with key_dim, so it is defined for output_dim == key_dim only")
+        if key_dim < 4 or key_dim > 512 or key_dim % 4 != 0:
+            raise NotImplementedError("AttentionLayer runs key_dim % 4 == 0, 4 <= key_dim <= 512 "
+                                      f"(float4 rows in csrc/attn_net.hip), got {key_dim}")
         self.output_dim, self.key_dim, self.num_heads = output_dim, key_dim, num_heads
         width = key_dim * num_heads
         in_dim = in_dim if in_dim is not None else width
-        self.query_net = torch.nn.Linear(in_dim, width)  # tf.layers.Dense (:24)
-        self.key_net = torch.nn.Linear(in_dim, width)    # (:25)
-        self.value_net = torch.nn.Linear(in_dim, width)  # (:26)
+        query_dim = query_dim if query_dim is not None else in_dim
+        self.query_net = torch.nn.Linear(query_dim, width)  # tf.layers.Dense (:24)
+        self.key_net = torch.nn.Linear(in_dim, width)       # (:25)
+        self.value_net = torch.nn.Linear(in_dim, width)     # (:26)
 
     def forward(self, inputs):
         x, query = inputs
         Q = self.query_net(query)
         K = self.key_net(x).contiguous()
         V = self.value_net(x).contiguous()
-        return attention_reduce(Q.reshape(Q.shape[0], Q.shape[1], -1).contiguous(), K, V)
+        return attention_reduce(Q.reshape(Q.shape[0], Q.shape[1], -1).contiguous(), K, V,
+                                self.key_dim)
 
 
 def _attention_scopes(scope):
@@ -251,3 +276,282 @@ def pointnet_sa_module_attention_and_pooling(xyz, points, npoint, radius, nsampl
     return pointnet_sa_module_attention(xyz, points, npoint, radius, nsample, mlp, mlp2,
                                         group_all, is_training, bn_decay, scope, bn, pooling, knn,
                                         use_xyz, use_nchw, params, and_pooling=True)
+
+
+# ------------------------------------------------------------------ the attention networks
+# attention_points/attention_scannet/attention_layer.py:48-210: InnerAttentionLayer,
+# FeedForwardLayer, InnerAttentionBlock, AttentionNetLayer, AttentionNetMLPLayer, store-based under
+# the reference's names and constructor arguments. Every class takes `scope=` (its variables are
+# '<scope>/...', hierarchical: INTEGRATION.md has the table and the TF1 `dense_<n>` order) and
+# `params=` (the ParamStore; default tf_util.default_store()). Calling a layer takes
+# is_training (None: the constructor's): on a trainable store it selects the HIP training layers.
+
+@functools.lru_cache(maxsize=None)
+def plan_accepts(cin, widths):
+    """Whether the fused MLP kernel takes a chain cin -> widths (pn2_shared_mlp_plan: host only,
+    the packed pointers are checked for alignment and never read). It refuses when a layer's
+    input row does not fit the LDS: 1027 input channels fit, 1280 do not."""
+    if not 1 <= len(widths) <= PN2_MLP_MAX_LAYERS:
+        return False
+    tab, c = (MlpLayer * len(widths))(), int(cin)
+    for i, w in enumerate(widths):
+        tab[i] = MlpLayer(1 << 20, c, int(w), 0)
+        c = int(w)
+    R, tpw = ctypes.c_int(0), ctypes.c_int(0)
+    return lib().pn2_shared_mlp_plan(32, int(cin), len(widths), tab, ctypes.addressof(R),
+                                     ctypes.addressof(tpw)) == 0
+
+
+def _layer_torch(x, L, is_training, bn_decay):
+    """One layer from differentiable torch ops (mlp_torch's arithmetic; the moving averages are
+    updated where they live): what a layer the fused kernel refuses falls back to."""
+    p = L.params
+    y = x @ p["weights"].to(x.device)
+    if p.get("biases") is not None:
+        y = y + p["biases"].to(x.device)
+    if p.get("gamma") is not None:
+        if is_training:
+            dims = tuple(range(y.dim() - 1))
+            mean, var = y.mean(dim=dims), y.var(dim=dims, unbiased=False)
+            decay = 0.9 if bn_decay is None else float(bn_decay)
+            with torch.no_grad():
+                for name, stat in (("moving_mean", mean), ("moving_variance", var)):
+                    p[name].mul_(decay).add_((1 - decay) * stat.detach().to(p[name].device))
+        else:
+            mean, var = p["moving_mean"].to(x.device), p["moving_variance"].to(x.device)
+        y = (y - mean) * (p["gamma"].to(x.device) / torch.sqrt(var + tf_util.BN_EPSILON)) + \
+            p["beta"].to(x.device)
+    return torch.relu(y) if L.relu else y
+
+
+def _flat(scopes):
+    return [s for sc in scopes for s in ((sc,) if isinstance(sc, str) else sc)]
+
+
+def _packed_chain(store, layers, scopes):
+    """SharedMLP of `layers` (tf_util.TorchLayer: Dense, or conv with batch norm), cached in the
+    store under the variables' scopes (an entry of `scopes` may be a tuple: one layer over
+    several Dense layers' variables side by side)."""
+    shape = tuple((tuple(L.params["weights"].shape), L.relu, "gamma" in L.params) for L in layers)
+    key = ("chain", tuple(_flat(scopes)), shape, store.precision)
+
+    def make():
+        return tf_util.SharedMLP([
+            tf_util.PackedLayer(L.params["weights"], L.params.get("biases"), L.params.get("gamma"),
+                                L.params.get("beta"), L.params.get("moving_mean"),
+                                L.params.get("moving_variance"), relu=L.relu, device=store.device,
+                                precision=store.precision) for L in layers])
+
+    return store.cached(key, _flat(scopes), tf_util.CONV_SUFFIXES + tf_util.DENSE_SUFFIXES, make)
+
+
+def run_layers(store, x, layers, scopes, is_training=False, bn_decay=None):
+    """x (..., cin) through `layers` (tf_util.TorchLayer each, with the scope(s) of its variables
+    in `scopes`). Inference: ONE fused kernel for the chain (tf_util.SharedMLP) when
+    pn2_shared_mlp_plan accepts it, else layer by layer. is_training on a trainable store: the
+    HIP training layers (tf_util.mlp_train; Dense layers have no batch norm), with gradients for
+    x and every variable. Otherwise (is_training on a plain store, or an input that requires a
+    gradient) the torch composition. A single layer whose widths the fused kernel refuses (or, in
+    training, whose transpose it refuses: the input gradient is the same kernel over W^T) runs
+    from torch ops; nothing else falls back."""
+    pu = pointnet_util
+    shapes = [tuple(int(s) for s in L.params["weights"].shape) for L in layers]
+    if is_training or pu._needs_grad(x):
+        hip = bool(is_training) and store.is_trainable
+        for L, (cin, cout) in zip(layers, shapes):
+            if hip and plan_accepts(cin, (cout,)) and plan_accepts(cout, (cin,)):
+                x = tf_util.mlp_train(x, [L], bn_decay)
+            else:
+                x = _layer_torch(x, L, is_training, bn_decay)
+        return x
+    if plan_accepts(shapes[0][0], tuple(s[1] for s in shapes)):
+        return _packed_chain(store, layers, scopes)(x)
+    with torch.no_grad():
+        for L, sc, (cin, cout) in zip(layers, scopes, shapes):
+            if plan_accepts(cin, (cout,)):
+                x = _packed_chain(store, [L], [sc])(x)
+            else:
+                x = _layer_torch(device_tensor(x, "inputs", torch.float32),
+                                 _device_layer(store, L, sc), False, None)
+    return x
+
+
+def _device_layer(store, L, scope):
+    """L with its variables by value on the store's device, cached like a packed layer (a plain
+    store keeps its variables on the host)."""
+    key = ("torch", tuple(_flat([scope])), tuple(L.params["weights"].shape), L.relu)
+
+    def make():
+        return tf_util.TorchLayer({k: v.detach().to(store.device) for k, v in L.params.items()
+                                   if v is not None}, relu=L.relu)
+
+    return store.cached(key, _flat([scope]), tf_util.CONV_SUFFIXES + tf_util.DENSE_SUFFIXES, make)
+
+
+def _dense_layer(store, scopes, cin, cout, relu=False):
+    """One tf_util.TorchLayer over one Dense layer's variables, or over several Dense layers of
+    one input side by side ([W_a | W_b | ...]: one GEMM)."""
+    if isinstance(scopes, str):
+        return tf_util.TorchLayer(store.dense(scopes, cin, cout), relu=relu,
+                                  train_precision=store.train_precision)
+    ps = [store.dense(s, cin, cout) for s in scopes]
+    dev = ps[0]["weights"].device
+    return tf_util.TorchLayer({"weights": torch.cat([p["weights"].to(dev) for p in ps], dim=1),
+                               "biases": torch.cat([p["biases"].to(dev) for p in ps])},
+                              relu=relu, train_precision=store.train_precision)
+
+
+def _store(params):
+    return params if params is not None else tf_util.default_store()
+
+
+def group_attention(store, scope, x, query, key_dim, num_heads=16, is_training=False):
+    """AttentionLayer.call (:29-45) on the store's variables '<scope>/{query,key,value}/
+    {kernel,bias}': x (B,M,ns,cin), query (B,M,cq) -> (B,M,num_heads*key_dim). Three Dense layers
+    (run_layers), then attention_reduce with key_dim."""
+    C = int(key_dim) * int(num_heads)
+    q, k, v = (f"{scope}/{n}" for n in ("query", "key", "value"))
+    cin, cq = int(x.shape[-1]), int(query.shape[-1])
+    Q = run_layers(store, query.contiguous(), [_dense_layer(store, q, cq, C)], [q], is_training)
+    K = run_layers(store, x, [_dense_layer(store, k, cin, C)], [k], is_training)
+    V = run_layers(store, x, [_dense_layer(store, v, cin, C)], [v], is_training)
+    return attention_reduce(Q, K, V, key_dim)
+
+
+class InnerAttentionLayer:
+    """attention_layer.py:48-78: attention among the 5 heads of ONE point (it never looks across
+    the group): Dense query | key | value of width 5*key_dim in one GEMM, torch.ops.pn2.head_mix,
+    then the Dense `out` to output_dim. Variables '<scope>/{query,key,value,out}/{kernel,bias}'."""
+    num_heads = 5
+
+    def __init__(self, output_dim, key_dim, scope="ScannetInnerAttentionLayer", params=None):
+        if key_dim % 4 or not 4 <= key_dim <= 256:
+            raise NotImplementedError("InnerAttentionLayer runs key_dim % 4 == 0, 4 <= key_dim <= "
+                                      f"256 (csrc/attn_net.hip), got {key_dim}")
+        self.output_dim, self.key_dim, self.scope, self.params = output_dim, key_dim, scope, params
+
+    def __call__(self, x, is_training=False):
+        store, H, kd = _store(self.params), self.num_heads, self.key_dim
+        qkv = tuple(f"{self.scope}/{n}" for n in ("query", "key", "value"))
+        y = run_layers(store, x, [_dense_layer(store, qkv, int(x.shape[-1]), H * kd)], [qkv],
+                       is_training)
+        y = call("head_mix", y, H, kd)
+        out = f"{self.scope}/out"
+        return run_layers(store, y, [_dense_layer(store, out, H * kd, self.output_dim)], [out],
+                          is_training)
+
+
+class FeedForwardLayer:
+    """attention_layer.py:81-105: Dense + ReLU three times (width inner_dim), then a Dense to
+    input_and_output_dim: one four-layer chain. The reference's dropout has rate 0. Variables
+    '<scope>/layer_{1..4}/{kernel,bias}'. relu_out: a ReLU on the result (AttentionNetMLPLayer
+    puts one between its blocks), folded into the last layer."""
+
+    def __init__(self, input_and_output_dim, inner_dim, dropout=0,
+                 scope="ScannetFeedForwardLayer", params=None):
+        if dropout:
+            raise NotImplementedError("FeedForwardLayer: the reference only builds it with "
+                                      "dropout = 0")
+        self.input_and_output_dim, self.inner_dim = input_and_output_dim, inner_dim
+        self.dropout, self.scope, self.params = dropout, scope, params
+
+    def __call__(self, x, is_training=False, relu_out=False):
+        store = _store(self.params)
+        widths = [self.inner_dim] * 3 + [self.input_and_output_dim]
+        scopes = [f"{self.scope}/layer_{i}" for i in (1, 2, 3, 4)]
+        layers, c = [], int(x.shape[-1])
+        for i, (sc, w) in enumerate(zip(scopes, widths)):
+            layers.append(_dense_layer(store, sc, c, w, relu=i < 3 or relu_out))
+            c = w
+        return run_layers(store, x, layers, scopes, is_training)
+
+
+class InnerAttentionBlock:
+    """attention_layer.py:108-125: p = pre_feed_forward(x); p = inner attention(p);
+    feed_forward(p) + p. Variables under '<scope>/{pre_feed_forward,inner_attention,
+    feed_forward}/'."""
+
+    def __init__(self, out_dim, key_dim, scope="ScannetInnerAttentionBlock", params=None):
+        self.out_dim, self.key_dim, self.scope, self.params = out_dim, key_dim, scope, params
+        self.attention_layer = InnerAttentionLayer(out_dim, key_dim,
+                                                   scope=f"{scope}/inner_attention", params=params)
+        self.feed_forward_layer = FeedForwardLayer(out_dim, out_dim,
+                                                   scope=f"{scope}/feed_forward", params=params)
+        self.pre_feed_forward_layer = FeedForwardLayer(
+            out_dim, out_dim, scope=f"{scope}/pre_feed_forward", params=params)
+
+    def __call__(self, x, is_training=False):
+        if isinstance(x, (list, tuple)):  # the reference passes a one-element list (:159)
+            x, = x
+        p = self.pre_feed_forward_layer(x, is_training)
+        p = self.attention_layer(p, is_training)
+        return self.feed_forward_layer(p, is_training) + p
+
+
+class _AttentionNetBase:
+    """sample_and_group (knn=False, use_xyz=True), the subclass's per-point blocks, then the
+    group attention with the group's first neighbour as the query (:166-167, :208-209)."""
+
+    def __init__(self, npoint, out_dim, inner_dimensions, is_training=True, radius=0.1, nsample=32,
+                 bn=True, scope=None, params=None):
+        if out_dim % 4 or not 4 <= out_dim <= 512:
+            raise NotImplementedError(f"{type(self).__name__} runs out_dim % 4 == 0, 4 <= out_dim "
+                                      f"<= 512 (key_dim = out_dim), got {out_dim}")
+        self.npoint, self.radius, self.nsample = npoint, radius, nsample
+        self.out_dim, self.key_dim, self.inner_dimensions = out_dim, out_dim, list(inner_dimensions)
+        self.is_training, self.bn = is_training, bn
+        self.scope = scope if scope is not None else type(self).__name__
+        self.params = params
+
+    def __call__(self, inputs, is_training=None):
+        xyz, points = inputs
+        training = self.is_training if is_training is None else is_training
+        if pointnet_util._is_empty_points(points):
+            points = None
+        new_xyz, x, idx, _ = pointnet_util.sample_and_group(self.npoint, self.radius, self.nsample,
+                                                           xyz, points, False, True)
+        x = self.blocks(x, training)
+        out = group_attention(_store(self.params), f"{self.scope}/attention", x,
+                              x[:, :, 0], self.key_dim, 16, training)
+        return [new_xyz, out, idx]
+
+
+class AttentionNetLayer(_AttentionNetBase):
+    """attention_layer.py:128-168. [xyz, points] -> [new_xyz, new_points (B, npoint, 16*out_dim),
+    idx]. Variables: '<scope>/block_<i>/...' (InnerAttentionBlock(inner_dimensions[i], out_dim))
+    and '<scope>/attention/{query,key,value}/{kernel,bias}'. The last inner dimension feeds the
+    attention's Dense layers, so any value works."""
+
+    def __init__(self, npoint, out_dim, inner_dimensions, is_training=True, radius=0.1, nsample=32,
+                 bn=True, scope=None, params=None):
+        super().__init__(npoint, out_dim, inner_dimensions, is_training, radius, nsample, bn,
+                         scope, params)
+        self.inner_blocks = [InnerAttentionBlock(d, self.key_dim, scope=f"{self.scope}/block_{i}",
+                                                 params=params)
+                             for i, d in enumerate(self.inner_dimensions)]
+
+    def blocks(self, x, training):
+        for block in self.inner_blocks:
+            x = block(x, training)
+        return x
+
+
+class AttentionNetMLPLayer(_AttentionNetBase):
+    """attention_layer.py:171-210: feed-forward blocks FeedForwardLayer(d, d) with a ReLU between
+    them and none after the last, then the attention. Variables '<scope>/feed_forward_<i>/
+    layer_{1..4}/...' and '<scope>/attention/...'."""
+
+    def __init__(self, npoint, out_dim, inner_dimensions, is_training=True, radius=0.1, nsample=32,
+                 bn=True, scope=None, params=None):
+        super().__init__(npoint, out_dim, inner_dimensions, is_training, radius, nsample, bn,
+                         scope, params)
+        if not self.inner_dimensions:
+            raise InvalidArgumentError("AttentionNetMLPLayer needs at least one inner dimension")
+        self.inner_blocks = [FeedForwardLayer(d, d, scope=f"{self.scope}/feed_forward_{i}",
+                                              params=params)
+                             for i, d in enumerate(self.inner_dimensions)]
+
+    def blocks(self, x, training):
+        for i, block in enumerate(self.inner_blocks):
+            x = block(x, training, relu_out=i + 1 < len(self.inner_blocks))
+        return x

@@ -1,8 +1,8 @@
 // Per-group attention reduction and SA pooling for gfx950.
 //
 // Replaces the reduction core of AttentionLayer.call
-// (attention_points/attention_scannet/attention_layer.py:35-42; instantiated with
-// key_dim = output_dim = 4, num_heads = C/4 at :256-258 and :313-315) — six TF ops per SA
+// (attention_points/attention_scannet/attention_layer.py:35-42; the SA modules build it with
+// key_dim = output_dim = 4, num_heads = C/4, :256-258, :313-315; other key_dim: attn_net.hip) — six TF ops per SA
 // layer (reshape, matmul, div, softmax, matmul, reshape) on 1x4 by 4xns heads — and the
 // pooling variants of pointnet_util.py:130-145 (max / avg / weighted_avg / max_and_avg).
 //

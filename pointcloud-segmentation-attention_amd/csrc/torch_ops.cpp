@@ -12,7 +12,8 @@
 // body returns before its first launch.
 // Autograd for gather_point / group_point / three_interpolate (w.r.t.
 // the points only, tf_sampling.py:44-48, tf_grouping.py:42-46, tf_interpolate.py:29-34) and
-// attn_reduce is registered from Python (torch.library.register_autograd, _torch_ops.py), and
+// attn_reduce (and the attention networks' attn_reduce_kd and head_mix, csrc/attn_net.hip)
+// is registered from Python (torch.library.register_autograd, _torch_ops.py), and
 // so is the training-mode shared-MLP layer's (mlp_layer_train -> mlp_layer_train_grad, and
 // mlp_layer_train_pool -> mlp_layer_train_pool_grad for the layer fused with the max pool), the
 // training-mode attention layer's (attn_kv_train -> attn_kv_train_grad) and the stand-alone
@@ -501,6 +502,87 @@ std::tuple<Tensor, Tensor, Tensor> attn_reduce_grad_hip(const Tensor& Q_, const 
                                 gK.data_ptr<float>(), gV.data_ptr<float>(), stream_of(Q)),
            "attn_reduce_grad");
   return {gQ, gK, gV};
+}
+
+// the reduction for any key_dim (csrc/attn_net.hip); the checks are pn2_attn_reduce_kd's, made
+// here so that a fake tensor meets them too
+void chk_attn_kd(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t kd, const char* op) {
+  TORCH_CHECK_VALUE(Q.dim() == 3 && K.dim() == 4 && V.sizes() == K.sizes() &&
+                        K.size(0) == Q.size(0) && K.size(1) == Q.size(1) && K.size(3) == Q.size(2),
+                    op, " expects Q (B,M,C) and K, V (B,M,ns,C)");
+  TORCH_CHECK_VALUE(kd >= 4 && kd <= 512 && kd % 4 == 0, op,
+                    " expects key_dim % 4 == 0, 4 <= key_dim <= 512");
+  TORCH_CHECK_VALUE(Q.size(2) % kd == 0, op, " expects C % key_dim == 0 (C = heads * key_dim)");
+  TORCH_CHECK_VALUE(K.size(2) >= 1, op, " expects ns >= 1");
+}
+
+Tensor attn_reduce_kd_hip(const Tensor& Q_, const Tensor& K_, const Tensor& V_, int64_t kd) {
+  chk_attn_kd(Q_, K_, V_, kd, "attn_reduce_kd");
+  Tensor Q = dev16(Q_, "Q", at::kFloat), K = dev16(K_, "K", at::kFloat);
+  Tensor V = dev16(V_, "V", at::kFloat);
+  const int B = I(K.size(0)), M = I(K.size(1)), ns = I(K.size(2)), C = I(K.size(3));
+  Tensor out = at::empty({B, M, C}, f32(Q));
+  if (fake(Q)) return out;
+  c10::hip::HIPGuard g(Q.device().index());
+  check_rc(pn2_attn_reduce_kd(F(Q), F(K), F(V), B, M, ns, C, I(kd), out.data_ptr<float>(),
+                              stream_of(Q)), "attn_reduce_kd");
+  return out;
+}
+
+std::tuple<Tensor, Tensor, Tensor> attn_reduce_kd_grad_hip(const Tensor& Q_, const Tensor& K_,
+                                                           const Tensor& V_, const Tensor& go_,
+                                                           int64_t kd) {
+  chk_attn_kd(Q_, K_, V_, kd, "attn_reduce_kd_grad");
+  TORCH_CHECK_VALUE(go_.sizes() == Q_.sizes(),
+                    "attn_reduce_kd_grad expects grad_out shaped like Q");
+  Tensor Q = dev16(Q_, "Q", at::kFloat), K = dev16(K_, "K", at::kFloat);
+  Tensor V = dev16(V_, "V", at::kFloat), go = dev16(go_, "grad_out", at::kFloat);
+  const int B = I(K.size(0)), M = I(K.size(1)), ns = I(K.size(2)), C = I(K.size(3));
+  Tensor gQ = at::empty_like(Q), gK = at::empty_like(K), gV = at::empty_like(V);
+  if (fake(Q)) return {gQ, gK, gV};
+  c10::hip::HIPGuard g(Q.device().index());
+  check_rc(pn2_attn_reduce_kd_grad(F(Q), F(K), F(V), F(go), B, M, ns, C, I(kd),
+                                   gQ.data_ptr<float>(), gK.data_ptr<float>(),
+                                   gV.data_ptr<float>(), stream_of(Q)), "attn_reduce_kd_grad");
+  return {gQ, gK, gV};
+}
+
+// head mixing (InnerAttentionLayer.call, csrc/attn_net.hip): qkv (..., 3*heads*key_dim)
+void chk_head_mix(const Tensor& qkv, int64_t heads, int64_t kd, const char* op) {
+  TORCH_CHECK_VALUE(heads >= 1 && heads <= PN2_HEAD_MIX_MAX_HEADS, op, " expects 1 <= heads <= ",
+                    PN2_HEAD_MIX_MAX_HEADS);
+  TORCH_CHECK_VALUE(kd >= 4 && kd <= 256 && kd % 4 == 0, op,
+                    " expects key_dim % 4 == 0, 4 <= key_dim <= 256");
+  TORCH_CHECK_VALUE(qkv.dim() >= 1 && qkv.size(-1) == 3 * heads * kd, op,
+                    " expects qkv (..., 3 * heads * key_dim) = [Q | K | V]");
+}
+
+Tensor head_mix_hip(const Tensor& qkv_, int64_t heads, int64_t kd) {
+  chk_head_mix(qkv_, heads, kd, "head_mix");
+  Tensor qkv = dev16(qkv_, "qkv", at::kFloat);
+  std::vector<int64_t> shape = qkv.sizes().vec();
+  shape.back() = heads * kd;
+  Tensor out = at::empty(shape, f32(qkv));
+  if (fake(qkv)) return out;
+  c10::hip::HIPGuard g(qkv.device().index());
+  check_rc(pn2_head_mix(F(qkv), out.numel() / (heads * kd), I(heads), I(kd),
+                        out.data_ptr<float>(), stream_of(qkv)), "head_mix");
+  return out;
+}
+
+Tensor head_mix_grad_hip(const Tensor& qkv_, const Tensor& go_, int64_t heads, int64_t kd) {
+  chk_head_mix(qkv_, heads, kd, "head_mix_grad");
+  TORCH_CHECK_VALUE(go_.dim() == qkv_.dim() && go_.size(-1) == heads * kd &&
+                        go_.sizes().slice(0, go_.dim() - 1) ==
+                            qkv_.sizes().slice(0, qkv_.dim() - 1),
+                    "head_mix_grad expects grad_out (..., heads * key_dim) for qkv's rows");
+  Tensor qkv = dev16(qkv_, "qkv", at::kFloat), go = dev16(go_, "grad_out", at::kFloat);
+  Tensor gqkv = at::empty_like(qkv);
+  if (fake(qkv)) return gqkv;
+  c10::hip::HIPGuard g(qkv.device().index());
+  check_rc(pn2_head_mix_grad(F(qkv), F(go), go.numel() / (heads * kd), I(heads), I(kd),
+                             gqkv.data_ptr<float>(), stream_of(qkv)), "head_mix_grad");
+  return gqkv;
 }
 
 Tensor group_pool_hip(const Tensor& x_, const std::optional<Tensor>& gxyz_, int64_t mode) {
@@ -1782,6 +1864,11 @@ TORCH_LIBRARY(pn2, m) {
   m.def("fp_fused(Tensor xyz1, Tensor xyz2, Tensor? points1, Tensor points2) -> Tensor");
   m.def("attn_reduce(Tensor Q, Tensor K, Tensor V) -> Tensor");
   m.def("attn_reduce_grad(Tensor Q, Tensor K, Tensor V, Tensor grad_out) -> (Tensor, Tensor, Tensor)");
+  m.def("attn_reduce_kd(Tensor Q, Tensor K, Tensor V, int key_dim) -> Tensor");
+  m.def("attn_reduce_kd_grad(Tensor Q, Tensor K, Tensor V, Tensor grad_out, int key_dim) -> "
+        "(Tensor, Tensor, Tensor)");
+  m.def("head_mix(Tensor qkv, int heads, int key_dim) -> Tensor");
+  m.def("head_mix_grad(Tensor qkv, Tensor grad_out, int heads, int key_dim) -> Tensor");
   m.def("group_pool(Tensor x, Tensor? grouped_xyz, int mode) -> Tensor");
   m.def("mlp_layer_train(Tensor x, Tensor weight, Tensor? bias, Tensor? gamma, Tensor? beta, "
         "float eps, bool relu) -> (Tensor out, Tensor y, Tensor mean, Tensor var)");
@@ -1872,6 +1959,10 @@ static void register_bodies(torch::Library& m) {
   m.impl("fp_fused", &fp_fused_hip);
   m.impl("attn_reduce", &attn_reduce_hip);
   m.impl("attn_reduce_grad", &attn_reduce_grad_hip);
+  m.impl("attn_reduce_kd", &attn_reduce_kd_hip);
+  m.impl("attn_reduce_kd_grad", &attn_reduce_kd_grad_hip);
+  m.impl("head_mix", &head_mix_hip);
+  m.impl("head_mix_grad", &head_mix_grad_hip);
   m.impl("group_pool", &group_pool_hip);
   m.impl("mlp_layer_train", &mlp_layer_train_hip<false>);
   m.impl("mlp_layer_train_grad", &mlp_layer_train_grad_hip<false>);
