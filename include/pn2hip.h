@@ -660,6 +660,39 @@ int pn2_shared_mlp(const float* x, long long rows, int cin, int nlayers,
  * as pn2_shared_mlp (apart from the buffers it does not take); both are 0 for rows = 0. */
 int pn2_shared_mlp_plan(long long rows, int cin, int nlayers, const pn2_mlp_layer* layers,
                         int* row_tiles, int* tiles_per_wg);
+/* One packed layer over rows at any input width: x (rows,cin) → out (rows,cout),
+ *   out[r][o] = act((sum_f x[r][f] * W[f][o]) * scale[o] + shift[o]),
+ * for the layers whose input row does not fit pn2_shared_mlp's on-chip rows (it refuses from
+ * 1,280 channels up): any cin from 1 to 4,194,304, any cout >= 1. `layer` is one fp32 layer
+ * packed by pn2_mlp_pack, the pack that pn2_shared_mlp reads, unchanged; layer->cin must equal
+ * cin. A layer flagged PN2_MLP_BF16 is refused (fp32 only). The kernel streams K through the
+ * chip in slabs and keeps each 32 x 32 output tile's sum in registers (csrc/mlp_wide.hip).
+ * - Summation order: up to 1,248 input channels (every width pn2_shared_mlp takes) an output is
+ *   one fp32 chain on the matrix cores over the chunks of 8 channels in ascending order, the
+ *   chunk's channels in pn2_shared_mlp's order, and the result is pn2_shared_mlp's, bit for
+ *   bit. A wider row is cut into segments of 512 channels: one such chain per segment, the
+ *   segments' sums added in ascending order (a single chain of thousands of additions would
+ *   round worse than the project's tests allow). No sum is split over waves or workgroups and
+ *   nothing is added with atomics: two runs give equal bits, and the bits depend on cin, never
+ *   on rows or the launch shape.
+ * - Alignment: x is read with 16-byte loads when cin % 4 == 0 and x is 16-byte aligned, out is
+ *   stored in 16-byte units when cout % 4 == 0 and out is 16-byte aligned; any other pointer
+ *   takes the per-float path (slower, the same bits). layer->packed must be 16-byte aligned.
+ * - Limits: 0 <= rows <= 2^31 - 1 (rows = 0: PN2_OK, nothing launched); row offsets into x and
+ *   out are 64-bit, so rows * cin and rows * cout may pass 2^31. Grid x = ceil(rows / (32 *
+ *   row_tiles)) row blocks, grid y = ceil(ceil(cout / 32) / out_tiles_per_wg) <= 65,535.
+ * Null x, out (with rows > 0), layer or layer->packed, cin <= 0 or above 4,194,304,
+ * layer->cout <= 0, rows < 0, a misaligned pack and a bf16 layer return PN2_EINVAL before any
+ * launch. */
+int pn2_dense_wide(const float* x, long long rows, int cin, const pn2_mlp_layer* layer,
+                   float* out, pn2_stream_t stream);
+/* The launch shape pn2_dense_wide would use for these arguments; launches nothing and needs no
+ * device. row_tiles: tiles of 32 rows per workgroup; k_slab: input channels per slab (a
+ * multiple of 8); out_tiles_per_wg: tiles of 32 output columns per workgroup. A workgroup's LDS
+ * is 2 * 32 * row_tiles * (k_slab + 4) * 4 bytes. The same argument checks as pn2_dense_wide
+ * (apart from the buffers it does not take); all three are 0 for rows = 0. */
+int pn2_dense_wide_plan(long long rows, int cin, const pn2_mlp_layer* layer, int* row_tiles,
+                        int* k_slab, int* out_tiles_per_wg);
 
 /* ---------------------------------------------------------------- shared MLP, training -- */
 /* One tf_util.conv2d / conv1d layer with is_training=True (tf_util.py:165-185, batch norm on

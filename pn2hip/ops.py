@@ -62,6 +62,13 @@ with autograd for attn_reduce_kd (Q, K, V) and head_mix (qkv):
                          sqrt(key_dim)) over the point's own heads -> (..., heads * key_dim)
     head_mix_grad(qkv, grad_out, heads, key_dim)        -> grad_qkv
 
+and one packed inference layer at any input width, for the layers whose row the fused MLP kernel
+refuses (1,280 channels and up; csrc/mlp_wide.hip), listed in WIDE_NAMES:
+
+    dense_wide(x, packed, cin, cout, relu)              x (..., cin) through one fp32 layer packed
+                         by pn2_mlp_pack (tf_util.PackedLayer.buf) -> (..., cout); the training
+                         ops above take such widths themselves
+
 and the training-mode segmentation head (csrc/head_train.hip):
 
     dropout(x, keep_prob, seed)                         tf_util.py:594-612 with is_training: the
@@ -143,7 +150,9 @@ TRAIN_BF16_NAMES = ("mlp_layer_train_bf16", "mlp_layer_train_bf16_grad",
                     "mlp_layer_train_pool_bf16", "mlp_layer_train_pool_bf16_grad")
 # the attention networks' reductions (csrc/attn_net.hip; device-only, like NAMES)
 ATTN_NET_NAMES = ("attn_reduce_kd", "attn_reduce_kd_grad", "head_mix", "head_mix_grad")
-for _n in NAMES + HOST_NAMES + FEED_NAMES + TRAIN_BF16_NAMES + ATTN_NET_NAMES:
+# the K-streamed layer over rows at any input width (csrc/mlp_wide.hip; device-only, inference)
+WIDE_NAMES = ("dense_wide",)
+for _n in NAMES + HOST_NAMES + FEED_NAMES + TRAIN_BF16_NAMES + ATTN_NET_NAMES + WIDE_NAMES:
     globals()[_n] = getattr(_ops, _n)
 
-__all__ = list(NAMES + HOST_NAMES + FEED_NAMES + TRAIN_BF16_NAMES + ATTN_NET_NAMES)
+__all__ = list(NAMES + HOST_NAMES + FEED_NAMES + TRAIN_BF16_NAMES + ATTN_NET_NAMES + WIDE_NAMES)

@@ -302,9 +302,19 @@ def plan_accepts(cin, widths):
                                      ctypes.addressof(tpw)) == 0
 
 
+@functools.lru_cache(maxsize=None)
+def wide_accepts(cin, cout):
+    """Whether the K-streamed kernel takes a layer cin -> cout (pn2_dense_wide_plan: host only).
+    It takes every positive width; the grid bounds cout at 32 * 8 * 65,535."""
+    tab = (MlpLayer * 1)(MlpLayer(1 << 20, int(cin), int(cout), 0))
+    out = [ctypes.c_int(0) for _ in range(3)]
+    return lib().pn2_dense_wide_plan(32, int(cin), tab, *(ctypes.addressof(o) for o in out)) == 0
+
+
 def _layer_torch(x, L, is_training, bn_decay):
     """One layer from differentiable torch ops (mlp_torch's arithmetic; the moving averages are
-    updated where they live): what a layer the fused kernel refuses falls back to."""
+    updated where they live): what a layer the fused kernel refuses runs on with
+    ParamStore(wide_layers="torch"), and with is_training on a plain store."""
     p = L.params
     y = x @ p["weights"].to(x.device)
     if p.get("biases") is not None:
@@ -345,22 +355,44 @@ def _packed_chain(store, layers, scopes):
     return store.cached(key, _flat(scopes), tf_util.CONV_SUFFIXES + tf_util.DENSE_SUFFIXES, make)
 
 
+def _packed_wide(store, L, scope):
+    """One layer (tf_util.TorchLayer) that the fused kernel refuses, packed for the K-streamed
+    kernel (tf_util.WideLayer) and cached as _packed_chain caches: fp32 whatever the store's
+    precision is (the kernel has no bf16 form)."""
+    key = ("wide", tuple(_flat([scope])), tuple(L.params["weights"].shape), L.relu,
+           "gamma" in L.params)
+
+    def make():
+        return tf_util.WideLayer(tf_util.PackedLayer(
+            L.params["weights"], L.params.get("biases"), L.params.get("gamma"),
+            L.params.get("beta"), L.params.get("moving_mean"), L.params.get("moving_variance"),
+            relu=L.relu, device=store.device, precision="fp32"))
+
+    return store.cached(key, _flat([scope]), tf_util.CONV_SUFFIXES + tf_util.DENSE_SUFFIXES, make)
+
+
 def run_layers(store, x, layers, scopes, is_training=False, bn_decay=None):
     """x (..., cin) through `layers` (tf_util.TorchLayer each, with the scope(s) of its variables
     in `scopes`). Inference: ONE fused kernel for the chain (tf_util.SharedMLP) when
-    pn2_shared_mlp_plan accepts it, else layer by layer. is_training on a trainable store: the
-    HIP training layers (tf_util.mlp_train; Dense layers have no batch norm), with gradients for
-    x and every variable. Otherwise (is_training on a plain store, or an input that requires a
-    gradient) the torch composition. A single layer whose widths the fused kernel refuses (or, in
-    training, whose transpose it refuses: the input gradient is the same kernel over W^T) runs
-    from torch ops; nothing else falls back."""
+    pn2_shared_mlp_plan accepts it, else layer by layer: a layer the fused kernel refuses (its
+    input row does not fit the LDS) runs on the K-streamed kernel (tf_util.WideLayer over
+    pn2_dense_wide, fp32). is_training on a trainable store: the HIP training layers
+    (tf_util.mlp_train; Dense layers have no batch norm), with gradients for x and every
+    variable; a layer that the fused kernel refuses, or whose transpose it refuses (the input
+    gradient is a layer over W^T), trains in fp32 there, its GEMMs on the K-streamed kernel.
+    Otherwise (is_training on a plain store, or an input that requires a gradient) the torch
+    composition. With ParamStore(wide_layers="torch") the refused layers run from torch ops
+    (_layer_torch) instead, as they did before the K-streamed kernel existed."""
     pu = pointnet_util
     shapes = [tuple(int(s) for s in L.params["weights"].shape) for L in layers]
+    wide_hip = store.wide_layers == "hip"
     if is_training or pu._needs_grad(x):
         hip = bool(is_training) and store.is_trainable
         for L, (cin, cout) in zip(layers, shapes):
             if hip and plan_accepts(cin, (cout,)) and plan_accepts(cout, (cin,)):
                 x = tf_util.mlp_train(x, [L], bn_decay)
+            elif hip and wide_hip and wide_accepts(cin, cout) and wide_accepts(cout, cin):
+                x = tf_util.mlp_train(x, [L], bn_decay, precision="fp32")
             else:
                 x = _layer_torch(x, L, is_training, bn_decay)
         return x
@@ -370,6 +402,8 @@ def run_layers(store, x, layers, scopes, is_training=False, bn_decay=None):
         for L, sc, (cin, cout) in zip(layers, scopes, shapes):
             if plan_accepts(cin, (cout,)):
                 x = _packed_chain(store, [L], [sc])(x)
+            elif wide_hip and wide_accepts(cin, cout):
+                x = _packed_wide(store, L, sc)(x)
             else:
                 x = _layer_torch(device_tensor(x, "inputs", torch.float32),
                                  _device_layer(store, L, sc), False, None)

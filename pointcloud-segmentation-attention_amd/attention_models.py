@@ -11,7 +11,9 @@ seed). model(inputs) returns the logits (B, N, num_class), get_end_points(inputs
 train.train_step_with(model.body, store, ...), and get_loss is pointnet2_sem_seg's.
 
 A feature-propagation MLP whose input is wider than the fused kernel takes (fa_layer1 reads
-512 + 1024 channels here) runs its first layer from torch ops (attention_layer.run_layers).
+512 + 1024 channels here) runs its first layer on the K-streamed kernel (pn2_dense_wide) with
+ParamStore(wide_layers="hip"), from torch ops with the default wide_layers="torch"
+(attention_layer.run_layers).
 """
 from . import pointnet_util, tf_util
 from .attention_layer import (AttentionNetLayer, AttentionNetMLPLayer, _store, plan_accepts,
@@ -23,7 +25,8 @@ NPOINTS = (1024, 256, 64, 16)
 
 def fp_module(store, xyz1, xyz2, points1, points2, mlp, is_training, bn_decay, scope):
     """pointnet_util.pointnet_fp_module; where the fused kernel refuses the MLP's input width,
-    the interpolation and concat kernels, then the layers one by one (run_layers)."""
+    the interpolation and concat kernels, then the layers one by one (run_layers: the wide first
+    layer on pn2_dense_wide or from torch ops, as the store's wide_layers says)."""
     C = (0 if points1 is None else int(points1.shape[2])) + int(points2.shape[2])
     training = is_training or pointnet_util._needs_grad(points1, points2)
     if not training and plan_accepts(C, tuple(mlp)):

@@ -34,6 +34,7 @@
 #include <torch/csrc/autograd/custom_function.h>
 #include <torch/library.h>
 
+#include <climits>
 #include <initializer_list>
 #include <string>
 #include <tuple>
@@ -638,7 +639,35 @@ void linear_rows(const Tensor& in, const Tensor& w, const Tensor& bias, int64_t 
   check_rc((bf16 ? pn2_mlp_pack_bf16 : pn2_mlp_pack)(F(w), F(bias), nullptr, nullptr, cin, cout,
                                                      P(packed), bytes, stream_of(in)), op);
   const pn2_mlp_layer layer = {P(packed), cin, cout, bf16 ? PN2_MLP_BF16 : 0};
+  // a row too wide for the fused kernel's LDS: the K-streamed kernel over the same pack (fp32
+  // only; the bf16 ops keep raising for such a layer)
+  int row_tiles = 0, tiles_per_wg = 0;
+  if (!bf16 && pn2_shared_mlp_plan(rows, cin, 1, &layer, &row_tiles, &tiles_per_wg) == PN2_EINVAL) {
+    check_rc(pn2_dense_wide(F(in), rows, cin, &layer, out.data_ptr<float>(), stream_of(in)), op);
+    return;
+  }
   check_rc(pn2_shared_mlp(F(in), rows, cin, 1, &layer, out.data_ptr<float>(), stream_of(in)), op);
+}
+
+// dense_wide: one packed fp32 layer (pn2_mlp_pack) over rows at any input width, inference:
+// x (..., cin) -> (..., cout) on pn2_dense_wide (csrc/mlp_wide.hip)
+Tensor dense_wide_hip(const Tensor& x_, const Tensor& packed_, int64_t cin, int64_t cout,
+                      bool relu) {
+  TORCH_CHECK_VALUE(cin > 0 && cout > 0 && cin <= INT_MAX && cout <= INT_MAX,
+                    "dense_wide expects positive cin and cout");
+  TORCH_CHECK_VALUE(x_.dim() >= 1 && x_.size(-1) == cin, "dense_wide expects (..., cin) x");
+  const size_t bytes = pn2_mlp_packed_size(I(cin), I(cout));
+  TORCH_CHECK_VALUE(packed_.dim() == 1 && static_cast<size_t>(packed_.numel()) * 4 >= bytes,
+                    "dense_wide expects packed with the pn2_mlp_packed_size(cin, cout) bytes of "
+                    "pn2_mlp_pack");
+  Tensor x = dev(x_, "x", at::kFloat), packed = dev16(packed_, "packed", at::kFloat);
+  Tensor out = at::empty(with_last(x, cout), f32(x));
+  if (fake(x)) return out;
+  c10::hip::HIPGuard g(x.device().index());
+  const pn2_mlp_layer layer = {P(packed), I(cin), I(cout), relu ? PN2_MLP_RELU : 0};
+  check_rc(pn2_dense_wide(F(x), x.numel() / cin, I(cin), &layer, out.data_ptr<float>(),
+                          stream_of(x)), "dense_wide");
+  return out;
 }
 
 // the last layer of a set-abstraction MLP fused with the max pool over nsample
@@ -1868,6 +1897,7 @@ TORCH_LIBRARY(pn2, m) {
   m.def("attn_reduce_kd_grad(Tensor Q, Tensor K, Tensor V, Tensor grad_out, int key_dim) -> "
         "(Tensor, Tensor, Tensor)");
   m.def("head_mix(Tensor qkv, int heads, int key_dim) -> Tensor");
+  m.def("dense_wide(Tensor x, Tensor packed, int cin, int cout, bool relu) -> Tensor");
   m.def("head_mix_grad(Tensor qkv, Tensor grad_out, int heads, int key_dim) -> Tensor");
   m.def("group_pool(Tensor x, Tensor? grouped_xyz, int mode) -> Tensor");
   m.def("mlp_layer_train(Tensor x, Tensor weight, Tensor? bias, Tensor? gamma, Tensor? beta, "
@@ -1964,6 +1994,7 @@ static void register_bodies(torch::Library& m) {
   m.impl("head_mix", &head_mix_hip);
   m.impl("head_mix_grad", &head_mix_grad_hip);
   m.impl("group_pool", &group_pool_hip);
+  m.impl("dense_wide", &dense_wide_hip);
   m.impl("mlp_layer_train", &mlp_layer_train_hip<false>);
   m.impl("mlp_layer_train_grad", &mlp_layer_train_grad_hip<false>);
   m.impl("mlp_layer_train_pool", &mlp_layer_train_pool_hip<false>);

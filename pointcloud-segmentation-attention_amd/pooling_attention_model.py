@@ -5,8 +5,9 @@ get_end_points and body as attention_models' classes.
 
 The levels' features are 16 * out_dim = 1024, 2048, 4096 and 8192 wide, so l3 and l4 read 2051
 and 4099 channels and the first two feature-propagation modules 12288 and 2304: the first layer of
-each of those MLPs is wider than the fused kernel takes and runs from torch ops
-(attention_layer.run_layers; DESIGN.md lists them).
+each of those MLPs is wider than the fused kernel takes and runs on the K-streamed kernel
+(pn2_dense_wide, csrc/mlp_wide.hip) with ParamStore(wide_layers="hip"), from torch ops with the
+default wide_layers="torch" (attention_layer.run_layers; DESIGN.md §3.5c lists them).
 """
 from .attention_models import _Model, get_loss  # noqa: F401
 from .pooling_attention_layer import PoolingAttentionNetLayer

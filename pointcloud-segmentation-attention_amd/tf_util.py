@@ -70,16 +70,34 @@ def check_precision(precision):
     return precision
 
 
+# What runs a layer whose input row the fused MLP kernel refuses (1,280 channels and up; the
+# attention networks have such layers): "hip", the K-streamed kernel (pn2_dense_wide, and the
+# HIP training layers in training), or "torch", a matmul and a hand-written batch norm from torch
+# ops (attention_layer._layer_torch). ParamStore(wide_layers=...) selects it per store. The
+# default stays "torch", what these layers ran on before the kernel existed: the kernel is
+# faster at 1,536 and 2,304 input channels and slower at the pooling model's widest layers
+# (profiles/dense_wide/summary.json); "hip" is the tested opt-in.
+WIDE_LAYERS = ("hip", "torch")
+WIDE_LAYERS_DEFAULT = "torch"
+
+
+def check_wide_layers(value):
+    if value not in WIDE_LAYERS:
+        raise InvalidArgumentError(f"wide_layers must be one of {WIDE_LAYERS}, got {value!r}")
+    return value
+
+
 class ParamStore(dict):
     """TF variable name -> float32 tensor, with the reference's initialisers for misses."""
 
     def __init__(self, *args, seed=0, device="cuda", precision="fp32", train_precision="fp32",
-                 **kw):
+                 wide_layers=WIDE_LAYERS_DEFAULT, **kw):
         super().__init__()
         self.seed = seed
         self.device = device
         self.precision = check_precision(precision)
         self.train_precision = check_precision(train_precision)
+        self.wide_layers = check_wide_layers(wide_layers)
         self.is_trainable = False
         self._packed = {}
         self._stamps = {}
@@ -295,6 +313,26 @@ class SharedMLP:
         check(lib().pn2_shared_mlp(ptr(x), rows, self.cin, n, tab, ptr(out), stream_of(x)),
               "shared_mlp")
         return out
+
+
+class WideLayer:
+    """One fp32 PackedLayer run on the K-streamed kernel (torch.ops.pn2.dense_wide over
+    pn2_dense_wide): any input width, the layers pn2_shared_mlp refuses included."""
+
+    def __init__(self, layer):
+        if layer.precision != "fp32":
+            raise InvalidArgumentError("the K-streamed kernel is fp32 only: pack the layer fp32")
+        self.layer = layer
+        self.cin, self.cout = layer.cin, layer.cout
+
+    def __call__(self, x):
+        """x (..., cin) -> (..., cout)."""
+        x = device_tensor(x, "inputs", torch.float32)
+        if int(x.shape[-1]) != self.cin:
+            raise InvalidArgumentError(f"inputs have {int(x.shape[-1])} channels, the layer "
+                                       f"expects {self.cin}")
+        return _torch_ops.call("dense_wide", x, self.layer.buf, self.cin, self.cout,
+                               self.layer.relu)
 
 
 def packed_mlp(store, scopes, cin, widths, bn=True, relu=True, precision=None):
