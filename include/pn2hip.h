@@ -67,6 +67,9 @@
  *                        benchmark/evaluate.py:58-108 and           pn2_label_lut,
  *                        data_transformation.py:21-67 (label        pn2cpu_scene_vote, ...
  *                        look-ups)                                  (host twins)
+ *   render_ball          pointnet2_tensorflow/utils/              → pn2_render_ball,
+ *                        render_balls_so.cpp:14-56 and the          pn2_render_project,
+ *                        projection of show3d_balls.py:52-74        pn2cpu_render_* (host twins)
  *
  * (reference paths are under pointnet2_tensorflow/tf_ops/{sampling,grouping,interpolation_3d},
  *  pointnet2_tensorflow/utils and attention_points/attention_scannet.)
@@ -1102,6 +1105,71 @@ int pn2cpu_val_chunks(const float* points, const int32_t* labels, const int32_t*
                       const float* label_weights, int L, double min_inside, float* out_points,
                       int32_t* out_labels, int32_t* out_colors, float* out_normals,
                       float* out_weights, int32_t* column, int32_t* kept);
+
+/* ---------------------------------------------------------------- scene rendering ------ */
+
+/* The reference's ball renderer, headless (pointnet2_tensorflow/utils/render_balls_so.cpp
+ * render_ball and the projection of show3d_balls.py:52-74). csrc/render.hip, with host twins in
+ * csrc/cpu_render.cpp; both run the arithmetic of csrc/render_math.h.
+ *
+ * render_ball is a serial loop over points x disk entries in which a pixel keeps the first point
+ * that reaches the greatest depth. Here every pixel holds one 64-bit key,
+ *     ((z2 + 2^31) << 32) | (0xFFFFFFFF - i),      0 = nothing drawn,
+ * and every (point, disk entry) pair applies an unsigned 64-bit atomic max; a second pass shades
+ * the winners. Tie rule: the greatest z2 wins and among equal z2 the lowest point index, the
+ * serial loop's strict `depth < z2`. An integer max commutes: the image is a pure function of the
+ * inputs, the same bits in every run. No float atomics.
+ *
+ * pn2_render_ball renders F frames in one call. ixyz (F,n,3) int32: each frame's x (row), y
+ * (column), z (depth). Colours: c0, c1, c2 (n) fp32 shared by the frames, or, with labels (n)
+ * int32 not NULL, palette (npal,3) fp32 whose row labels[i] is (c0, c1, c2) of point i (a label
+ * outside [0, npal) reads row 0; the look-up runs once per pixel). images (F,h,w,3) uint8.
+ *   radius     r = max(r, 1). The disk's entries are the (dx, dy) with dx*dx + dy*dy < r*r;
+ *              dz = sqrt(double(r*r - dx*dx - dy*dy)), depth offset int(dz), shade
+ *              float(dz / r).
+ *   reach      entry (dx, dy) of point i reaches pixel (x + dx, y + dy) with z2 = z + int(dz) if
+ *              the pixel lies in the image and z2 > -2100000000. A point may lie partly or
+ *              wholly outside.
+ *   depth cue  zmin = min(z) - r and zmax = max(z) + r over all n points of the frame, those
+ *              outside the image too; intensity = min(1.0, (z2 - zmin) / (zmax - zmin) * 0.7 +
+ *              0.3) in double.
+ *   pixel      (shade * c2[i] * intensity, shade * c0[i] * intensity, shade * c1[i] *
+ *              intensity), the reference's channel order: a float product, then a double
+ *              product, then truncation to uint8. Colours are expected in [0, 255] and are
+ *              clamped into it first (NaN: 0), because the reference's conversion is undefined
+ *              outside. A pixel nothing reaches is (bg0, bg1, bg2).
+ * Coordinates are supported for |value| < 2^30 (outside, where the reference's int arithmetic
+ * overflows, an entry whose z2 leaves int32 is not drawn). workspace:
+ * pn2_render_ball_workspace_size(F, h, w) bytes (the keys and each frame's depth range),
+ * 8-byte aligned; the call zeroes it.
+ * PN2_EINVAL, checked before any launch: F, n, h or w negative, n >= 2^31, h * w >= 2^31,
+ * F > 65535, r > PN2_RENDER_MAX_RADIUS, a background byte outside [0, 255], a NULL images, a
+ * workspace that is NULL, misaligned or too small, and for n > 0 a NULL ixyz, a NULL channel
+ * without labels, labels without a palette or with npal < 1. F, h or w = 0 is a no-op; n = 0
+ * returns the background. */
+#define PN2_RENDER_MAX_RADIUS 32767
+size_t pn2_render_ball_workspace_size(int F, int h, int w);
+int pn2_render_ball(const int32_t* ixyz, int F, long long n, const float* c0, const float* c1,
+                    const float* c2, const int32_t* labels, const float* palette, int npal, int r,
+                    int h, int w, int bg0, int bg1, int bg2, uint8_t* images, void* workspace,
+                    size_t workspace_bytes, pn2_stream_t stream);
+/* The viewer's projection, xyz.dot(rotmat) + offset and astype('int32'), for F frames. xyz (n,3)
+ * fp32 (is_f64 = 0) or fp64 (is_f64 != 0), already centred and scaled; mats (F,12) fp64: each
+ * frame's 3x3 matrix R row-major, then the offset. ixyz (F,n,3) int32:
+ *   ixyz[f,i,k] = int32(trunc((x*R[0][k] + y*R[1][k]) + z*R[2][k] + off[k]))
+ * in double, in exactly that order, no contraction; a value outside int32 (or NaN) gives
+ * INT32_MIN as the reference's conversion does on x86. Supported range: |value| < 2^30.
+ * PN2_EINVAL before any launch: F or n negative, n >= 2^31, a NULL buffer, mats (or an fp64
+ * xyz) not 8-byte aligned. F = 0 or n = 0 is a no-op. */
+int pn2_render_project(const void* xyz, int is_f64, long long n, const double* mats, int F,
+                       int32_t* ixyz, pn2_stream_t stream);
+/* The same two functions on HOST pointers in plain C++, synchronous, without workspace: equal
+ * bits. */
+int pn2cpu_render_ball(const int32_t* ixyz, int F, long long n, const float* c0, const float* c1,
+                       const float* c2, const int32_t* labels, const float* palette, int npal,
+                       int r, int h, int w, int bg0, int bg1, int bg2, uint8_t* images);
+int pn2cpu_render_project(const void* xyz, int is_f64, long long n, const double* mats, int F,
+                          int32_t* ixyz);
 
 #ifdef __cplusplus
 }

@@ -33,7 +33,7 @@ MODULES = ("tf_sampling", "tf_grouping", "tf_interpolate", "pointnet_util", "tf_
            "generate_predictions", "evaluate", "pointnet2_sem_seg_attention",
            "pointnet2_sem_seg_attention_and_pooling", "pointnet2_sem_seg_attention_single_layer",
            "compute_class_weights", "attention_models", "pooling_attention_layer",
-           "pooling_attention_model")
+           "pooling_attention_model", "show3d_balls", "visualization")
 for _name in MODULES:
     _mod = getattr(_impl, _name)
     globals()[_name] = _mod

@@ -127,6 +127,18 @@ Meta and CPU kernels too (host twins with equal bits, csrc/cpu_feed.cpp):
     val_chunks(points, labels, colors, normals, counts, sel, inner, choice, u, npoints,
                label_weights, min_inside)               draws, keep test, compaction, gathers
                          -> (points, labels, colors, normals, weights, column, kept)
+
+and scene rendering (csrc/render.hip; pointnet2_tensorflow/utils/render_balls_so.cpp and
+show3d_balls.py:52-74), listed in RENDER_NAMES: CUDA, Meta and CPU kernels (host twins with
+equal bits, csrc/cpu_render.cpp), no autograd:
+
+    render_ball(ixyz, c0, c1, c2, labels, palette, r, h, w, background)   the reference's
+                         render_ball for (F,n,3) int32 frames: a 64-bit atomic max of
+                         ((z2 + 2^31) << 32) | (0xFFFFFFFF - i) per (point, disk entry), then a
+                         resolve pass; three (n) colour channels, or labels and a palette
+                         -> (F,h,w,3) uint8
+    render_project(xyz, mats)                           the viewer's xyz.dot(rotmat) + offset and
+                         astype('int32') for (F,12) float64 frames   -> (F,n,3) int32
 """
 import importlib
 
@@ -152,7 +164,11 @@ TRAIN_BF16_NAMES = ("mlp_layer_train_bf16", "mlp_layer_train_bf16_grad",
 ATTN_NET_NAMES = ("attn_reduce_kd", "attn_reduce_kd_grad", "head_mix", "head_mix_grad")
 # the K-streamed layer over rows at any input width (csrc/mlp_wide.hip; device-only, inference)
 WIDE_NAMES = ("dense_wide",)
-for _n in NAMES + HOST_NAMES + FEED_NAMES + TRAIN_BF16_NAMES + ATTN_NET_NAMES + WIDE_NAMES:
+# scene rendering (csrc/render.hip; CUDA, Meta and CPU kernels, like FEED_NAMES)
+RENDER_NAMES = ("render_ball", "render_project")
+_ALL = (NAMES + HOST_NAMES + FEED_NAMES + TRAIN_BF16_NAMES + ATTN_NET_NAMES + WIDE_NAMES +
+        RENDER_NAMES)
+for _n in _ALL:
     globals()[_n] = getattr(_ops, _n)
 
-__all__ = list(NAMES + HOST_NAMES + FEED_NAMES + TRAIN_BF16_NAMES + ATTN_NET_NAMES + WIDE_NAMES)
+__all__ = list(_ALL)

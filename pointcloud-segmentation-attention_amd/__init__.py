@@ -33,6 +33,11 @@ Drop-in modules (reference names, argument order, shapes, dtypes, error messages
   pooling_attention_layer  PoolingAttentionNetLayer
   attention_models         AttentionNetModel, AttentionNetFeatureModel, AttentionNetMLPModel
   pooling_attention_model  PoolingAttentionNetModel
+  show3d_balls           showpoints: the reference's ball viewer, headless (the image comes back as
+                         a device tensor; any number of views per call)
+  visualization          label_colors, mask_unannotated, orbit, render_scene, animate_prediction,
+                         labels_over_training (attention_points/visualization: a scene coloured
+                         by label, as frames on disk)
 Everything runs the gfx950 kernels of libpn2hip.so (C ABI: include/pn2hip.h).
 
 The directory name has hyphens, so import it with importlib:
@@ -41,8 +46,8 @@ The directory name has hyphens, so import it with importlib:
 from . import attention_layer, attention_models, complete_scene_loader, compute_class_weights, data_transformation, evaluate, \
     generate_predictions, grid, plan, pointnet2_sem_seg, pointnet2_sem_seg_attention, \
     pointnet2_sem_seg_attention_and_pooling, pointnet2_sem_seg_attention_single_layer, \
-    pointnet2_sem_seg_features, pointnet_util, pooling_attention_layer, pooling_attention_model, shard, stack, synth, tf_grouping, tf_interpolate, tf_sampling, \
-    tf_util, train
+    pointnet2_sem_seg_features, pointnet_util, pooling_attention_layer, pooling_attention_model, shard, show3d_balls, stack, synth, tf_grouping, tf_interpolate, tf_sampling, \
+    tf_util, train, visualization
 from .data_transformation import random_rotate, rotation_cs, scene_val_chunks
 from .generate_predictions import predict_scene
 from .train import (CLASS_WEIGHTS, AdamOptimizer, SegMetrics, eval_model, eval_step, get_bn_decay,
@@ -54,6 +59,6 @@ __all__ = ["tf_sampling", "tf_grouping", "tf_interpolate", "pointnet_util", "att
            "generate_predictions", "evaluate", "predict_scene", "eval_step",
            "pointnet2_sem_seg_attention", "pointnet2_sem_seg_attention_and_pooling",
            "pointnet2_sem_seg_attention_single_layer", "attention_models", "pooling_attention_layer",
-           "pooling_attention_model", "compute_class_weights", "random_rotate", "rotation_cs",
+           "pooling_attention_model", "compute_class_weights", "show3d_balls", "visualization", "random_rotate", "rotation_cs",
            "scene_val_chunks", "CLASS_WEIGHTS", "get_data_tensors", "eval_model", "train_step_with",
            "AdamOptimizer", "SegMetrics", "get_learning_rate", "get_bn_decay", "train_step", "lib", "LIB_PATH", "InvalidArgumentError", "Pn2RuntimeError"]

@@ -19,7 +19,9 @@ seg_confusion, mean_iou) mutate their arguments in place and are not differentia
 prediction ops (csrc/predict.hip: scene_vote, scene_labels, map_back_rows, label_lut) are
 integers and copied bytes; they also have CPU kernels (the host twins, equal bits), and so have
 the training feed's ops (csrc/feed.hip, pn2_val_select in csrc/scene.hip: feed_batch, val_select,
-val_chunks; host twins in csrc/cpu_feed.cpp), whose arithmetic is fixed operation by operation.
+val_chunks; host twins in csrc/cpu_feed.cpp), whose arithmetic is fixed operation by operation,
+and the rendering ops (csrc/render.hip: render_ball, render_project; host twins in
+csrc/cpu_render.cpp), which carry no autograd.
 
 The mirror modules (tf_sampling, tf_grouping, tf_interpolate, attention_layer) call these ops
 for every reference-signature call; the pn2hip alias package re-exports them as pn2hip.ops.

@@ -25,8 +25,9 @@
 // tf_interpolate.cpp:187,222,262), through the host twins pn2cpu_* (csrc/cpu_interp.cpp);
 // and for the four prediction ops (scene_vote, scene_labels, map_back_rows, label_lut: integers
 // and copied bytes, host twins in csrc/cpu_predict.cpp with equal bits) and the three feed ops
-// (feed_batch, val_select, val_chunks: host twins in csrc/cpu_feed.cpp with equal bits). Those ten
-// bodies are templates over HIP / CPU; every other op has no CPU kernel, so a CPU tensor fails in the
+// (feed_batch, val_select, val_chunks: host twins in csrc/cpu_feed.cpp with equal bits) and the two
+// rendering ops (render_ball, render_project: host twins in csrc/cpu_render.cpp with equal bits).
+// Those twelve bodies are templates over HIP / CPU; every other op has no CPU kernel, so a CPU tensor fails in the
 // dispatcher (no CPU fallback).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPGuard.h>
@@ -1612,6 +1613,103 @@ Tensor7 val_chunks_impl(const Tensor& points_, const Tensor& labels_,
   return {op_, ol, oc, on, ow, column, kept};
 }
 
+// ---- scene rendering (csrc/render.hip): the reference's render_ball as a 64-bit atomic max per
+// pixel and a resolve pass, and the viewer's projection. CUDA, Meta and CPU (the host twins of
+// csrc/cpu_render.cpp: equal bits) from one body each. No autograd.
+// an fp64 argument: the kernels read it with 8-byte loads, so a view at an odd offset is copied
+Tensor f64_arg(const Tensor& t) {
+  Tensor c = t.contiguous();
+  if (!fake(c) && reinterpret_cast<uintptr_t>(c.data_ptr()) % 8 != 0) c = c.clone();
+  return c;
+}
+
+template <bool HIP>
+Tensor render_ball_impl(const Tensor& ixyz_, const std::optional<Tensor>& c0_,
+                        const std::optional<Tensor>& c1_, const std::optional<Tensor>& c2_,
+                        const std::optional<Tensor>& labels_, const std::optional<Tensor>& palette_,
+                        int64_t r, int64_t h, int64_t w, at::IntArrayRef background) {
+  const char* op = "render_ball";
+  TORCH_CHECK_VALUE(ixyz_.dim() == 3 && ixyz_.size(2) == 3, op, " expects (F,n,3) int32 ixyz, got ",
+                    ixyz_.sizes());
+  feed_device<HIP>(ixyz_, op);
+  Tensor ixyz = feed_arg(ixyz_, ixyz_, at::kInt, op, "ixyz");
+  const int64_t nf = ixyz.size(0), n = ixyz.size(1);
+  TORCH_CHECK_VALUE(nf <= 65535 && n <= INT32_MAX, op, " expects F <= 65535 and n below 2^31");
+  TORCH_CHECK_VALUE(h >= 0 && w >= 0 && h * w <= INT32_MAX, op,
+                    " expects 0 <= h, w and h * w below 2^31, got ", h, " x ", w);
+  TORCH_CHECK_VALUE(r <= PN2_RENDER_MAX_RADIUS, op, " expects r <= ", PN2_RENDER_MAX_RADIUS,
+                    ", got ", r);
+  TORCH_CHECK_VALUE(background.size() == 3, op, " expects three background bytes");
+  for (int64_t b : background)
+    TORCH_CHECK_VALUE(b >= 0 && b <= 255, op, " expects background bytes in [0, 255], got ", b);
+  Tensor c0, c1, c2, labels, palette;
+  if (has(labels_)) {
+    TORCH_CHECK_VALUE(has(palette_) && !has(c0_) && !has(c1_) && !has(c2_), op,
+                      " expects labels with a palette and without colour channels");
+    labels = feed_arg(*labels_, ixyz_, at::kInt, op, "labels");
+    palette = feed_arg(*palette_, ixyz_, at::kFloat, op, "palette");
+    TORCH_CHECK_VALUE(labels.dim() == 1 && labels.size(0) == n, op, " expects (n) labels, got ",
+                      labels.sizes());
+    TORCH_CHECK_VALUE(palette.dim() == 2 && palette.size(0) >= 1 && palette.size(1) == 3 &&
+                          palette.size(0) <= INT32_MAX,
+                      op, " expects (npal,3) palette with npal >= 1, got ", palette.sizes());
+  } else {
+    TORCH_CHECK_VALUE(has(c0_) && has(c1_) && has(c2_) && !has(palette_), op,
+                      " expects three colour channels, or labels and a palette");
+    c0 = feed_arg(*c0_, ixyz_, at::kFloat, op, "c0");
+    c1 = feed_arg(*c1_, ixyz_, at::kFloat, op, "c1");
+    c2 = feed_arg(*c2_, ixyz_, at::kFloat, op, "c2");
+    TORCH_CHECK_VALUE(c0.dim() == 1 && c0.size(0) == n && c1.sizes() == c0.sizes() &&
+                          c2.sizes() == c0.sizes(),
+                      op, " expects (n) c0, c1 and c2, got ", c0.sizes(), ", ", c1.sizes(), " and ",
+                      c2.sizes());
+  }
+  Tensor images = at::empty({nf, h, w, 3}, ixyz.options().dtype(at::kByte));
+  if (fake(ixyz) || images.numel() == 0) return images;
+  const int bg0 = I(background[0]), bg1 = I(background[1]), bg2 = I(background[2]);
+  const int npal = palette.defined() ? I(palette.size(0)) : 0;
+  const int32_t* lp = labels.defined() ? Ii(labels) : nullptr;
+  if (HIP) {
+    c10::hip::HIPGuard g(ixyz.device().index());
+    const size_t ws = pn2_render_ball_workspace_size(I(nf), I(h), I(w));
+    Tensor work = at::empty({static_cast<int64_t>(ws / 8)}, ixyz.options().dtype(at::kLong));
+    check_rc(pn2_render_ball(Ii(ixyz), I(nf), n, F(c0), F(c1), F(c2), lp, F(palette), npal, I(r),
+                             I(h), I(w), bg0, bg1, bg2, images.data_ptr<uint8_t>(),
+                             work.data_ptr(), ws, stream_of(ixyz)), op);
+  } else {
+    check_rc(pn2cpu_render_ball(Ii(ixyz), I(nf), n, F(c0), F(c1), F(c2), lp, F(palette), npal,
+                                I(r), I(h), I(w), bg0, bg1, bg2, images.data_ptr<uint8_t>()), op);
+  }
+  return images;
+}
+
+template <bool HIP>
+Tensor render_project_impl(const Tensor& xyz_, const Tensor& mats_) {
+  const char* op = "render_project";
+  TORCH_CHECK_VALUE(xyz_.dim() == 2 && xyz_.size(1) == 3 && xyz_.size(0) <= INT32_MAX, op,
+                    " expects (n,3) xyz, got ", xyz_.sizes());
+  TORCH_CHECK_VALUE(xyz_.scalar_type() == at::kFloat || xyz_.scalar_type() == at::kDouble, op,
+                    " expects float32 or float64 xyz, got ", xyz_.scalar_type());
+  TORCH_CHECK_VALUE(mats_.dim() == 2 && mats_.size(1) == 12 && mats_.size(0) <= INT32_MAX, op,
+                    " expects (F,12) float64 mats, got ", mats_.sizes());
+  feed_device<HIP>(xyz_, op);
+  const bool f64 = xyz_.scalar_type() == at::kDouble;
+  Tensor xyz = f64 ? f64_arg(xyz_) : xyz_.contiguous();
+  Tensor mats = f64_arg(feed_arg(mats_, xyz_, at::kDouble, op, "mats"));
+  const int64_t nf = mats.size(0), n = xyz.size(0);
+  Tensor ixyz = at::empty({nf, n, 3}, i32(xyz));
+  if (fake(xyz) || ixyz.numel() == 0) return ixyz;
+  if (HIP) {
+    c10::hip::HIPGuard g(xyz.device().index());
+    check_rc(pn2_render_project(xyz.data_ptr(), f64, n, mats.data_ptr<double>(), I(nf),
+                                ixyz.data_ptr<int32_t>(), stream_of(xyz)), op);
+  } else {
+    check_rc(pn2cpu_render_project(xyz.data_ptr(), f64, n, mats.data_ptr<double>(), I(nf),
+                                   ixyz.data_ptr<int32_t>()), op);
+  }
+  return ixyz;
+}
+
 // ---- training-mode geometry (csrc/geom_train.hip): the fused forward kernels of the SA and FP
 // modules with their gradients as ordered gathers (no float atomics, no zero fill, no slices)
 void chk_group_concat_grad(const Tensor& grad, const Tensor& idx, int64_t N, int64_t C,
@@ -1962,6 +2060,9 @@ TORCH_LIBRARY(pn2, m) {
         "-> (Tensor xyz, Tensor features, Tensor smpw)");
   m.def("val_select(Tensor points, Tensor bounds, float margin, float inner_margin) -> "
         "(Tensor counts, Tensor sel, Tensor inner)");
+  m.def("render_ball(Tensor ixyz, Tensor? c0, Tensor? c1, Tensor? c2, Tensor? labels, "
+        "Tensor? palette, int r, int h, int w, int[] background) -> Tensor");
+  m.def("render_project(Tensor xyz, Tensor mats) -> Tensor");
   m.def("val_chunks(Tensor points, Tensor labels, Tensor? colors, Tensor? normals, Tensor counts, "
         "Tensor sel, Tensor inner, Tensor? choice, Tensor? u, int npoints, Tensor label_weights, "
         "float min_inside) -> (Tensor points, Tensor labels, Tensor colors, Tensor normals, "
@@ -2024,6 +2125,8 @@ static void register_bodies(torch::Library& m) {
   m.impl("feed_batch", &feed_batch_impl<true>);
   m.impl("val_select", &val_select_impl<true>);
   m.impl("val_chunks", &val_chunks_impl<true>);
+  m.impl("render_ball", &render_ball_impl<true>);
+  m.impl("render_project", &render_project_impl<true>);
 }
 TORCH_LIBRARY_IMPL(pn2, CUDA, m) { register_bodies(m); }
 TORCH_LIBRARY_IMPL(pn2, Meta, m) { register_bodies(m); }
@@ -2048,4 +2151,7 @@ TORCH_LIBRARY_IMPL(pn2, CPU, m) {
   m.impl("feed_batch", &feed_batch_impl<false>);
   m.impl("val_select", &val_select_impl<false>);
   m.impl("val_chunks", &val_chunks_impl<false>);
+  // scene rendering's host twins (csrc/cpu_render.cpp)
+  m.impl("render_ball", &render_ball_impl<false>);
+  m.impl("render_project", &render_project_impl<false>);
 }
